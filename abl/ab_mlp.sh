@@ -3,7 +3,7 @@
 rounds=$1; shift; wl="$1"; shift
 for r in $(seq 1 $rounds); do
   for t in "$@"; do
-    LDE_LIB_PATH=$PWD/abl/liblde_$t.so python3 bench.py $wl --steps 20 --warmup 5 --no-cpu-baseline --no-other-sensealg 2>/dev/null | python3 -c "
+    LDE_LIB_PATH=$PWD/abl/liblde_$t.so python3 bench.py --full $wl --steps 20 --warmup 5 --no-cpu-baseline --no-other-sensealg 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d.get('kernel_ms',{})

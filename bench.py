@@ -11,10 +11,15 @@ t=0:0.05:2.45, Tsit5 abstol=1e-6 reltol=1e-3), batch 256 PER GPU (weak scaling: 
 trajectory with no data-path collective; a collective exists only for workloads with shared RHS-MLP
 weights, whose dW is all-reduced once per step).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0 (the driver's contract). A plain run sets up, warms up, times the K steps and
+prints the headline (metric, value, unit, higher_is_better, dtype, ms_per_step, …). `--full` adds what takes runs of
+its own, as before:
   "roofline":     dominant kernel's algorithmic bytes / its average launch duration (HIP events on the launch stream)
   "cpu_baseline": the CPU oracle (a port of the same algorithm, OpenMP over trajectories like the reference's
-                  EnsembleThreads [REF src/models/GOKU.jl:121]) timed on this box's host cores, bounded sample.
+                  EnsembleThreads [REF src/models/GOKU.jl:121]) timed on this box's host cores, bounded sample
+  and the per-kernel / per-call figures, the other definition of the gradient, the strong-scaling rider (N > 1) and
+  `--sweep`'s large batches (which implies --full).
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -210,6 +215,39 @@ def cpu_baseline(w, d_native, ts, z0, theta, W, dz, budget_s=12.0):
     return out
 
 
+DUMP_BUDGET_BYTES = 60 << 20     # (under 64 MB however a megabyte is counted, .npy headers included)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays a caller of the timed path receives from its last step, as DIR/<name>.npy — float64 stays
+    float64, everything else (f32, bf16, int32 return codes) is written as float32. At most DUMP_BUDGET_BYTES in all: an array
+    that does not fit its share is replaced by a fixed sample of its elements (seeded by its name, flat order kept), so that two
+    builds run with the same arguments compare element for element."""
+    import zlib
+
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu()
+            a = (a if a.dtype == torch.float64 else a.float()).numpy()
+        a = np.asarray(a)
+        host[name] = np.ascontiguousarray(a if a.dtype == np.float64 else a.astype(np.float32))
+    left, n_left = DUMP_BUDGET_BYTES, len(host)
+    for name, a in sorted(host.items(), key=lambda kv: kv[1].nbytes):
+        share = left // n_left
+        if a.nbytes > share:
+            k = share // a.itemsize
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
+        n_left -= 1
+
+
 def cpu_model():
     try:
         with open("/proc/cpuinfo") as f:
@@ -332,36 +370,9 @@ def run_decoder(args, torch, dist, world, rank, local):
         el = float(tmax.item())
     assert int(ret.abs().sum().item()) == 0 and bool(torch.isfinite(flat).all()) and float(flat.abs().max()) > 0
 
-    def ev_ms(fn, n):
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
-        for a, b in evs:
-            a.record(stream); fn(); b.record(stream)
-        torch.cuda.synchronize()
-        return float(np.mean([a.elapsed_time(b) for a, b in evs]))
-
-    n = min(args.steps, 50)
-    parts = {
-        "reconstructor_forward": ev_ms(lambda: ck(lib.lde_chain_forward_save(chains["rec"][0], p(zout), N, p(xhat), p(saved["rec"]), sp), chains["rec"][0], "f"), n),
-        "reconstructor_backward": ev_ms(lambda: ck(lib.lde_chain_backward_saved(chains["rec"][0], p(zout), p(xhat), p(dxh), p(saved["rec"]), N, p(dz), p(gW["rec"]), sp), chains["rec"][0], "b"), n),
-        "reconstructor_backward_recompute": ev_ms(lambda: ck(lib.lde_chain_backward(chains["rec"][0], p(zout), p(xhat), p(dxh), N, p(dz), p(gW["rec"]), sp), chains["rec"][0], "b"), n),
-        "lde_forward": ev_ms(lambda: L.check(lib.lde_forward(h, p(z0), p(th), tsp, T, B, p(zout), p(ret), sp), h, "f"), n),
-        "lde_adjoint": ev_ms(lambda: L.check(lib.lde_adjoint(h, p(zout), p(th), tsp, T, B, p(dz), p(dz0), p(dth), C.c_void_p(), sp), h, "a"), n),
-        "latent_out_forward_x2": ev_ms(lambda: lib.lde_chain_group_forward_save(2, lo_h, lo_x, lo_N, lo_y, lo_sv, sp), n),
-        "latent_out_backward_x2": ev_ms(lambda: lib.lde_chain_group_backward_saved(2, lo_h, lo_x, lo_y, lo_dy, lo_sv, lo_N, lo_dx, lo_dW, sp), n),
-        "latent_out_forward_separate_calls": ev_ms(lambda: (lib.lde_chain_forward_save(chains["lo_z0"][0], p(zt), B, p(z0), p(saved["lo_z0"]), sp),
-                                                            lib.lde_chain_forward_save(chains["lo_th"][0], p(tt), B, p(th), p(saved["lo_th"]), sp)), n),
-        "latent_out_backward_separate_calls": ev_ms(lambda: (lib.lde_chain_backward_saved(chains["lo_z0"][0], p(zt), p(z0), p(dz0), p(saved["lo_z0"]), B, p(dzt), p(gW["lo_z0"]), sp),
-                                                             lib.lde_chain_backward_saved(chains["lo_th"][0], p(tt), p(th), p(dth), p(saved["lo_th"]), B, p(dtt), p(gW["lo_th"]), sp)), n),
-    }
-    mac = lambda sizes: sum(a * b for a, b in zip(sizes[:-1], sizes[1:]))
-    F_rec = 2 * mac(specs["rec"][0]) * N
-    F_lo = 2 * (mac(specs["lo_z0"][0]) + mac(specs["lo_th"][0])) * B
-    # algorithmic flops of a step: forward F, pullback 2F (input + weight gradients); the solve's flops are negligible here
-    flops = 3 * (F_rec + F_lo)
+    # the last timed step's results, before the --full probes below launch the same calls on these buffers again
+    dumped = {k: v.clone() for k, v in dict(x_hat=xhat, z_hat=zout, retcode=ret, dW=flat, dl_z0=dzt, dl_theta=dtt).items()} if args.dump_outputs else None
     ms_per_step = el / args.steps * 1e3
-    dom = max(("reconstructor_forward", "reconstructor_backward"), key=lambda k: parts[k])
-    dom_flops = F_rec if dom == "reconstructor_forward" else 2 * F_rec
-    ach = dom_flops / (parts[dom] * 1e-3) / 1e12
     out = {
         "metric": "trajectories/sec (latent_out -> solve -> reconstructor, forward + pullback) goku_decoder",
         "value": B * world * args.steps / el, "unit": "trajectories/s", "n_gpus": world, "steps": args.steps,
@@ -370,22 +381,51 @@ def run_decoder(args, torch, dist, world, rank, local):
         "config": {"workload": f"goku_decoder: {DECODER['desc']}", "batch_per_gpu": B, "global_batch": B * world,
                    "save_points": T, "columns_through_the_reconstructor": N,
                    "parallelism": f"dp{world} (batch sharded by trajectory; one all-reduce of the flat decoder gradient per step)"},
-        "roofline": dict(bound="mfma", kernel=f"lde_chain {dom}", achieved=ach, peak=FP32_PEAK_TFLOPS if args.dtype == "f32" else BF16_PEAK_TFLOPS, unit="TFLOP/s",
-                         frac=ach / (FP32_PEAK_TFLOPS if args.dtype == "f32" else BF16_PEAK_TFLOPS), traffic=None, alg_flops_per_launch=dom_flops, avg_launch_ms=parts[dom],
-                         whole_step_TFLOPs=flops / (ms_per_step * 1e-3) / 1e12),
-        "kernel_ms": parts,
+        "roofline": None, "cpu_baseline": None,
     }
-    hv, tr, trk = chain_hbm_view("goku_decoder", args.dtype != "f32")
-    if hv:   # the bf16 chain kernels move 2.4–4 TB/s of counter bytes: HBM-bound, not MFMA-bound — both views side by side
-        out["roofline"]["traffic"] = tr
-        out["roofline"]["traffic_kernel"] = trk
-        out["roofline"]["hbm_view"] = hv
-        if args.dtype != "f32":
-            out["roofline"]["bound"] = "hbm (mixed: see hbm_view; the MFMA fraction is quoted beside it)"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = decoder_cpu_baseline(specs, weights, d, ts, zt.cpu().numpy(), tt.cpu().numpy(), dxh.cpu().numpy(), B, T)
-    else:
-        out["cpu_baseline"] = None
+    if args.full:   # per-call HIP-event times, the MFMA roofline of the dominant chain kernel (+ its HBM view), the CPU baseline
+        def ev_ms(fn, n):
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+            for a, b in evs:
+                a.record(stream); fn(); b.record(stream)
+            torch.cuda.synchronize()
+            return float(np.mean([a.elapsed_time(b) for a, b in evs]))
+
+        n = min(args.steps, 50)
+        parts = {
+            "reconstructor_forward": ev_ms(lambda: ck(lib.lde_chain_forward_save(chains["rec"][0], p(zout), N, p(xhat), p(saved["rec"]), sp), chains["rec"][0], "f"), n),
+            "reconstructor_backward": ev_ms(lambda: ck(lib.lde_chain_backward_saved(chains["rec"][0], p(zout), p(xhat), p(dxh), p(saved["rec"]), N, p(dz), p(gW["rec"]), sp), chains["rec"][0], "b"), n),
+            "reconstructor_backward_recompute": ev_ms(lambda: ck(lib.lde_chain_backward(chains["rec"][0], p(zout), p(xhat), p(dxh), N, p(dz), p(gW["rec"]), sp), chains["rec"][0], "b"), n),
+            "lde_forward": ev_ms(lambda: L.check(lib.lde_forward(h, p(z0), p(th), tsp, T, B, p(zout), p(ret), sp), h, "f"), n),
+            "lde_adjoint": ev_ms(lambda: L.check(lib.lde_adjoint(h, p(zout), p(th), tsp, T, B, p(dz), p(dz0), p(dth), C.c_void_p(), sp), h, "a"), n),
+            "latent_out_forward_x2": ev_ms(lambda: lib.lde_chain_group_forward_save(2, lo_h, lo_x, lo_N, lo_y, lo_sv, sp), n),
+            "latent_out_backward_x2": ev_ms(lambda: lib.lde_chain_group_backward_saved(2, lo_h, lo_x, lo_y, lo_dy, lo_sv, lo_N, lo_dx, lo_dW, sp), n),
+            "latent_out_forward_separate_calls": ev_ms(lambda: (lib.lde_chain_forward_save(chains["lo_z0"][0], p(zt), B, p(z0), p(saved["lo_z0"]), sp),
+                                                                lib.lde_chain_forward_save(chains["lo_th"][0], p(tt), B, p(th), p(saved["lo_th"]), sp)), n),
+            "latent_out_backward_separate_calls": ev_ms(lambda: (lib.lde_chain_backward_saved(chains["lo_z0"][0], p(zt), p(z0), p(dz0), p(saved["lo_z0"]), B, p(dzt), p(gW["lo_z0"]), sp),
+                                                                 lib.lde_chain_backward_saved(chains["lo_th"][0], p(tt), p(th), p(dth), p(saved["lo_th"]), B, p(dtt), p(gW["lo_th"]), sp)), n),
+        }
+        mac = lambda sizes: sum(a * b for a, b in zip(sizes[:-1], sizes[1:]))
+        F_rec = 2 * mac(specs["rec"][0]) * N
+        F_lo = 2 * (mac(specs["lo_z0"][0]) + mac(specs["lo_th"][0])) * B
+        # algorithmic flops of a step: forward F, pullback 2F (input + weight gradients); the solve's flops are negligible here
+        flops = 3 * (F_rec + F_lo)
+        dom = max(("reconstructor_forward", "reconstructor_backward"), key=lambda k: parts[k])
+        dom_flops = F_rec if dom == "reconstructor_forward" else 2 * F_rec
+        ach = dom_flops / (parts[dom] * 1e-3) / 1e12
+        out["roofline"] = dict(bound="mfma", kernel=f"lde_chain {dom}", achieved=ach, peak=FP32_PEAK_TFLOPS if args.dtype == "f32" else BF16_PEAK_TFLOPS, unit="TFLOP/s",
+                               frac=ach / (FP32_PEAK_TFLOPS if args.dtype == "f32" else BF16_PEAK_TFLOPS), traffic=None, alg_flops_per_launch=dom_flops, avg_launch_ms=parts[dom],
+                               whole_step_TFLOPs=flops / (ms_per_step * 1e-3) / 1e12)
+        out["kernel_ms"] = parts
+        hv, tr, trk = chain_hbm_view("goku_decoder", args.dtype != "f32")
+        if hv:   # the bf16 chain kernels move 2.4–4 TB/s of counter bytes: HBM-bound, not MFMA-bound — both views side by side
+            out["roofline"]["traffic"] = tr
+            out["roofline"]["traffic_kernel"] = trk
+            out["roofline"]["hbm_view"] = hv
+            if args.dtype != "f32":
+                out["roofline"]["bound"] = "hbm (mixed: see hbm_view; the MFMA fraction is quoted beside it)"
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = decoder_cpu_baseline(specs, weights, d, ts, zt.cpu().numpy(), tt.cpu().numpy(), dxh.cpu().numpy(), B, T)
     for ch, _ in chains.values():
         lib.lde_chain_destroy(ch)
     lib.lde_destroy(h)
@@ -393,6 +433,8 @@ def run_decoder(args, torch, dist, world, rank, local):
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, dumped)
         emit(out)
 
 
@@ -576,6 +618,10 @@ def run_goku_step(args, torch, dist, world, rank, local):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         el = float(tmax.item())
     assert bool(torch.isfinite(loss))
+    if rank == 0 and args.dump_outputs:   # the loss of the last timed step, and the parameters and gradients that step left behind
+        grads = [q.grad.reshape(-1).float() for q in params if q.grad is not None]
+        dump_outputs(args.dump_outputs, dict(loss=loss.reshape(1), params=torch.cat([q.detach().reshape(-1).float() for q in params]),
+                                             grads=torch.cat(grads) if grads else None))
     N = B * T
     mac = lambda sizes: sum(a * b for a, b in zip(sizes[:-1], sizes[1:]))
     F_dense = 2 * (mac(enc.feature_extractor.sizes) + mac(dec.reconstructor.sizes)) * N
@@ -795,7 +841,14 @@ def main():
     ap.add_argument("--no-other-sensealg", action="store_true", help="skip the second measurement with the other definition of the gradient (profiling runs: one set of kernels per trace)")
     ap.add_argument("--sweep", action="store_true", help="also report a large-batch sweep (extra keys, rank 0)")
     ap.add_argument("--dry-launch", action="store_true", help="exercise the N-rank launch path without GPUs (gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: per-kernel and per-call times, roofline, CPU baseline, the other definition of "
+                         "the gradient, the strong-scaling rider (N > 1); without it a run times the K steps and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.sweep:   # (the large-batch sweep is one of the --full extras)
+        args.full = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args, sys.argv[1:])
@@ -885,8 +938,9 @@ def main():
         torch.cuda.synchronize()
         return float(np.mean(br)), float(np.median(br)), a.elapsed_time(b) / n
 
-    def measure(B, seed_shift, detail, sensealg=None):
-        """W warm-up steps, then exactly K timed steps of lde_forward + lde_adjoint on B resident trajectories."""
+    def measure(B, seed_shift, detail, sensealg=None, keep=False):
+        """W warm-up steps, then exactly K timed steps of lde_forward + lde_adjoint on B resident trajectories (detail: the --full
+        probes after them; keep: a copy of the last timed step's outputs for --dump-outputs)."""
         d, ts, z0, theta, W, dz = build_problem(w, B, seed_shift=seed_shift, sensealg=sensealg or sense)
         h = C.c_void_p()
         L.check(lib.lde_create(C.byref(d), C.byref(h)), None, "lde_create")
@@ -991,6 +1045,8 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             el = float(tmax.item())
         res = dict(el=el, B=B, nW=nW, problem=(d, ts, z0, theta, W, dz), graphed=bool(graphs))
+        if keep:   # the last timed step's results, before the probes below launch the same calls on these buffers again
+            res["outputs"] = {k: v.clone() for k, v in dict(z_hat=zout, retcode=ret, dz0=dz0, dtheta=dth, dW=dW).items() if v is not None}
         if detail:
             nprobe = min(max(args.steps, 20), 200)
             fwd()
@@ -1037,6 +1093,67 @@ def main():
         res["handle"] = h
         return res
 
+    def full_figures(m, out):
+        """--full: per-launch HIP-event times of lde_forward / lde_adjoint, the dominant kernel's roofline (+ counter bytes from the committed
+        profiles), the per-step event figures, the solver statistics and the device-synchronised per-call time."""
+        B, h = m["B"], m["handle"]
+        disc = sense == "discrete"
+        (fwd_ms, fwd_med, fwd_stream), (bwd_ms, bwd_med, bwd_stream) = m["fwd"], m["bwd"]
+        fstat, bstat = m["fstat"], m["bstat"]
+
+        fb, bb = alg_bytes_per_traj(w)
+        dom, dom_ms, dom_stream, dom_bytes = ("lde_adjoint", bwd_ms, bwd_stream, bb) if bwd_ms >= fwd_ms else ("lde_forward", fwd_ms, fwd_stream, fb)
+        Ff = flops_per_eval(w)
+        # flops of the pullback per evaluation it reports: the continuous adjoint's evaluations are fused (forward + z-VJP + weight gradient:
+        # 3·F_f); the discrete sweep reports 2S per accepted step — S forward-only (F_f) and S fused (3·F_f): 2·F_f on average
+        adj_f = 2 if disc else 3
+        if Ff and w["batching"] == "coupled":
+            flops = (fstat["nfe"] * Ff + bstat["nfe"] * adj_f * Ff) * B
+        else:
+            flops = fstat["nfe"] * Ff + bstat["nfe"] * adj_f * Ff
+        if Ff:  # MLP right-hand side: compute-bound on the f32 MFMA/VALU rate
+            # the DOMINANT kernel = the adjoint's solve kernel: its flops are the recomputed forward pass and the z-VJP of every evaluation
+            # (2·F_f each; the weight-gradient product, the third F_f, is counted where it runs — inside that kernel or in the tail)
+            cols = B if w["batching"] == "coupled" else 1
+            ph = m.get("phase_ms")
+            # k_mlp64 / k_mlpb / k_mlpc fold gW inside the solve kernel (what follows it is the fixed-order row sum: a few µs); the tile
+            # kernels and k_mlpw / k_mlpv stage (a_l, δ_l) for k_mlp_dw, whose product then is the tail's
+            # which family ran: reported by the library (option "adjoint_family": 1 k_mlp64, 2 k_mlpb, 3 k_mlpc fold in the kernel), not guessed
+            in_kernel_dw = m.get("adjoint_family", -1) in (1, 2, 3)
+            dom_flops = bstat["nfe"] * ((2 if in_kernel_dw else 1.5) if disc else (3 if in_kernel_dw else 2)) * Ff * cols
+            dom_ms_k = ph[0] if ph else bwd_stream
+            ach = dom_flops / (dom_ms_k * 1e-3) / 1e12
+            whole = flops / ((fwd_stream + bwd_stream) * 1e-3) / 1e12
+            roof = dict(bound="mfma", kernel="lde_adjoint: solve kernel (HIP events of lde_set_phase_timing)", achieved=ach, peak=FP32_PEAK_TFLOPS,
+                        unit="TFLOP/s", frac=ach / FP32_PEAK_TFLOPS, traffic=None, alg_flops_per_launch=dom_flops, avg_launch_ms=dom_ms_k,
+                        tail=dict(what="weight-gradient product + fixed-order sums after the solve kernel", avg_launch_ms=ph[1] if ph else None,
+                                  alg_flops=0 if in_kernel_dw else bstat["nfe"] * Ff * cols),
+                        whole_step=dict(kernel="lde_forward+lde_adjoint", achieved=whole, frac=whole / FP32_PEAK_TFLOPS, alg_flops_per_step=flops,
+                                        avg_launch_ms=fwd_stream + bwd_stream, avg_launch_ms_bracketed=fwd_ms + bwd_ms))
+        else:
+            # average launch duration of the dominant call over n back-to-back launches (HIP events on the launch stream); the
+            # bracketed figure (an event pair around every single launch) carries the events' own ≈ 2.5 µs
+            ach = dom_bytes * B / (dom_stream * 1e-3) / 1e9
+            roof = dict(bound="hbm", kernel=dom, achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS,
+                        traffic=None, alg_bytes_per_launch=dom_bytes * B, avg_launch_ms=dom_stream, avg_launch_ms_bracketed=dom_ms)
+
+        # HBM traffic of the dominant kernel from the committed rocprofv3 PMC passes of this same command
+        lib.lde_last_kernel.restype = C.c_char_p
+        launched = {"lde_forward": (lib.lde_last_kernel(h, 0) or b"").decode(), "lde_adjoint": (lib.lde_last_kernel(h, 1) or b"").decode()}
+        attach_traffic(roof, args.workload + ("_discrete" if disc else ""), B, mlp=bool(Ff), full_batch=(B == w["B"]), dom=None if Ff else dom, launched=launched)
+        roof["launched_kernels"] = launched
+
+        out.update({
+            "roofline": roof,
+            "kernel_ms": {"lde_forward": fwd_stream, "lde_adjoint": bwd_stream, "lde_forward_bracketed": fwd_ms, "lde_adjoint_bracketed": bwd_ms},
+            # per-step figures from HIP events (an event pair around every step): the wall-clock mean above is K steps / elapsed
+            "ms_per_step_events": {"median": m["step"][1], "mean": m["step"][0], "back_to_back": m["step"][2], "samples": min(max(args.steps, 20), 200)},
+            "solver_stats": {"forward": fstat, "adjoint": bstat},
+            # SURVEY.md §8(d): device-synchronised per call, median of ≥ 100 (host enqueue + wake-up included) — beside the pipelined figure above
+            "per_call_synchronised": {"median_ms": m["sync_call"][0], "mean_ms": m["sync_call"][1], "samples": m["sync_call"][2],
+                                      "value": B * world / (m["sync_call"][0] * 1e-3), "unit": "trajectories/s"},
+        })
+
     sense = resolve_sensealg(args.workload, args.sensealg)
     Bw = args.batch or w["B"]
     if args.scaling == "strong":
@@ -1046,57 +1163,12 @@ def main():
     else:
         B = Bw
         global_batch = Bw * world
-    m = measure(B, rank, True)
+    m = measure(B, rank, args.full, keep=bool(args.dump_outputs))
     el, nW, h = m["el"], m["nW"], m["handle"]
     d, ts, z0, theta, W, dz = m["problem"]
     ms_per_step = el / args.steps * 1e3
     value = global_batch * args.steps / el
-    (fwd_ms, fwd_med, fwd_stream), (bwd_ms, bwd_med, bwd_stream) = m["fwd"], m["bwd"]
-    fstat, bstat = m["fstat"], m["bstat"]
-
-    fb, bb = alg_bytes_per_traj(w)
-    dom, dom_ms, dom_stream, dom_bytes = ("lde_adjoint", bwd_ms, bwd_stream, bb) if bwd_ms >= fwd_ms else ("lde_forward", fwd_ms, fwd_stream, fb)
-    Ff = flops_per_eval(w)
-    # flops of the pullback per evaluation it reports: the continuous adjoint's evaluations are fused (forward + z-VJP + weight gradient:
-    # 3·F_f); the discrete sweep reports 2S per accepted step — S forward-only (F_f) and S fused (3·F_f): 2·F_f on average
     disc = sense == "discrete"
-    adj_f = 2 if disc else 3
-    if Ff and w["batching"] == "coupled":
-        flops = (fstat["nfe"] * Ff + bstat["nfe"] * adj_f * Ff) * B
-    else:
-        flops = fstat["nfe"] * Ff + bstat["nfe"] * adj_f * Ff
-    if Ff:  # MLP right-hand side: compute-bound on the f32 MFMA/VALU rate
-        # the DOMINANT kernel = the adjoint's solve kernel: its flops are the recomputed forward pass and the z-VJP of every evaluation
-        # (2·F_f each; the weight-gradient product, the third F_f, is counted where it runs — inside that kernel or in the tail)
-        cols = B if w["batching"] == "coupled" else 1
-        ph = m.get("phase_ms")
-        # k_mlp64 / k_mlpb / k_mlpc fold gW inside the solve kernel (what follows it is the fixed-order row sum: a few µs); the tile
-        # kernels and k_mlpw / k_mlpv stage (a_l, δ_l) for k_mlp_dw, whose product then is the tail's
-        # which family ran: reported by the library (option "adjoint_family": 1 k_mlp64, 2 k_mlpb, 3 k_mlpc fold in the kernel), not guessed
-        in_kernel_dw = m.get("adjoint_family", -1) in (1, 2, 3)
-        dom_flops = bstat["nfe"] * ((2 if in_kernel_dw else 1.5) if disc else (3 if in_kernel_dw else 2)) * Ff * cols
-        dom_ms_k = ph[0] if ph else bwd_stream
-        ach = dom_flops / (dom_ms_k * 1e-3) / 1e12
-        whole = flops / ((fwd_stream + bwd_stream) * 1e-3) / 1e12
-        roof = dict(bound="mfma", kernel="lde_adjoint: solve kernel (HIP events of lde_set_phase_timing)", achieved=ach, peak=FP32_PEAK_TFLOPS,
-                    unit="TFLOP/s", frac=ach / FP32_PEAK_TFLOPS, traffic=None, alg_flops_per_launch=dom_flops, avg_launch_ms=dom_ms_k,
-                    tail=dict(what="weight-gradient product + fixed-order sums after the solve kernel", avg_launch_ms=ph[1] if ph else None,
-                              alg_flops=0 if in_kernel_dw else bstat["nfe"] * Ff * cols),
-                    whole_step=dict(kernel="lde_forward+lde_adjoint", achieved=whole, frac=whole / FP32_PEAK_TFLOPS, alg_flops_per_step=flops,
-                                    avg_launch_ms=fwd_stream + bwd_stream, avg_launch_ms_bracketed=fwd_ms + bwd_ms))
-    else:
-        # average launch duration of the dominant call over n back-to-back launches (HIP events on the launch stream); the
-        # bracketed figure (an event pair around every single launch) carries the events' own ≈ 2.5 µs
-        ach = dom_bytes * B / (dom_stream * 1e-3) / 1e9
-        roof = dict(bound="hbm", kernel=dom, achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS,
-                    traffic=None, alg_bytes_per_launch=dom_bytes * B, avg_launch_ms=dom_stream, avg_launch_ms_bracketed=dom_ms)
-
-    # HBM traffic of the dominant kernel from the committed rocprofv3 PMC passes of this same command
-    lib.lde_last_kernel.restype = C.c_char_p
-    launched = {"lde_forward": (lib.lde_last_kernel(h, 0) or b"").decode(), "lde_adjoint": (lib.lde_last_kernel(h, 1) or b"").decode()}
-    attach_traffic(roof, args.workload + ("_discrete" if disc else ""), B, mlp=bool(Ff), full_batch=(B == w["B"]), dom=None if Ff else dom, launched=launched)
-    roof["launched_kernels"] = launched
-
     out = {
         "metric": "trajectories/sec (fwd+adjoint) GOKU pendulum, batch=256, 1/2/4/8 GPU"
         if args.workload == "goku_pendulum" else f"trajectories/sec (fwd+adjoint) {args.workload}",
@@ -1109,21 +1181,16 @@ def main():
                    if not nW else f"dp{world} (batch sharded; one all-reduce of dW per step: {comm_kind})",
                    "submission": "hipGraph replays of ≤ 256 captured steps (each step = lde_forward + lde_adjoint)" if m.get("graphed")
                    else "stream launches (two per step)"},
-        "roofline": roof,
-        "kernel_ms": {"lde_forward": fwd_stream, "lde_adjoint": bwd_stream, "lde_forward_bracketed": fwd_ms, "lde_adjoint_bracketed": bwd_ms},
-        # per-step figures from HIP events (an event pair around every step): the wall-clock mean above is K steps / elapsed
-        "ms_per_step_events": {"median": m["step"][1], "mean": m["step"][0], "back_to_back": m["step"][2], "samples": min(max(args.steps, 20), 200)},
-        "solver_stats": {"forward": fstat, "adjoint": bstat},
+        "roofline": None,
         "sensealg": ("LDE_SENSE_DISCRETE (the exact derivative of the discrete solve on its accepted steps: the reference's ForwardDiffSensitivity)" if disc
                      else "continuous adjoint (reverse-time solve; time-parallel on the analytic GOKU path)")
         + (" — the reference's default for this workload" if sense == REF_SENSEALG[args.workload] else " — forced by --sensealg"),
-        # device-synchronised per call, median of ≥ 100 (host enqueue + wake-up included) — beside the pipelined figure above
-        "per_call_synchronised": {"median_ms": m["sync_call"][0], "mean_ms": m["sync_call"][1], "samples": m["sync_call"][2],
-                                  "value": B * world / (m["sync_call"][0] * 1e-3), "unit": "trajectories/s"},
     }
+    if args.full:
+        full_figures(m, out)
 
     # the same K steps with the other definition of the gradient, beside the headline (every rank takes part: the timing's barriers are collective)
-    if not args.no_other_sensealg:
+    if args.full and not args.no_other_sensealg:
         other = "continuous" if disc else "discrete"
         mo = measure(B, rank, False, sensealg=other)
         out["other_sensealg"] = {"sensealg": other, "value": global_batch * args.steps / mo["el"], "unit": "trajectories/s",
@@ -1137,7 +1204,7 @@ def main():
         out["training_step"] = {"what": "lde_set_weights_device + lde_forward + lde_adjoint (option adjoint_overwrite: dW written, no fill launch)",
                                 "ms_per_step": st_[2], "ms_per_step_bracketed": st_[0], "value": global_batch / (st_[2] * 1e-3),
                                 "adjoint_family": m.get("adjoint_family")}
-    if world > 1 and args.scaling == "weak" and args.workload == "goku_pendulum":
+    if args.full and world > 1 and args.scaling == "weak" and args.workload == "goku_pendulum":
         # the same ranks on the GLOBAL batch of the metric (256 split over the GPUs): the strong-scaling figure beside the weak one
         lo, hi = shard_bounds(Bw, rank, world)
         try:   # (an extra: whatever happens here must not cost the line above)
@@ -1150,6 +1217,7 @@ def main():
 
     if rank == 0 and args.sweep and not nW:
         sweep = {}
+        fb, bb = alg_bytes_per_traj(w)
         for Bs in (1 << 12, 1 << 16, 1 << 20):
             d2, ts2, z02, th2, _, dz2 = build_problem(w, Bs)
             a = torch.from_numpy(z02).to(dev); b_ = torch.from_numpy(th2).to(dev); c = torch.from_numpy(dz2).to(dev)
@@ -1177,7 +1245,7 @@ def main():
         dist.destroy_process_group()
     # the CPU baseline is taken AFTER the timed region and after the process group is gone (the other ranks have exited or are
     # exiting: nothing competes for the host cores); on N > 1 too, with a shorter budget, so that every line carries it
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(w, d, ts, z0, theta, W, dz, budget_s=12.0 if world == 1 else 6.0)
         except Exception as e:   # noqa: BLE001 — the GPU figure is measured; a broken CPU leg is reported, not fatal
@@ -1192,6 +1260,8 @@ def main():
             for k_ in ("reverse_sweep", "continuous_adjoint"):
                 if cb.get(k_):
                     out["vs_cpu_baseline"]["ratio_vs_" + k_] = out["value"] / cb[k_]["value"] / max(world, 1)
+        if "outputs" in m:
+            dump_outputs(args.dump_outputs, m["outputs"])
         emit(out)
 
 

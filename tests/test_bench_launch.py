@@ -54,3 +54,22 @@ def test_world_size_mismatch_is_an_error():
     # a torchrun environment is taken as is (no self-launch): the dry path reports what the environment says
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert d["n_gpus"] == 1
+
+
+def test_dump_outputs_keeps_dtypes_and_the_size_bound(tmp_path):
+    """--dump-outputs' writer: float64 stays float64, the rest becomes float32; an array over its share of the 64 MB is replaced by a fixed
+    sample of its elements, the same one run after run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(20_000_000, dtype=torch.float32)
+    arrs = dict(ret=torch.zeros(5, dtype=torch.int32), w=np.ones(3), big=big, none=None)
+    bench.dump_outputs(str(tmp_path / "a"), arrs)
+    bench.dump_outputs(str(tmp_path / "b"), arrs)
+    got = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"ret.npy", "w.npy", "big.npy"}
+    assert got["ret.npy"].dtype == np.float32 and got["w.npy"].dtype == np.float64
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in got) <= 64e6
+    s = got["big.npy"]
+    assert 0 < s.size < big.numel() and (np.diff(s) >= 0).all() and np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))

@@ -1,4 +1,5 @@
-"""GPU: bench.py keeps the driver's contract — one JSON line with the agreed keys, for the metric workload and the others."""
+"""GPU: bench.py keeps the driver's contract — one JSON line with the agreed keys, for the metric workload and the others. The full line
+(`--full`: roofline, CPU baseline, per-kernel figures) and the plain one (the headline only, --dump-outputs beside it)."""
 import json
 import os
 import subprocess
@@ -21,7 +22,7 @@ def _run(*args):
 
 
 def test_metric_line():
-    d = _run("--steps", "20", "--warmup", "3")
+    d = _run("--steps", "20", "--warmup", "3", "--full")
     assert KEYS <= set(d), KEYS - set(d)
     assert d["metric"].startswith("trajectories/sec (fwd+adjoint) GOKU pendulum, batch=256") and d["unit"] == "trajectories/s"
     assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 3 and d["higher_is_better"] is True and d["scaling"] == "weak"
@@ -61,7 +62,7 @@ def test_two_ranks_on_one_gpu_run_the_n_gt_1_path(workload):
     env = dict(os.environ, LDE_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
                         "--master-port", "29641", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3",
-                        "--workload", workload], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--workload", workload, "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2500:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines
@@ -80,6 +81,29 @@ def test_two_ranks_on_one_gpu_run_the_n_gt_1_path(workload):
 
 @pytest.mark.parametrize("workload,bound", [("c2", "mfma"), ("goku_decoder", "mfma"), ("goku_step", "mfma")])
 def test_other_workloads(workload, bound):
-    d = _run("--workload", workload, "--steps", "5", "--warmup", "2", "--no-cpu-baseline")
+    d = _run("--workload", workload, "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--full")
     assert KEYS <= set(d) and d["roofline"]["bound"] == bound and d["value"] > 0 and d["cpu_baseline"] is None
     assert workload in d["config"]["workload"] and "model" not in d["config"]
+
+
+HEADLINE = {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"}
+
+
+@pytest.mark.parametrize("workload,names", [("goku_pendulum", {"z_hat", "retcode", "dz0", "dtheta"}),
+                                            ("goku_decoder", {"x_hat", "z_hat", "retcode", "dW", "dl_z0", "dl_theta"}),
+                                            ("goku_step", {"loss", "params", "grads"})])
+def test_plain_run_prints_the_headline_and_dumps_its_outputs(tmp_path, workload, names):
+    """Without --full a run times its K steps and prints the headline only; --dump-outputs writes what the last timed step computed."""
+    import numpy as np
+    d = _run("--workload", workload, "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path))
+    assert HEADLINE <= set(d) and d["steps"] == 7 and d["warmup"] == 2 and d["higher_is_better"] is True and d["value"] > 0
+    assert d["ms_per_step"] > 0 and d["cpu_baseline"] is None and "other_sensealg" not in d and "kernel_ms" not in d
+    assert {f[:-4] for f in os.listdir(tmp_path)} == names
+    total = 0
+    for n in names:
+        a = np.load(tmp_path / (n + ".npy"))
+        total += (tmp_path / (n + ".npy")).stat().st_size
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), n
+    assert total <= 64e6
+    if "retcode" in names:
+        assert (np.load(tmp_path / "retcode.npy") == 0).all()

@@ -59,8 +59,8 @@ def test_lde_comm_two_ranks(tmp_path):
 @pytest.mark.skipif(_ngpu() < 2, reason="needs two GPUs on the node")
 @pytest.mark.parametrize("workload", ["goku_pendulum", "c3"])
 def test_bench_two_gpus(workload):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--workload", workload],
-                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--workload", workload,
+                        "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
