@@ -86,12 +86,26 @@ enum lde_sensealg {
                                            sequence under ForwardDiffSensitivity differs from its primal solve's; here the primal sequence is used.
                                            With LDE_BATCH_COUPLED_GLOBAL every rank records the common step sequence and its own columns' states; the
                                            sweep has no step control, so the sharded pullback exchanges nothing. */
-  LDE_SENSE_PARALLEL_CHECKPOINTED  = 2  /* checkpointed adjoint, parallel in time: with z reset at every save time the T-1 save
+  LDE_SENSE_PARALLEL_CHECKPOINTED  = 2, /* checkpointed adjoint, parallel in time: with z reset at every save time the T-1 save
                                            intervals are independent and λ enters linearly, so each (trajectory, interval) pair
                                            integrates the interval's transition operator (λ_j = M_j λ_{j+1}, g += n_j·λ_{j+1}) on
                                            its own lane and a short scan composes them. Same continuous adjoint as mode 0, agreeing
                                            to solver tolerance. Implemented for analytic right-hand sides with per-trajectory batching;
                                            for MLP right-hand sides / coupled batching mode 0 runs instead. */
+  LDE_SENSE_FORWARD_DUAL           = 4  /* ForwardDiffSensitivity as the reference EXECUTES it during training: the solve on dual numbers
+                                           [REF examples/pendulum_friction-less/pendulum.jl:8-11], [REF src/models/GOKU.jl:107, :121]. Every state
+                                           component carries its value and its partials with respect to (x₀, v₀, L) (seeds e₀, e₁, 0) through the
+                                           stages, the solution weights, the FSAL slope and the saveat interpolant (Tsit5's free interpolant, RK4's
+                                           cubic Hermite), and the step control sees them: ‖u_i‖ = sqrt(v² + Σ_q p_q²) in the Hairer initial step,
+                                           in the scale abstol + reltol·max(‖y_i‖, ‖y_new,i‖) and in EEst — OrdinaryDiffEq's ODE_DEFAULT_NORM on duals.
+                                           The accepted steps therefore differ from LDE_SENSE_DISCRETE's (the primal sequence): this mode gives
+                                           the reference's training-time ẑ and gradient. lde_forward writes ẑ and J_j = ∂ẑ(t_j)/∂(x₀, v₀, L) into
+                                           the dual record (below); lde_adjoint forms dz0 = Σ_j J_j[:, 0:2]ᵀ dz_out_j, dθ = Σ_j J_j[:, 2]ᵀ dz_out_j
+                                           from it and nothing else (dW must be NULL). A failed trajectory: NaN ẑ block, retcode != 0, zero
+                                           gradients. Analytic right-hand sides (LDE_RHS_PENDULUM, LDE_RHS_PENDULUM_FRICTION) with
+                                           LDE_BATCH_PER_TRAJECTORY, Tsit5 adaptive or fixed-step and RK4 fixed-step; any other description gives
+                                           LDE_ERR_UNSUPPORTED (lde_desc_error names the missing piece). Opt-in: lde_problem_desc_default keeps
+                                           LDE_SENSE_DISCRETE. */
 };
 
 enum lde_activation { LDE_ACT_RELU = 0, LDE_ACT_TANH = 1 };
@@ -166,6 +180,10 @@ const char* lde_build_info(void);
  * of the discrete solve. A binding of `NODE` sets LDE_SENSE_BACKSOLVE_CHECKPOINTED itself (DiffEqFlux's InterpolatingAdjoint
  * [REF src/models/LatentODE.jl:67-70]); the time-parallel continuous adjoint (LDE_SENSE_PARALLEL_CHECKPOINTED) stays selectable. */
 int lde_problem_desc_default(lde_problem_desc* desc);
+
+/* Why lde_create would refuse `desc`: "" when the description is valid, otherwise the reason (the text that goes with its
+ * LDE_ERR_INVALID_ARG / LDE_ERR_UNSUPPORTED — no handle exists to ask lde_last_error). Static or thread-local storage; never NULL. */
+const char* lde_desc_error(const lde_problem_desc* desc);
 
 /* Number of floats in the flat weight vector implied by desc (0 for analytic RHS). */
 int64_t lde_num_weights(const lde_problem_desc* desc);
@@ -257,6 +275,15 @@ int lde_set_global_sum_peers(lde_handle* h, int rank, int nranks, void* const* m
  * Capacity = option "record_capacity" accepted steps per sequence (default max(64, 4·T)); a solve that needs more leaves the record
  * incomplete and the discrete adjoint then returns NaN gradients with retcode LDE_RET_MAXITERS in its statistics — never a silently
  * truncated sweep. The reference has no counterpart (dual numbers carry the derivative through the solve [REF src/models/GOKU.jl:121]). */
+/* The dual record (sensealg = LDE_SENSE_FORWARD_DUAL) goes through the same calls: lde_step_record_bytes(h, B, T) sizes it, lde_set_step_record
+ * hands a caller's block over (or the handle's own serves, ONE outstanding forward per handle), lde_forward writes it, lde_adjoint reads it.
+ * Its size is fixed by (B, T) — it cannot overflow, and lde_step_record_status never reports an overflow for it (capacity = maxiters).
+ * Layout (A(x) = x rounded up to a multiple of 256 bytes), from the 256-byte aligned base:
+ *     n  int32 [B]                at 0                      accepted steps of trajectory b; −retcode when its solve failed
+ *     J  float [T][2][3][B]       at A(4B)                  J[j][i][q][b] = ∂ẑ_i(t_j)/∂(x₀, v₀, L)_q of trajectory b (trajectory fastest)
+ *     t  double [cap][B]          at A(4B) + A(24TB)        option "step_trace" = 1 only: start time of accepted step s of trajectory b at s·B + b
+ *     dt double [cap][B]          at … + A(8·cap·B)         … and its size; cap = lde_step_record_capacity(h, T)
+ * J of a failed trajectory is zero. With "step_trace" = 1 lde_get_step_record(h, 0, …) returns the accepted steps (what a checker replays). */
 int64_t lde_step_record_bytes(const lde_handle* h, int B, int T);
 int lde_set_step_record(lde_handle* h, void* rec_dev, int64_t bytes);
 /* Did the record hold the solve? lde_step_record_capacity(h, T) = the accepted steps per sequence a record made now would hold;

@@ -59,11 +59,16 @@ const LDE_SENSE_BACKSOLVE_CHECKPOINTED = Int32(0)   # InterpolatingAdjoint / Bac
 const LDE_SENSE_BACKSOLVE              = Int32(1)   # BacksolveAdjoint(checkpointing = false)
 const LDE_SENSE_PARALLEL_CHECKPOINTED  = Int32(2)   # the time-parallel continuous adjoint (analytic right-hand sides): selectable, not a default
 const LDE_SENSE_DISCRETE               = Int32(3)   # ForwardDiffSensitivity(): the exact derivative of the discrete solve
+const LDE_SENSE_FORWARD_DUAL           = Int32(4)   # ForwardDiffSensitivity() as upstream EXECUTES it in training: the solve on duals, norm included
 # `Pendulum()` carries ForwardDiffSensitivity() [REF examples/pendulum_friction-less/pendulum.jl:8-11], splatted into solve() at
 # [REF src/models/GOKU.jl:107, :121]: LDE_SENSE_DISCRETE reproduces that gradient definition (to f32 round-off on the same steps; the one
 # stated deviation: the primal step sequence is differentiated, upstream's norm also sees the dual partials — measured at 1.5e-4 in ẑ and
 # 4e-5 in the gradient at the example's tolerances, tests/test_oracle_dual.py).
-sensealg_code(::ForwardDiffSensitivity) = LDE_SENSE_DISCRETE
+# Opt-in (default off: today's mapping): `LdeNative.DUAL_NORM[] = true` maps ForwardDiffSensitivity to LDE_SENSE_FORWARD_DUAL instead — the
+# dual-number solve whose error norm sees the partials, i.e. upstream's training-time step sequence (GOKU path: analytic right-hand sides).
+# Set it before the first call on a `diffeq`: its handle is built once.
+const DUAL_NORM = Ref(false)
+sensealg_code(::ForwardDiffSensitivity) = DUAL_NORM[] ? LDE_SENSE_FORWARD_DUAL : LDE_SENSE_DISCRETE
 sensealg_code(::InterpolatingAdjoint)   = LDE_SENSE_BACKSOLVE_CHECKPOINTED
 sensealg_code(s::BacksolveAdjoint)      = s.checkpointing ? LDE_SENSE_BACKSOLVE_CHECKPOINTED : LDE_SENSE_BACKSOLVE
 sensealg_code(::Any)                    = LDE_SENSE_DISCRETE            # (any other discrete-exact tag, e.g. ReverseDiffAdjoint)
@@ -136,7 +141,8 @@ function ChainRulesCore.rrule(::typeof(diffeq_layer), decoder::Decoder{T}, l̂, 
     function pullback(Δ)
         Δẑ = ROCArray{Float32}(unthunk(Δ))
         dẑ₀ = similar(ẑ₀); dθ̂ = similar(θ̂)
-        rec2 = record_that_holds(h, rec, ẑ, θ̂, ts)                # (a solve with more accepted steps than the record holds: grow it, repeat the forward solve)
+        rec2 = record_that_holds(h, rec, ẑ, θ̂, ts)                # (a solve with more accepted steps than the record holds: grow it, repeat the forward solve;
+                                                                  #  a dual record — LDE_SENSE_FORWARD_DUAL — cannot overflow and is passed through)
         with_step_record(h, rec2) do
             rc = ccall((:lde_adjoint, liblde), Cint,
                        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float64}, Cint, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{Float32},
@@ -206,13 +212,13 @@ function with_step_record(f, h::LdeHandle, rec)
         ccall((:lde_set_step_record, liblde), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), h.ptr, C_NULL, 0)
     end
 end
-new_step_record(h::LdeHandle, sensealg, B, T) = sensealg == LDE_SENSE_DISCRETE ?
+new_step_record(h::LdeHandle, sensealg, B, T) = (sensealg == LDE_SENSE_DISCRETE || sensealg == LDE_SENSE_FORWARD_DUAL) ?
     ROCArray{UInt8}(undef, ccall((:lde_step_record_bytes, liblde), Int64, (Ptr{Cvoid}, Cint, Cint), h.ptr, B, T)) : nothing
 # The reference's ForwardDiffSensitivity differentiates any solve up to maxiters [REF src/models/GOKU.jl:121]; a record holds
 # "record_capacity" steps per trajectory (default max(64, 4T)). Before the pullback: did it hold the solve? If not, raise the capacity and
 # repeat the (deterministic) forward solve into a larger record — never NaN gradients into an optimiser (include/lde.h: lde_step_record_status).
 function record_that_holds(h::LdeHandle, rec, ẑ, θ̂, ts)
-    rec === nothing && return rec
+    (rec === nothing || h.sensealg == LDE_SENSE_FORWARD_DUAL) && return rec
     Dp, B, T = size(ẑ)
     nmax = Ref{Int32}(0); cap = Ref{Int32}(0)
     ccall((:lde_step_record_status, liblde), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ref{Int32}, Ref{Int32}, Ptr{Cvoid}),

@@ -18,14 +18,14 @@ LDE_MAX_LAYERS = 6
 RHS_PENDULUM, RHS_PENDULUM_FRICTION, RHS_MLP, RHS_PENDULUM_PLUS_MLP = 0, 1, 2, 3
 SOLVER_TSIT5, SOLVER_RK4 = 0, 1
 BATCH_PER_TRAJECTORY, BATCH_COUPLED, BATCH_COUPLED_GLOBAL = 0, 1, 2
-SENSE_BACKSOLVE_CHECKPOINTED, SENSE_BACKSOLVE, SENSE_PARALLEL_CHECKPOINTED, SENSE_DISCRETE = 0, 1, 2, 3
+SENSE_BACKSOLVE_CHECKPOINTED, SENSE_BACKSOLVE, SENSE_PARALLEL_CHECKPOINTED, SENSE_DISCRETE, SENSE_FORWARD_DUAL = 0, 1, 2, 3, 4
 ACT_RELU, ACT_TANH = 0, 1
 
 STATUS = {0: "LDE_OK", -1: "LDE_ERR_INVALID_ARG", -2: "LDE_ERR_UNSUPPORTED", -3: "LDE_ERR_NO_DEVICE",
           -4: "LDE_ERR_HIP", -5: "LDE_ERR_NO_WEIGHTS", -6: "LDE_ERR_ALLOC"}
 
 # every symbol include/lde.h declares
-EXPORTS = ["lde_abi_version", "lde_problem_desc_default", "lde_num_weights", "lde_create", "lde_destroy",
+EXPORTS = ["lde_abi_version", "lde_problem_desc_default", "lde_desc_error", "lde_num_weights", "lde_create", "lde_destroy",
            "lde_build_info", "lde_global_sum_mailbox_bytes", "lde_set_global_sum_peers", "lde_set_weights", "lde_set_weights_device", "lde_reserve", "lde_forward", "lde_adjoint",
            "lde_get_stats", "lde_last_error", "lde_last_kernel", "lde_set_global_sum_hook", "lde_set_phase_timing", "lde_get_phase_ms",
            "lde_step_record_bytes", "lde_set_step_record", "lde_get_step_record", "lde_step_record_capacity", "lde_step_record_status", "lde_set_option", "lde_get_option",
@@ -110,6 +110,8 @@ def load():
     lib.lde_build_info.restype = C.c_char_p
     lib.lde_build_info.argtypes = []
     lib.lde_problem_desc_default.argtypes = [C.POINTER(ProblemDesc)]
+    lib.lde_desc_error.argtypes = [C.POINTER(ProblemDesc)]
+    lib.lde_desc_error.restype = C.c_char_p
     lib.lde_num_weights.argtypes = [C.POINTER(ProblemDesc)]
     lib.lde_num_weights.restype = i64
     lib.lde_create.argtypes = [C.POINTER(ProblemDesc), C.POINTER(vp)]

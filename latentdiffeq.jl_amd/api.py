@@ -84,10 +84,15 @@ class ForwardDiffSensitivity(DiscreteSensitivity):
     (see DiscreteSensitivity; upstream pushes dual numbers through the stepper, here the same derivative is taken in reverse mode).
     `Pendulum()` carries it, as in the reference. The continuous adjoints stay selectable: `ParallelAdjoint()` (time-parallel,
     checkpointed), `BacksolveAdjoint()`, `InterpolatingAdjoint()`. (`exact=False`, rounds 1–5's meaning of this tag — the time-parallel
-    continuous adjoint — is still accepted and equals `ParallelAdjoint()`.)"""
+    continuous adjoint — is still accepted and equals `ParallelAdjoint()`.)
 
-    def __init__(self, exact: bool = True):
-        self.code = L.SENSE_DISCRETE if exact else L.SENSE_PARALLEL_CHECKPOINTED
+    `dual_norm=True` (opt-in; LDE_SENSE_FORWARD_DUAL): the solve on dual numbers as upstream runs it during training — the error norm sees
+    the partials, so the accepted steps are the reference's training-time ones, not the primal solve's. The forward pass carries the
+    Jacobians ∂ẑ(t_j)/∂(ẑ₀, θ̂) and the pullback contracts them. Analytic right-hand sides (Pendulum, Pendulum_friction) only."""
+
+    def __init__(self, exact: bool = True, dual_norm: bool = False):
+        self.dual_norm = bool(dual_norm)
+        self.code = L.SENSE_FORWARD_DUAL if dual_norm else L.SENSE_DISCRETE if exact else L.SENSE_PARALLEL_CHECKPOINTED
 
 
 # ------------------------------------------------------------------------------------------------
@@ -121,7 +126,10 @@ class _Handle:
         self.lib = L.load()
         self.desc = desc
         self.ptr = C.c_void_p()
-        L.check(self.lib.lde_create(C.byref(desc), C.byref(self.ptr)), None, "lde_create")
+        rc = self.lib.lde_create(C.byref(desc), C.byref(self.ptr))
+        if rc != 0:
+            why = self.lib.lde_desc_error(C.byref(desc)).decode()   # (no handle to ask lde_last_error)
+            raise L.LdeError(f"lde_create failed: {L.STATUS.get(rc, str(rc))}" + (f": {why}" if why else ""))
         self.nW = int(self.lib.lde_num_weights(C.byref(desc)))
         self.check_record = True          # _SolveFn.backward: look at the step record's counts before the discrete pullback
 
@@ -394,8 +402,9 @@ class _SolveFn(torch.autograd.Function):
         retcode = torch.empty((B,), device=z0.device, dtype=torch.int32)
         tsp = ts.ctypes.data_as(C.POINTER(C.c_double))
         ctx.rec = None
-        if handle.desc.sensealg == L.SENSE_DISCRETE:
-            # the step record travels with THIS graph node (several forwards of one diffeq may be in flight before their pullbacks)
+        if handle.desc.sensealg in (L.SENSE_DISCRETE, L.SENSE_FORWARD_DUAL):
+            # the step record (the dual record: the Jacobians) travels with THIS graph node (several forwards of one diffeq may be in flight
+            # before their pullbacks)
             nbytes = int(lib.lde_step_record_bytes(handle.ptr, B, T))
             ctx.rec = torch.empty((nbytes,), device=z0.device, dtype=torch.uint8)
             L.check(lib.lde_set_step_record(handle.ptr, _ptr(ctx.rec), nbytes), handle.ptr, "lde_set_step_record")
@@ -430,7 +439,9 @@ class _SolveFn(torch.autograd.Function):
         dW = torch.zeros((handle.nW,), device=z_out.device, dtype=torch.float32) if ctx.has_W else None
         tsp = ts.ctypes.data_as(C.POINTER(C.c_double))
         rec = ctx.rec
-        if rec is not None and handle.check_record and not torch.cuda.is_current_stream_capturing():
+        # (a dual record has a fixed size — it cannot overflow: no look at it, no host synchronisation, nothing to re-solve under capture)
+        if (rec is not None and handle.check_record and handle.desc.sensealg == L.SENSE_DISCRETE
+                and not torch.cuda.is_current_stream_capturing()):
             rec = _SolveFn._record_that_holds(handle, rec, z_out, theta, ts, stream)
         if rec is not None:
             L.check(lib.lde_set_step_record(handle.ptr, _ptr(rec), rec.numel()), handle.ptr, "lde_set_step_record")

@@ -35,6 +35,11 @@ const char* pend_last_kernel(int which);
 int launch_pend_adjoint_disc(int kind, int solver, const float* z_out, const float* theta, const double* ts_dev, const KOpts& o,
                              const float* dz_out, float* dz0, float* dtheta, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret,
                              hipStream_t stream, const PendTune& tn);
+int launch_pend_forward_dual(int kind, int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o,
+                             const DualRec& rec, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej,
+                             int32_t* ret, hipStream_t stream);
+int launch_pend_adjoint_dual(const DualRec& rec, const float* dz_out, int T, int B, float* dz0, float* dtheta, int32_t* nfe,
+                             int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
 struct MlpPlan;
 int mlp_plan_create(const lde_problem_desc& d, MlpPlan** out, std::string& err);
 void mlp_plan_destroy(MlpPlan* p);
@@ -88,7 +93,8 @@ struct lde_handle {
   void* rec_user = nullptr;
   size_t rec_user_bytes = 0;
   lde::StepRec rec_last[2] = {};     // the views the last forward / adjoint were given (lde_get_step_record reads them back)
-  int rec_B = 0, rec_T = 0;          // shape of the forward that wrote rec_last[0]
+  int rec_B = 0, rec_T = 0;          // shape of the forward that wrote rec_last[0] / dual_last
+  lde::DualRec dual_last = {};       // LDE_SENSE_FORWARD_DUAL: the dual record the last forward wrote (in rec_own[0] or the caller's block)
   int opt_record_capacity = 0;       // 0: automatic
   int opt_step_trace = 0;
   int opt_adjoint_overwrite = 0;
@@ -168,6 +174,13 @@ int lde_problem_desc_default(lde_problem_desc* d) {
 }
 
 int64_t lde_num_weights(const lde_problem_desc* d) { return num_weights(d); }
+
+const char* lde_desc_error(const lde_problem_desc* d) {
+  static thread_local std::string why;
+  why.clear();
+  if (validate(d, &why) == LDE_OK) why.clear();
+  return why.c_str();
+}
 
 int lde_create(const lde_problem_desc* desc, lde_handle** out) {
   if (!out) return LDE_ERR_INVALID_ARG;
@@ -285,6 +298,36 @@ static int rec_prepare(lde_handle* h, int which, int B, int T, lde::StepRec* out
   return LDE_OK;
 }
 
+// LDE_SENSE_FORWARD_DUAL: the dual record of a call of shape (B, T) (lde_host.h: dual_rec_view) — the caller's block if one was handed over,
+// else the handle's own (rec_own[0]), grown here. `trace`: with the accepted steps (option "step_trace").
+static int dual_prepare(lde_handle* h, int B, int T, bool trace, lde::DualRec* out) {
+  const int cap = rec_capacity(h, T, 0);
+  const size_t need = dual_rec_bytes(B, T, cap, trace);
+  void* base = nullptr;
+  if (h->rec_user) {
+    if (h->rec_user_bytes < need) {
+      h->err = "dual record: the caller's buffer is smaller than lde_step_record_bytes(h, B, T)";
+      return LDE_ERR_INVALID_ARG;
+    }
+    base = h->rec_user;
+  } else {
+    if (h->rec_own_bytes[0] < need) {
+      if (h->rec_own[0] && (void*)h->dual_last.n == h->rec_own[0]) {   // the last forward's record goes with the old buffer
+        h->dual_last = lde::DualRec{};
+        h->rec_last[0] = lde::StepRec{};
+      }
+      if (h->rec_own[0]) (void)hipFree(h->rec_own[0]);
+      h->rec_own[0] = nullptr;
+      h->rec_own_bytes[0] = 0;
+      HIP_TRY(h, hipMalloc(&h->rec_own[0], need));
+      h->rec_own_bytes[0] = need;
+    }
+    base = h->rec_own[0];
+  }
+  *out = dual_rec_view(base, B, T, cap, trace);
+  return LDE_OK;
+}
+
 // adjoint_ws: also size the workspace only lde_adjoint needs (the MLP adjoint's staging area is large)
 static int reserve_impl(lde_handle* h, int B, int T, bool adjoint_ws, int64_t steps_hint) {
   if (!h || B < 1 || T < 1) return LDE_ERR_INVALID_ARG;
@@ -324,7 +367,11 @@ static int reserve_impl(lde_handle* h, int B, int T, bool adjoint_ws, int64_t st
       h->par_cap = need;
     }
   }
-  if (!h->rec_user && (h->d.sensealg == LDE_SENSE_DISCRETE || h->opt_step_trace)) {   // (lde_reserve pre-sizes the handle's own records too)
+  if (!h->rec_user && h->d.sensealg == LDE_SENSE_FORWARD_DUAL) {   // (the dual record; no reverse-time trace: the pullback solves nothing)
+    lde::DualRec tmp;
+    const int rc = dual_prepare(h, B, T, h->opt_step_trace != 0, &tmp);
+    if (rc) return rc;
+  } else if (!h->rec_user && (h->d.sensealg == LDE_SENSE_DISCRETE || h->opt_step_trace)) {   // (lde_reserve pre-sizes the handle's own records too)
     lde::StepRec tmp;
     int rc = rec_prepare(h, 0, B, T, &tmp);
     if (!rc && h->opt_step_trace && adjoint_ws && h->d.sensealg != LDE_SENSE_DISCRETE) rc = rec_prepare(h, 1, B, T, &tmp);
@@ -377,6 +424,22 @@ int lde_forward(lde_handle* h, const float* z0, const float* theta, const double
   if (rc) return rc;
   lde::KOpts o = make_opts(h->d, ts, T, B);
   h->rec_last[0] = lde::StepRec{};
+  if (h->d.sensealg == LDE_SENSE_FORWARD_DUAL) {
+    lde::DualRec r;
+    rc = dual_prepare(h, B, T, h->opt_step_trace != 0, &r);
+    if (rc) return rc;
+    h->dual_last = r;
+    h->rec_B = B;
+    h->rec_T = T;
+    if (r.t) h->rec_last[0] = lde::StepRec{r.n, r.t, r.dt, nullptr, r.cap, B};   // (lde_get_step_record's view of the trace)
+    h->last_B[0] = B;
+    int32_t** st = h->st[0];
+    rc = lde::launch_pend_forward_dual(h->d.rhs_kind, h->d.solver, z0, theta, h->ts_dev, o, r, z_out, retcode, st[0], st[1], st[2], st[3],
+                                       stream);
+    h->last_kernel[0] = "k_pend_forward_dual";
+    if (rc) h->err = "lde_forward: kernel launch failed";
+    return rc;
+  }
   if (h->d.sensealg == LDE_SENSE_DISCRETE || h->opt_step_trace) {
     rc = rec_prepare(h, 0, B, T, &o.rec);
     if (rc) return rc;
@@ -418,6 +481,28 @@ int lde_adjoint(lde_handle* h, const float* z_out, const float* theta, const dou
   int32_t** st = h->st[1];
   h->last_B[1] = B;
   h->rec_last[1] = lde::StepRec{};
+  if (h->d.sensealg == LDE_SENSE_FORWARD_DUAL) {
+    // the pullback is the contraction of the Jacobians the forward left in its dual record: no solve, no MLP
+    if (dW) {
+      h->err = "lde_adjoint (LDE_SENSE_FORWARD_DUAL): dW must be NULL (analytic right-hand side: no weights)";
+      return LDE_ERR_INVALID_ARG;
+    }
+    lde::DualRec r;
+    if (h->rec_user) {
+      rc = dual_prepare(h, B, T, false, &r);   // (n and J sit where they sit whether or not the forward traced its steps)
+      if (rc) return rc;
+    } else {
+      if (!h->dual_last.n || h->rec_B != B || h->rec_T != T) {
+        h->err = "lde_adjoint (LDE_SENSE_FORWARD_DUAL): no dual record of an lde_forward with this (B, T) on this handle";
+        return LDE_ERR_INVALID_ARG;
+      }
+      r = h->dual_last;
+    }
+    rc = lde::launch_pend_adjoint_dual(r, dz_out, T, B, dz0, dtheta, st[0], st[1], st[2], st[3], stream);
+    h->last_kernel[1] = "k_pend_adjoint_dual";
+    if (rc) h->err = "lde_adjoint: kernel launch failed";
+    return rc;
+  }
   if (h->d.sensealg == LDE_SENSE_DISCRETE) {
     // the record of the forward solve this call differentiates: the caller's buffer (lde_set_step_record) or the handle's own
     lde::StepRec r;
@@ -515,6 +600,7 @@ int lde_set_global_sum_peers(lde_handle* h, int rank, int nranks, void* const* m
 
 int64_t lde_step_record_bytes(const lde_handle* h, int B, int T) {
   if (!h || B < 1 || T < 1) return 0;
+  if (h->d.sensealg == LDE_SENSE_FORWARD_DUAL) return (int64_t)dual_rec_bytes(B, T, rec_capacity(h, T, 0), h->opt_step_trace != 0);
   return (int64_t)rec_bytes(h->d, B, rec_capacity(h, T, 0), true);
 }
 
@@ -532,6 +618,22 @@ int lde_step_record_capacity(const lde_handle* h, int T) { return (!h || T < 1) 
 
 int lde_step_record_status(lde_handle* h, const void* rec_dev, int B, int T, int32_t* max_steps, int32_t* capacity, void* stream_) {
   if (!h || !max_steps || B < 1 || T < 1) return LDE_ERR_INVALID_ARG;
+  if (h->d.sensealg == LDE_SENSE_FORWARD_DUAL) {   // a dual record holds any solve up to maxiters: never an overflow
+    const int32_t* n = rec_dev ? dual_rec_view(const_cast<void*>(rec_dev), B, T, 0, false).n : h->dual_last.n;
+    if (!rec_dev && (!n || h->rec_B != B || h->rec_T != T)) {
+      h->err = "lde_step_record_status: no dual record of an lde_forward with this (B, T) on this handle";
+      return LDE_ERR_INVALID_ARG;
+    }
+    HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream_));
+    std::vector<int32_t> nh((size_t)B);
+    HIP_TRY(h, hipMemcpy(nh.data(), n, nh.size() * 4, hipMemcpyDeviceToHost));
+    int32_t m = 0;
+    for (int32_t v : nh) m = std::max(m, v);
+    const int32_t cap = (int32_t)std::min<int64_t>(h->d.maxiters, INT32_MAX);
+    *max_steps = std::min(m, cap);
+    if (capacity) *capacity = cap;
+    return LDE_OK;
+  }
   lde::StepRec r;
   if (rec_dev) {
     r = rec_view(h->d, const_cast<void*>(rec_dev), B, rec_capacity(h, T, 0), true);
@@ -556,7 +658,7 @@ int lde_get_step_record(lde_handle* h, int which, double* t_host, double* dt_hos
   if (!h || which < 0 || which > 1 || !dt_host || !n_host || nseq < 1 || cap < 1) return LDE_ERR_INVALID_ARG;
   const lde::StepRec& r = h->rec_last[which];
   if (!r.n) {
-    h->err = "lde_get_step_record: the last call made no record (LDE_SENSE_DISCRETE or option \"step_trace\")";
+    h->err = "lde_get_step_record: the last call made no record (LDE_SENSE_DISCRETE or option \"step_trace\"; LDE_SENSE_FORWARD_DUAL: \"step_trace\")";
     return LDE_ERR_INVALID_ARG;
   }
   if (nseq != r.nseq) {

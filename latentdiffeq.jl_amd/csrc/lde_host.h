@@ -15,6 +15,7 @@
 namespace lde_host {
 using lde::KOpts;
 using lde::StepRec;
+using lde::DualRec;
 
 static bool has_mlp(const lde_problem_desc& d) {
   return d.rhs_kind == LDE_RHS_MLP || d.rhs_kind == LDE_RHS_PENDULUM_PLUS_MLP;
@@ -45,7 +46,7 @@ static int validate(const lde_problem_desc* d, std::string* why) {
   if (d->batching != LDE_BATCH_PER_TRAJECTORY && d->batching != LDE_BATCH_COUPLED && d->batching != LDE_BATCH_COUPLED_GLOBAL)
     return bad("unknown batching");
   if (d->batching == LDE_BATCH_COUPLED_GLOBAL && !has_mlp(*d)) return bad("LDE_BATCH_COUPLED_GLOBAL needs an MLP right-hand side");
-  if (d->sensealg < LDE_SENSE_BACKSOLVE_CHECKPOINTED || d->sensealg > LDE_SENSE_DISCRETE) return bad("unknown sensealg");
+  if (d->sensealg < LDE_SENSE_BACKSOLVE_CHECKPOINTED || d->sensealg > LDE_SENSE_FORWARD_DUAL) return bad("unknown sensealg");
   // (LDE_SENSE_DISCRETE with LDE_BATCH_COUPLED_GLOBAL: every rank records the common step sequence and ITS columns' states; the sweep
   //  has no step control, hence no sum to exchange)
 
@@ -57,6 +58,16 @@ static int validate(const lde_problem_desc* d, std::string* why) {
   if (d->adaptive && (!(d->abstol > 0) || !(d->reltol > 0))) return bad("tolerances must be > 0");
   if (d->maxiters < 1) return bad("maxiters < 1");
   if (!(d->qmin > 0) || !(d->qmax > 0) || !(d->gamma > 0)) return bad("controller constants must be > 0");
+  if (d->sensealg == LDE_SENSE_FORWARD_DUAL) {   // the dual-number solve is served for the GOKU path only (include/lde.h)
+    if (has_mlp(*d)) {
+      if (why) *why = "LDE_SENSE_FORWARD_DUAL: no MLP right-hand side (the weights would be thousands of partials); analytic right-hand sides only";
+      return LDE_ERR_UNSUPPORTED;
+    }
+    if (d->batching != LDE_BATCH_PER_TRAJECTORY) {
+      if (why) *why = "LDE_SENSE_FORWARD_DUAL: no coupled solve; LDE_BATCH_PER_TRAJECTORY only";
+      return LDE_ERR_UNSUPPORTED;
+    }
+  }
   return LDE_OK;
 }
 
@@ -84,6 +95,22 @@ static StepRec rec_view(const lde_problem_desc& d, void* base, int B, int cap, b
   r.y = with_y ? (float*)p : nullptr;
   r.cap = cap;
   r.nseq = (int)nseq;
+  return r;
+}
+
+// LDE_SENSE_FORWARD_DUAL's record (include/lde.h: "the dual record"): n [B] | J [T][2][3][B] f32 | with the step trace t, dt [cap][B] f64.
+// J first: its place depends on B alone, so the pullback (which reads n and J) finds it whether or not the forward traced its steps.
+static size_t dual_rec_bytes(int B, int T, int cap, bool trace) {
+  return align256((size_t)B * 4) + align256((size_t)T * 6 * B * 4) + (trace ? 2 * align256((size_t)cap * B * 8) : 0);
+}
+static DualRec dual_rec_view(void* base, int B, int T, int cap, bool trace) {
+  DualRec r{};
+  unsigned char* p = (unsigned char*)base;
+  r.n = (int32_t*)p; p += align256((size_t)B * 4);
+  r.J = (float*)p; p += align256((size_t)T * 6 * B * 4);
+  r.t = trace ? (double*)p : nullptr; p += trace ? align256((size_t)cap * B * 8) : 0;
+  r.dt = trace ? (double*)p : nullptr;
+  r.cap = trace ? cap : 0;
   return r;
 }
 
@@ -136,6 +163,16 @@ static PendFwdMap pend_forward_mapping(int kind, int solver, bool adaptive, bool
   if (tn.lb_ring > 0 && T > 1 && T <= 2048 && B >= tn.lb_min_b) return PEND_FWD_RING;
   return PEND_FWD_LANE;
 }
+
+// Which mapping serves a solve under LDE_SENSE_FORWARD_DUAL (csrc/lde_pend_dual.hip switches on this). Kept apart from pend_forward_mapping,
+// whose seven results tests/host_logic_driver.cpp pins: the dual solve has ONE mapping, a lane per trajectory (two values and six partials in
+// registers), and the batch only sizes its workgroups — a wave each up to 4 096 trajectories (one wave per CU as long as there are CUs to spare),
+// four waves beyond.
+enum PendDualMap {
+  PEND_DUAL_LANE64 = 0,   // k_pend_forward_dual, 64-lane workgroups
+  PEND_DUAL_LANE256       // k_pend_forward_dual, 256-lane workgroups
+};
+static PendDualMap pend_dual_mapping(int B) { return B <= 4096 ? PEND_DUAL_LANE64 : PEND_DUAL_LANE256; }
 
 static KOpts make_opts(const lde_problem_desc& d, const double* ts, int T, int B) {
   KOpts o;

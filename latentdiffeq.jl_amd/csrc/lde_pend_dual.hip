@@ -1,0 +1,323 @@
+// lde_pend_dual.hip — LDE_SENSE_FORWARD_DUAL: ForwardDiffSensitivity as the reference executes it during training, on the GOKU path.
+//
+// `Pendulum()` carries ForwardDiffSensitivity() [REF examples/pendulum_friction-less/pendulum.jl:8-11], splatted into solve() at
+// [REF src/models/GOKU.jl:107, :121]: upstream seeds (u0, p) with dual partials and runs the SAME OrdinaryDiffEq solve on Dual numbers, and
+// its error norm (ODE_DEFAULT_NORM on a Dual = sqrt(value² + Σ partials²)) sees the partials — the accepted steps of a training solve are not
+// the primal solve's. LDE_SENSE_DISCRETE differentiates the primal sequence; this mode reproduces the dual one. The specification is the
+// checker's dual_solve with dual_norm = 1 (oracle/), step for step.
+//
+// k_pend_forward_dual: a lane per trajectory, the dual state in registers — two values and six partials ∂(x, v)/∂(x₀, v₀, L), Tsit5's seven
+// slopes of it — every stage's sin x and cos x from ONE hw_sincos on the step's turn anchor (as PendBwd), ∂f/∂L = (G/L²)·sin x on the L column.
+// The stage sums, the solution weights and the interpolant are lde_device.h's (tsit5_attempt / rk4_step / tsit5_dense_* on an 8-vector); what
+// decides the steps — the dual norms, their squares, the RMS (accumulated in f64 as the oracle does) and the Hairer initial step — follows the
+// oracle's order of operations. ẑ goes to z_out [T×B×2] as lde_forward's other kernels write it; J_j = ∂ẑ(t_j)/∂(x₀, v₀, L) to the dual
+// record, trajectory fastest (lde_types.h: DualRec), so that a wave's 64 lanes write — and the pullback's read — 256 consecutive bytes.
+// k_pend_adjoint_dual: dz0 = Σ_j J_j[:, 0:2]ᵀ dz_out_j, dθ = Σ_j J_j[:, 2]ᵀ dz_out_j, summed j outer, i inner in f32 (the oracle's order).
+#include "lde_device.h"
+#include "lde_host.h"
+
+namespace lde {
+
+namespace {
+
+constexpr int DN = 8;                 // [x, v, ∂x/∂x₀, ∂x/∂v₀, ∂x/∂L, ∂v/∂x₀, ∂v/∂v₀, ∂v/∂L]
+constexpr int DUAL_TS_LDS_MAX = 6000;   // doubles of the save-time grid kept in LDS (48 KB)
+
+// du = [v, −(G/L) sin x (− (b/m) v)] on duals: ∂f/∂u = [[0, 1], [−(G/L) cos x, (−b/m)]], ∂f/∂L = [0, (G/L²) sin x]
+template <int KIND>
+struct PendDual {
+  float ngl, gl2;   // −G/L, G/L²
+  float noff;       // −(whole turns of the step's start angle): turn_anchor (lde_device.h)
+  __device__ __forceinline__ explicit PendDual(float L) : ngl(-10.0f / L), gl2(10.0f / (L * L)), noff(0.f) {}
+  __device__ __forceinline__ void anchor(float x0) { noff = turn_anchor(x0); }
+  __device__ __forceinline__ void operator()(const float (&y)[DN], float (&dy)[DN]) const {
+    float s, c;
+    hw_sincos(y[0], s, c, noff);
+    dy[0] = y[1];
+    float acc = ngl * s;
+    if (KIND == 1) acc -= 0.7f * y[1];
+    dy[1] = acc;
+    const float ngc = ngl * c;
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+      dy[2 + q] = y[5 + q];
+      float a = ngc * y[2 + q];
+      if (KIND == 1) a -= 0.7f * y[5 + q];
+      dy[5 + q] = a;
+    }
+    dy[7] += gl2 * s;
+  }
+};
+
+// ‖u_i‖ of component i (0: x, 1: v) as ODE_DEFAULT_NORM takes it on a dual: sqrt(v² + Σ_q p_q²), the squares added in the oracle's order, unfused
+__device__ __forceinline__ float dual_abs(const float (&u)[DN], int i) {
+#pragma clang fp contract(off)
+  float s2 = u[i] * u[i];
+#pragma unroll
+  for (int q = 0; q < 3; q++) s2 += u[2 + 3 * i + q] * u[2 + 3 * i + q];
+  return sqrtf(s2);
+}
+
+// RMS over the two components of ‖e_i‖ / sk_i: each ratio and its square in f32, the sum of squares and the root in f64 (oracle: dual_rms)
+__device__ __forceinline__ double dual_rms(const float (&e)[DN], const float (&sk)[2]) {
+#pragma clang fp contract(off)
+  double s2 = 0.0;
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    const float r = dual_abs(e, i) / sk[i];
+    s2 += (double)(r * r);
+  }
+  return sqrt(s2 / 2.0);
+}
+
+// Hairer–Nørsett–Wanner initial step with every norm the dual norm; f0 = f(y0) given (oracle: dual_solve's initial step)
+template <class F>
+__device__ __forceinline__ double dual_init_dt(F& f, const float (&y)[DN], const float (&f0)[DN], double dtmax, const KOpts& o) {
+  float sk[2];
+  {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < 2; i++) sk[i] = o.abstol + dual_abs(y, i) * o.reltol;
+  }
+  const double d0 = dual_rms(y, sk), d1 = dual_rms(f0, sk);
+  double dt0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+  if (dt0 > dtmax) dt0 = dtmax;
+  const float h = (float)dt0;
+  float tmp[DN], f1[DN];
+#pragma unroll
+  for (int c = 0; c < DN; c++) tmp[c] = y[c] + h * f0[c];
+  f(tmp, f1);
+#pragma unroll
+  for (int c = 0; c < DN; c++) f1[c] -= f0[c];
+  const double d2 = dual_rms(f1, sk) / dt0, dm = d1 > d2 ? d1 : d2;
+  const double dt1 = (dm <= 1e-15) ? fmax(1e-6, dt0 * 1e-3) : pow(10.0, -(2.0 + log10(dm)) / 5.0);
+  const double dt = fmin(100.0 * dt0, dt1);
+  return dt > dtmax ? dtmax : dt;
+}
+
+// EEst of a Tsit5 attempt on duals: e = h·Σ_j b̃_j k_j per component, scale abstol + reltol·max(‖y_i‖, ‖y_new,i‖), RMS of ‖e_i‖ / scale
+__device__ __forceinline__ float dual_eest(float h, const float (&y)[DN], const float (&yn)[DN], const float (&k)[7][DN], const KOpts& o) {
+  float e[DN];
+#pragma unroll
+  for (int c = 0; c < DN; c++) {
+    float a = ts5::BT[0] * k[0][c];
+#pragma unroll
+    for (int j = 1; j < 7; j++) a += ts5::BT[j] * k[j][c];
+    e[c] = a * h;
+  }
+  float sk[2];
+  {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < 2; i++) sk[i] = o.abstol + fmaxf(dual_abs(y, i), dual_abs(yn, i)) * o.reltol;
+  }
+  return (float)dual_rms(e, sk);
+}
+
+}  // namespace
+
+template <int KIND, int SOLVER, bool TS_LDS>
+__global__ void __launch_bounds__(256) k_pend_forward_dual(const float2* __restrict__ z0, const float* __restrict__ theta,
+                                                           const double* __restrict__ ts_g, KOpts o, DualRec rec,
+                                                           float2* __restrict__ z_out, int32_t* __restrict__ retcode,
+                                                           int32_t* __restrict__ st_nfe, int32_t* __restrict__ st_nacc,
+                                                           int32_t* __restrict__ st_nrej, int32_t* __restrict__ st_ret) {
+  extern __shared__ __attribute__((aligned(16))) double s_ts_dual[];
+  const int T = o.T, B = o.B;
+  if (TS_LDS)
+    for (int i = threadIdx.x; i < T; i += blockDim.x) s_ts_dual[i] = ts_g[i];
+  __syncthreads();
+  auto s_ts = [&](int i) -> double { return TS_LDS ? s_ts_dual[i] : ts_g[i]; };
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+
+  // J_j of this trajectory: six rows of B floats per save time
+  auto save = [&](int j, const float (&u)[DN]) {
+    z_out[(size_t)j * B + b] = make_float2(u[0], u[1]);
+    float* Jj = rec.J + (size_t)j * 6 * B + b;
+#pragma unroll
+    for (int c = 0; c < 6; c++) Jj[(size_t)c * B] = u[2 + c];
+  };
+
+  const float2 zi = z0[b];
+  PendDual<KIND> f(theta[b]);
+  float y[DN] = {zi.x, zi.y, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f};   // seeds: ∂y₀/∂x₀ = e₀, ∂y₀/∂v₀ = e₁, ∂y₀/∂L = 0
+  float k[7][DN], yn[DN];
+  save(0, y);   // ts[0] is saved as ẑ₀ itself
+  int ret = LDE_RET_SUCCESS, nfe = 0, nacc = 0, nrej = 0;
+
+  if (T > 1) {
+    double t = o.t_first;
+    const double tend = o.t_last, dtmax = tend - t;
+    f.anchor(y[0]);
+    f(y, k[0]);
+    nfe = 1;
+    double dt;
+    if (!o.adaptive) dt = o.dt_fixed;
+    else if (o.dt_fixed > 0) dt = fmin(o.dt_fixed, dtmax);
+    else {
+      dt = dual_init_dt(f, y, k[0], dtmax, o);
+      nfe++;
+    }
+    float qold = 1e-4f;
+    long long iters = 0;
+    int j = 1;
+    double tj = s_ts(1), tjn = s_ts(min(2, T - 1));
+    while (t < tend) {
+      if (iters++ >= o.maxiters) { ret = LDE_RET_MAXITERS; break; }
+      double dtp = dt;
+      bool last = false;
+      if (t + dt >= tend - 1e-12 * fabs(tend)) { dt = tend - t; last = true; }
+      const float h = (float)dt;
+      float EEst = 0.f;
+      f.anchor(y[0]);
+      if (SOLVER == LDE_SOLVER_TSIT5) {
+        tsit5_attempt<DN, PendDual<KIND>, false, 0>(f, h, y, k, yn, o);
+        if (o.adaptive) EEst = dual_eest(h, y, yn, k, o);
+        nfe += 6;
+      } else {
+        rk4_step<DN>(f, h, y, k, yn);
+        nfe += 4;
+      }
+      if (!all_finite<DN>(yn) || !(EEst == EEst)) {
+        if (o.adaptive && dt > o.dtmin) { nrej++; dt = dt * (double)o.qmin; continue; }
+        ret = LDE_RET_NONFINITE;
+        break;
+      }
+      if (o.adaptive) {
+        float q11;
+        const float q = pi_q(EEst, qold, o, q11);
+        if (EEst > 1.0f) {
+          nrej++;
+          dt = dt * (double)fast_rcp(fminf(o.q_hi, q11 * o.inv_gamma));
+          if (dt < o.dtmin) { ret = LDE_RET_DTMIN; break; }
+          continue;
+        }
+        qold = fmaxf(EEst, 1e-4f);
+        dtp = dt * (double)fast_rcp(q);
+        if (dtp > dtmax) dtp = dtmax;
+      }
+      if (rec.t && nacc < rec.cap) {   // option "step_trace": the accepted step's start time and size
+        rec.t[(size_t)nacc * B + b] = t;
+        rec.dt[(size_t)nacc * B + b] = dt;
+      }
+      nacc++;
+      const double tnew = last ? tend : t + dt;
+      if (j < T && tj <= tnew) {   // at least one save time in (t, tnew]
+        float P[3][DN];
+        if (SOLVER == LDE_SOLVER_TSIT5) tsit5_dense_coeffs<DN>(k, P);
+        do {
+          float u[DN];
+          if (tj >= tnew || (j == T - 1 && last)) {
+#pragma unroll
+            for (int c = 0; c < DN; c++) u[c] = yn[c];
+          } else {
+            const double thd = (tj - t) / dt;
+            if (SOLVER == LDE_SOLVER_TSIT5) {
+              const float th = (float)thd;
+#pragma unroll
+              for (int c = 0; c < DN; c++) u[c] = tsit5_dense_eval<DN>(th, h, y[c], k[0][c], P[0][c], P[1][c], P[2][c]);
+            } else {   // cubic Hermite between (y, k₁) and (y_new, f(y_new)), coefficients in f64 as the oracle forms them
+              const double om = 1.0 - thd;
+              const float h00 = (float)((1.0 + 2.0 * thd) * om * om), h10 = (float)(thd * om * om * dt);
+              const float h01 = (float)(thd * thd * (3.0 - 2.0 * thd)), h11 = (float)(thd * thd * (thd - 1.0) * dt);
+#pragma unroll
+              for (int c = 0; c < DN; c++) u[c] = h00 * y[c] + h10 * k[0][c] + h01 * yn[c] + h11 * k[4][c];
+            }
+          }
+          save(j, u);
+          j++;
+          tj = tjn;
+          tjn = s_ts(min(j + 1, T - 1));
+        } while (j < T && tj <= tnew);
+      }
+#pragma unroll
+      for (int c = 0; c < DN; c++) y[c] = yn[c];
+      constexpr int FS = (SOLVER == LDE_SOLVER_TSIT5) ? 6 : 4;   // FSAL slope
+#pragma unroll
+      for (int c = 0; c < DN; c++) k[0][c] = k[FS][c];
+      t = tnew;
+      dt = o.adaptive ? dtp : o.dt_fixed;
+    }
+  }
+  if (ret != LDE_RET_SUCCESS) {   // failed solve ⇒ NaN block and zero Jacobians (zero gradient) [REF GOKU.jl:114]
+    const float qn = __int_as_float(0x7fc00000);
+    for (int j = 0; j < T; j++) {
+      z_out[(size_t)j * B + b] = make_float2(qn, qn);
+      float* Jj = rec.J + (size_t)j * 6 * B + b;
+#pragma unroll
+      for (int c = 0; c < 6; c++) Jj[(size_t)c * B] = 0.f;
+    }
+  }
+  if (retcode) retcode[b] = ret;
+  st_ret[b] = ret;
+  st_nfe[b] = nfe;
+  st_nacc[b] = nacc;
+  st_nrej[b] = nrej;
+  rec.n[b] = ret == LDE_RET_SUCCESS ? nacc : -ret;
+}
+
+__global__ void __launch_bounds__(256) k_pend_adjoint_dual(DualRec rec, const float2* __restrict__ dz_out, int T, int B,
+                                                           float2* __restrict__ dz0, float* __restrict__ dtheta,
+                                                           int32_t* __restrict__ st_nfe, int32_t* __restrict__ st_nacc,
+                                                           int32_t* __restrict__ st_nrej, int32_t* __restrict__ st_ret) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int n = rec.n[b];
+  float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+  if (n >= 0) {   // (a failed trajectory's gradient is zero whatever its cotangent holds: a NaN ẑ block usually brings a NaN one)
+    const float* Jb = rec.J + b;
+    for (int j = 0; j < T; j++) {
+      const float2 d = dz_out[(size_t)j * B + b];
+      const float* Jj = Jb + (size_t)j * 6 * B;
+      g0 += Jj[0] * d.x;
+      g1 += Jj[(size_t)B] * d.x;
+      g2 += Jj[(size_t)2 * B] * d.x;
+      g0 += Jj[(size_t)3 * B] * d.y;
+      g1 += Jj[(size_t)4 * B] * d.y;
+      g2 += Jj[(size_t)5 * B] * d.y;
+    }
+  }
+  dz0[b] = make_float2(g0, g1);
+  dtheta[b] = g2;
+  st_nfe[b] = 0;
+  st_nacc[b] = 0;
+  st_nrej[b] = 0;
+  st_ret[b] = n < 0 ? -n : LDE_RET_SUCCESS;
+}
+
+// ---- host-side launchers (called from lde_api.hip) -------------------------------------------------------------------------------
+static int dual_block(int B) { return lde_host::pend_dual_mapping(B) == lde_host::PEND_DUAL_LANE64 ? 64 : 256; }
+
+int launch_pend_forward_dual(int kind, int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o,
+                             const DualRec& rec, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej,
+                             int32_t* ret, hipStream_t stream) {
+  const int block = dual_block(o.B), grid = (o.B + block - 1) / block;
+  const size_t shm = o.T <= DUAL_TS_LDS_MAX ? (size_t)o.T * sizeof(double) : 0;
+#define LDE_LAUNCH_DUAL(K, S)                                                                                                        \
+  do {                                                                                                                               \
+    if (shm)                                                                                                                         \
+      hipLaunchKernelGGL((k_pend_forward_dual<K, S, true>), dim3(grid), dim3(block), shm, stream, (const float2*)z0, theta, ts_dev, o, \
+                         rec, (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                                        \
+    else                                                                                                                             \
+      hipLaunchKernelGGL((k_pend_forward_dual<K, S, false>), dim3(grid), dim3(block), 0, stream, (const float2*)z0, theta, ts_dev, o, \
+                         rec, (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                                        \
+  } while (0)
+  if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH_DUAL(0, LDE_SOLVER_TSIT5);
+  else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_RK4) LDE_LAUNCH_DUAL(0, LDE_SOLVER_RK4);
+  else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH_DUAL(1, LDE_SOLVER_TSIT5);
+  else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_RK4) LDE_LAUNCH_DUAL(1, LDE_SOLVER_RK4);
+  else return LDE_ERR_UNSUPPORTED;
+#undef LDE_LAUNCH_DUAL
+  return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
+}
+
+int launch_pend_adjoint_dual(const DualRec& rec, const float* dz_out, int T, int B, float* dz0, float* dtheta, int32_t* nfe,
+                             int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream) {
+  const int block = dual_block(B), grid = (B + block - 1) / block;
+  hipLaunchKernelGGL(k_pend_adjoint_dual, dim3(grid), dim3(block), 0, stream, rec, (const float2*)dz_out, T, B, (float2*)dz0, dtheta,
+                     nfe, nacc, nrej, ret);
+  return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
+}
+
+}  // namespace lde

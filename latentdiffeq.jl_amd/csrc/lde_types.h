@@ -20,6 +20,16 @@ struct StepRec {
   int cap, nseq;
 };
 
+// LDE_SENSE_FORWARD_DUAL's record in device memory (include/lde.h: lde_set_step_record): written by k_pend_forward_dual, read by
+// k_pend_adjoint_dual. J holds ∂ẑ(t_j)/∂(x₀, v₀, L) of every save time, trajectory fastest: element (j, i, q, b) at ((j·2 + i)·3 + q)·B + b.
+struct DualRec {
+  int32_t* n;    // [B] accepted steps; −retcode for a failed trajectory
+  float* J;      // [T][2][3][B]
+  double* t;     // [cap][B] start time of accepted step n (option "step_trace"; nullptr otherwise)
+  double* dt;    // [cap][B] its size
+  int cap;       // 0 without the trace
+};
+
 // Kernel-choice knobs of a handle (lde_set_option; tests force a family / a threshold through them — formerly LDE_* environment variables,
 // which a library behind a `ccall` host must not read). Defaults = the measured choices.
 struct PendTune {
