@@ -24,17 +24,10 @@ namespace lde {
 int launch_pend_forward(int kind, int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o,
                         float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret,
                         hipStream_t stream, const PendTune& tn);
-int launch_pend_adjoint(int kind, int solver, const float* z_out, const float* theta, const double* ts_dev,
-                        const KOpts& o, const float* dz_out, float* dz0, float* dtheta, int32_t* nfe, int32_t* nacc,
-                        int32_t* nrej, int32_t* ret, hipStream_t stream);
-int launch_pend_adjoint_par(int kind, int solver, const float* z_out, const float* theta, const double* ts_dev,
-                            const KOpts& o, const float* dz_out, float* dz0, float* dtheta, float* ops, int32_t* info,
-                            int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
-bool pend_adjoint_needs_ops(int B, int T);
+int launch_pend_adjoint(int kind, int solver, int sensealg, const float* z_out, const float* theta, const double* ts_dev, const KOpts& o,
+                        const float* dz_out, float* dz0, float* dtheta, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret,
+                        hipStream_t stream, const PendTune& tn);
 const char* pend_last_kernel(int which);
-int launch_pend_adjoint_disc(int kind, int solver, const float* z_out, const float* theta, const double* ts_dev, const KOpts& o,
-                             const float* dz_out, float* dz0, float* dtheta, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret,
-                             hipStream_t stream, const PendTune& tn);
 int launch_pend_forward_dual(int kind, int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o,
                              const DualRec& rec, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej,
                              int32_t* ret, hipStream_t stream);
@@ -82,10 +75,6 @@ struct lde_handle {
   int32_t* st[2][4] = {};
   int cap_B = 0;
   int last_B[2] = {0, 0};
-  // parallel-in-time adjoint: per-(interval, trajectory) transition operators
-  float* par_ops = nullptr;
-  int32_t* par_info = nullptr;
-  size_t par_cap = 0;
   // step records (include/lde.h: lde_set_step_record): [0] the forward solve's (LDE_SENSE_DISCRETE / step tracing), [1] the continuous
   // adjoint's reverse-time steps (step tracing). own: the handle's buffer; user: the caller's (forward record only)
   void* rec_own[2] = {nullptr, nullptr};
@@ -227,8 +216,6 @@ void lde_destroy(lde_handle* h) {
   if (h->mlp) lde::mlp_plan_destroy(h->mlp);
   if (h->W_dev) (void)hipFree(h->W_dev);
   if (h->ts_dev) (void)hipFree(h->ts_dev);
-  if (h->par_ops) (void)hipFree(h->par_ops);
-  if (h->par_info) (void)hipFree(h->par_info);
   for (int i = 0; i < 2; i++)
     if (h->rec_own[i]) (void)hipFree(h->rec_own[i]);
   for (int i = 0; i < TS_RING; i++) {
@@ -354,18 +341,6 @@ static int reserve_impl(lde_handle* h, int B, int T, bool adjoint_ws, int64_t st
       HIP_TRY(h, hipHostMalloc((void**)&h->ts_pinned[i], (size_t)T * sizeof(double), hipHostMallocDefault));
     }
     h->ts_pin_cap = T;
-  }
-  if (!h->mlp && h->d.sensealg == LDE_SENSE_PARALLEL_CHECKPOINTED && lde::pend_adjoint_needs_ops(B, T)) {
-    const size_t need = (size_t)(T > 1 ? T - 1 : 1) * (size_t)B;
-    if (need > h->par_cap) {
-      if (h->par_ops) (void)hipFree(h->par_ops);
-      if (h->par_info) (void)hipFree(h->par_info);
-      h->par_ops = nullptr;
-      h->par_info = nullptr;
-      HIP_TRY(h, hipMalloc(&h->par_ops, need * 6 * sizeof(float)));
-      HIP_TRY(h, hipMalloc(&h->par_info, need * sizeof(int32_t)));
-      h->par_cap = need;
-    }
   }
   if (!h->rec_user && h->d.sensealg == LDE_SENSE_FORWARD_DUAL) {   // (the dual record; no reverse-time trace: the pullback solves nothing)
     lde::DualRec tmp;
@@ -517,16 +492,7 @@ int lde_adjoint(lde_handle* h, const float* z_out, const float* theta, const dou
       r = h->rec_last[0];
     }
     o.rec = r;
-    if (h->mlp)
-      return lde::mlp_adjoint(h->mlp, h->W_dev, z_out, theta, h->ts_dev, o, dz_out, dz0, dtheta, dW, st[0], st[1], st[2], st[3], stream,
-                              h->err);
-    rc = lde::launch_pend_adjoint_disc(h->d.rhs_kind, h->d.solver, z_out, theta, h->ts_dev, o, dz_out, dz0, dtheta, st[0], st[1], st[2],
-                                       st[3], stream, h->pend_tune);
-    h->last_kernel[1] = lde::pend_last_kernel(1);
-    if (rc) h->err = "lde_adjoint: kernel launch failed";
-    return rc;
-  }
-  if (h->opt_step_trace) {
+  } else if (h->opt_step_trace) {
     rc = rec_prepare(h, 1, B, T, &o.rec);
     if (rc) return rc;
     h->rec_last[1] = o.rec;
@@ -535,12 +501,8 @@ int lde_adjoint(lde_handle* h, const float* z_out, const float* theta, const dou
   if (h->mlp)
     return lde::mlp_adjoint(h->mlp, h->W_dev, z_out, theta, h->ts_dev, o, dz_out, dz0, dtheta, dW, st[0], st[1], st[2],
                             st[3], stream, h->err);
-  if (h->d.sensealg == LDE_SENSE_PARALLEL_CHECKPOINTED)
-    rc = lde::launch_pend_adjoint_par(h->d.rhs_kind, h->d.solver, z_out, theta, h->ts_dev, o, dz_out, dz0, dtheta, h->par_ops,
-                                      h->par_info, st[0], st[1], st[2], st[3], stream);
-  else
-    rc = lde::launch_pend_adjoint(h->d.rhs_kind, h->d.solver, z_out, theta, h->ts_dev, o, dz_out, dz0, dtheta, st[0], st[1],
-                                  st[2], st[3], stream);
+  rc = lde::launch_pend_adjoint(h->d.rhs_kind, h->d.solver, h->d.sensealg, z_out, theta, h->ts_dev, o, dz_out, dz0, dtheta, st[0], st[1],
+                                st[2], st[3], stream, h->pend_tune);
   h->last_kernel[1] = lde::pend_last_kernel(1);
   if (rc) h->err = "lde_adjoint: kernel launch failed";
   return rc;

@@ -9,6 +9,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 
 #include "lde_types.h"
 
@@ -162,6 +163,56 @@ static PendFwdMap pend_forward_mapping(int kind, int solver, bool adaptive, bool
   if (tn.ws != 0 && T <= ts_lds_max && T > 2 && B <= 16384) return PEND_FWD_WS;   // (21.6 against 31.2 µs at 16 384, 36.8 against 32.6 at 32 768)
   if (tn.lb_ring > 0 && T > 1 && T <= 2048 && B >= tn.lb_min_b) return PEND_FWD_RING;
   return PEND_FWD_LANE;
+}
+
+// PEND_FWD_TL with at most 64 save intervals: a lane serves exactly one save time (the variant without a load in the stepping loop)
+static bool pend_tl_one_save_per_lane(int T) { return T - 1 <= 64; }
+
+// The row ring of PEND_FWD_RING (options "pend_lb" = rows: 8 / 16 / 32, "pend_lb_hold" = the hold margin, −1: half the ring); a recording
+// forward has the 16-row ring. A lane sits out while j ≥ jc + rows − hold; the slowest lane has j = jc, so hold ≤ rows − 1 keeps it (and
+// with it jc) moving — hold ≥ rows would hold EVERY lane on every iteration and the solve loop would never end.
+struct PendRing {
+  int rows, hold;
+};
+static PendRing pend_ring_shape(bool recording, const lde::PendTune& tn) {
+  const int rows = recording ? 16 : tn.lb_ring >= 32 ? 32 : tn.lb_ring >= 16 ? 16 : 8;
+  return {rows, std::max(0, std::min(tn.lb_hold >= 0 ? tn.lb_hold : rows / 2, rows - 1))};
+}
+
+// Which pullback of the analytic right-hand sides serves an lde_adjoint (csrc/lde_pendulum.hip's launch code switches on this; DESIGN.md
+// §4.2). LDE_SENSE_FORWARD_DUAL has a pullback of its own (csrc/lde_pend_dual.hip).
+enum PendAdjMap {
+  PEND_ADJ_SEQ = 0,   // k_pend_adjoint: a lane per trajectory, the reverse-time solve (LDE_SENSE_BACKSOLVE[_CHECKPOINTED])
+  PEND_ADJ_FUSED,     // k_pend_adjoint_fused: a workgroup per trajectory, a lane per save interval, the interval operators composed in a tree
+  PEND_ADJ_STREAM,    // k_pend_adjoint_stream: a lane per trajectory, interval by interval (large batches, long save grids)
+  PEND_ADJ_DISC_TP,   // k_pend_adjoint_disc_tp: LDE_SENSE_DISCRETE, a wave per trajectory, the recorded steps side by side
+  PEND_ADJ_DISC       // k_pend_adjoint_disc: LDE_SENSE_DISCRETE, a lane per trajectory
+};
+static PendAdjMap pend_adjoint_mapping(int sensealg, int B, int T, const lde::PendTune& tn) {
+  // a wave per trajectory while the chip has waves to spare (option "pend_disc_tp_max_b"); 16·T + 3 168 bytes of LDS: within the 64 KB a
+  // launch gets without asking
+  if (sensealg == LDE_SENSE_DISCRETE) return T > 1 && T <= 3840 && B <= tn.disc_tp_max_b ? PEND_ADJ_DISC_TP : PEND_ADJ_DISC;
+  // measured (abl/adj_B.py): fused 9.5 µs vs stream 39 µs at 4096, 48 vs 41 µs at 32768
+  if (sensealg == LDE_SENSE_PARALLEL_CHECKPOINTED) return T > 1 && T - 1 <= 1024 && B <= 24576 ? PEND_ADJ_FUSED : PEND_ADJ_STREAM;
+  return PEND_ADJ_SEQ;
+}
+
+// The template arguments of the analytic right-hand sides' kernels: calls f(KIND, SOLVER, ADAPT) with std::integral_constants for exactly
+// the six combinations validate() admits — two right-hand sides × {Tsit5 adaptive, Tsit5 fixed-step, RK4 fixed-step} — and returns what f
+// returns; anything else is LDE_ERR_UNSUPPORTED. Kernels without an ADAPT parameter ignore the third argument.
+template <int KIND, class F>
+static int pend_dispatch_solver(int solver, bool adaptive, F& f) {
+  using K = std::integral_constant<int, KIND>;
+  using TSIT5 = std::integral_constant<int, LDE_SOLVER_TSIT5>;
+  if (solver == LDE_SOLVER_TSIT5) return adaptive ? f(K{}, TSIT5{}, std::true_type{}) : f(K{}, TSIT5{}, std::false_type{});
+  if (solver == LDE_SOLVER_RK4 && !adaptive) return f(K{}, std::integral_constant<int, LDE_SOLVER_RK4>{}, std::false_type{});
+  return LDE_ERR_UNSUPPORTED;
+}
+template <class F>
+static int pend_dispatch(int kind, int solver, bool adaptive, F&& f) {
+  if (kind == LDE_RHS_PENDULUM) return pend_dispatch_solver<LDE_RHS_PENDULUM>(solver, adaptive, f);
+  if (kind == LDE_RHS_PENDULUM_FRICTION) return pend_dispatch_solver<LDE_RHS_PENDULUM_FRICTION>(solver, adaptive, f);
+  return LDE_ERR_UNSUPPORTED;
 }
 
 // Which mapping serves a solve under LDE_SENSE_FORWARD_DUAL (csrc/lde_pend_dual.hip switches on this). Kept apart from pend_forward_mapping,

@@ -294,22 +294,16 @@ int launch_pend_forward_dual(int kind, int solver, const float* z0, const float*
                              int32_t* ret, hipStream_t stream) {
   const int block = dual_block(o.B), grid = (o.B + block - 1) / block;
   const size_t shm = o.T <= DUAL_TS_LDS_MAX ? (size_t)o.T * sizeof(double) : 0;
-#define LDE_LAUNCH_DUAL(K, S)                                                                                                        \
-  do {                                                                                                                               \
-    if (shm)                                                                                                                         \
-      hipLaunchKernelGGL((k_pend_forward_dual<K, S, true>), dim3(grid), dim3(block), shm, stream, (const float2*)z0, theta, ts_dev, o, \
-                         rec, (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                                        \
-    else                                                                                                                             \
-      hipLaunchKernelGGL((k_pend_forward_dual<K, S, false>), dim3(grid), dim3(block), 0, stream, (const float2*)z0, theta, ts_dev, o, \
-                         rec, (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                                        \
-  } while (0)
-  if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH_DUAL(0, LDE_SOLVER_TSIT5);
-  else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_RK4) LDE_LAUNCH_DUAL(0, LDE_SOLVER_RK4);
-  else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH_DUAL(1, LDE_SOLVER_TSIT5);
-  else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_RK4) LDE_LAUNCH_DUAL(1, LDE_SOLVER_RK4);
-  else return LDE_ERR_UNSUPPORTED;
-#undef LDE_LAUNCH_DUAL
-  return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
+  const int rc = lde_host::pend_dispatch(kind, solver, o.adaptive != 0, [&](auto K, auto S, auto) -> int {
+    if (shm)
+      hipLaunchKernelGGL((k_pend_forward_dual<K, S, true>), dim3(grid), dim3(block), shm, stream, (const float2*)z0, theta, ts_dev, o, rec,
+                         (float2*)z_out, retcode, nfe, nacc, nrej, ret);
+    else
+      hipLaunchKernelGGL((k_pend_forward_dual<K, S, false>), dim3(grid), dim3(block), 0, stream, (const float2*)z0, theta, ts_dev, o, rec,
+                         (float2*)z_out, retcode, nfe, nacc, nrej, ret);
+    return LDE_OK;
+  });
+  return rc != LDE_OK ? rc : hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
 }
 
 int launch_pend_adjoint_dual(const DualRec& rec, const float* dz_out, int T, int B, float* dz0, float* dtheta, int32_t* nfe,

@@ -1308,12 +1308,12 @@ __global__ void __launch_bounds__(256) k_pend_adjoint(const float2* __restrict__
 
 // ---- parallel-in-time checkpointed adjoint (LDE_SENSE_PARALLEL_CHECKPOINTED) ---------------------------------------
 // With z reset to the saved ẑ(t_j) at every save time, the T−1 save intervals are independent, and λ (and g) enter
-// the reverse-time system linearly. Phase 1 gives every (trajectory b, interval j) pair its own lane, which integrates
+// the reverse-time system linearly. Every (trajectory b, interval j) pair gets its own lane, which integrates
 // [z | λᵃ λᵇ | gᵃ gᵇ] (λᵃ(t_{j+1}) = e₁, λᵇ(t_{j+1}) = e₂) from t_{j+1} down to t_j: the 2×2 transition matrix M_j and
-// the row n_j of the parameter-gradient functional. Phase 2 composes them with a 49-term scan per trajectory:
+// the row n_j of the parameter-gradient functional. k_pend_adjoint_fused composes them per trajectory:
 //   g += n_j·λ ;  λ ← M_j λ + Δ_j.
-// The sequential chain of ≥49 Tsit5 steps per trajectory (k_pend_adjoint) becomes ≈1–2 steps + 49·8 FMAs, and a batch
-// of 256 trajectories fills 196 wavefronts instead of 4.
+// The sequential chain of ≥49 Tsit5 steps per trajectory (k_pend_adjoint) becomes ≈1–2 steps + a tree of compositions, and a
+// batch of 256 trajectories fills 256 wavefronts instead of 4.
 template <int KIND>
 struct PendBasis {
   float ngl, gl2;
@@ -1531,26 +1531,6 @@ __device__ __forceinline__ int pend_interval_operator(float2 zc, float L, double
   return ret;
 }
 
-// two-kernel form (large batches: every access coalesced over the batch index)
-template <int KIND, int SOLVER>
-__global__ void __launch_bounds__(256) k_pend_adjoint_par1(const float2* __restrict__ z_out, const float* __restrict__ theta,
-                                                           const double* __restrict__ ts_g, KOpts o,
-                                                           float* __restrict__ ops, int32_t* __restrict__ info) {
-  const int T = o.T, B = o.B;
-  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= (T - 1) * B) return;
-  const int j = gid / B, b = gid - j * B;   // lanes of a wave share j and cover consecutive b (coalesced)
-  float y[8];
-  int nacc, nrej;
-  const int ret = pend_interval_operator<KIND, SOLVER>(z_out[(size_t)(j + 1) * B + b], theta[b], ts_g[j], ts_g[j + 1], o, y,
-                                                       nacc, nrej);
-  // operator of interval j for trajectory b: [la0 la1 lb0 lb1 ga gb], plane-major so that phase 2 reads coalesced
-  const size_t plane = (size_t)(T - 1) * B, at = (size_t)j * B + b;
-#pragma unroll
-  for (int i = 0; i < 6; i++) ops[(size_t)i * plane + at] = y[2 + i];
-  info[at] = (ret << 24) | (min(nrej, 4095) << 12) | min(nacc, 4095);
-}
-
 // fused form (small/medium batches): one workgroup per trajectory, one lane per save interval; the interval operators
 // never leave registers — they are composed by an order-preserving tree reduction over the wave (affine maps
 // (λ,g) ↦ (Mλ+Δ, g+n·λ+γ) compose associatively), then across waves through LDS.
@@ -1691,233 +1671,6 @@ __global__ void __launch_bounds__(1024) k_pend_adjoint_fused(const float2* __res
     st_nfe[b] = (T - 1) + 6 * (nacc + nrej);
     st_ret[b] = ret;
   }
-}
-
-__global__ void __launch_bounds__(256) k_pend_adjoint_par2(const float2* __restrict__ z_out, const float2* __restrict__ dz_out,
-                                                           const float* __restrict__ ops, const int32_t* __restrict__ info,
-                                                           int T, int B, float2* __restrict__ dz0, float* __restrict__ dtheta,
-                                                           int32_t* __restrict__ st_nfe, int32_t* __restrict__ st_nacc,
-                                                           int32_t* __restrict__ st_nrej, int32_t* __restrict__ st_ret) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const float2 zT = z_out[(size_t)(T - 1) * B + b];
-  const float2 dT = dz_out[(size_t)(T - 1) * B + b];
-  float l0 = dT.x, l1 = dT.y, g = 0.f;
-  int ret = (isfinite(zT.x) && isfinite(zT.y)) ? 0 : LDE_RET_NONFINITE;
-  int nacc = 0, nrej = 0;
-  const size_t plane = (size_t)(T - 1) * B;
-  for (int j = T - 2; j >= 0; j--) {
-    const size_t at = (size_t)j * B + b;
-    const float la0 = ops[at], la1 = ops[plane + at], lb0 = ops[2 * plane + at], lb1 = ops[3 * plane + at];
-    const float ga = ops[4 * plane + at], gb = ops[5 * plane + at];
-    const float2 d = dz_out[at];
-    const int inf = info[at];
-    g += ga * l0 + gb * l1;
-    const float n0 = la0 * l0 + lb0 * l1 + d.x;
-    const float n1 = la1 * l0 + lb1 * l1 + d.y;
-    l0 = n0;
-    l1 = n1;
-    nacc += inf & 4095;
-    nrej += (inf >> 12) & 4095;
-    if (!ret) ret = inf >> 24;
-  }
-  dz0[b] = ret ? make_float2(0.f, 0.f) : make_float2(l0, l1);
-  dtheta[b] = ret ? 0.f : g;
-  st_nacc[b] = nacc;
-  st_nrej[b] = nrej;
-  st_nfe[b] = (T - 1) + 6 * (nacc + nrej);
-  st_ret[b] = ret;
-}
-
-// ---- host-side launchers (called from lde_api.cpp) -------------------------------------------------
-static inline int pick_block(int B) { return B <= 4096 ? 64 : 256; }
-
-int launch_pend_forward(int kind, int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o,
-                        float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret,
-                        hipStream_t stream, const PendTune& tn) {
-  const int block = pick_block(o.B), grid = (o.B + block - 1) / block;
-  const size_t shm = o.T <= TS_LDS_MAX ? (size_t)o.T * sizeof(double) : 0;
-  // which mapping serves this solve: csrc/lde_host.h (pend_forward_mapping — pure host logic, tested on the CPU: tests/test_sanitizers.py)
-  const bool recording = o.rec.n != nullptr;   // k_pend_forward_lp / _sh, k_pend_forward_ws, k_pend_forward and the 16-row ring form write step records
-  const lde_host::PendFwdMap map = lde_host::pend_forward_mapping(kind, solver, o.adaptive != 0, recording, o.B, o.T, tn, TS_LDS_MAX);
-  const bool lp_shape = map == lde_host::PEND_FWD_LP4 || map == lde_host::PEND_FWD_LP3;
-  if (lp_shape || map == lde_host::PEND_FWD_SH) {
-    const bool ad = o.adaptive != 0;
-    const int g8 = ((o.B + 7) / 8) * 8;
-#define LDE_LAUNCH_SH(K, S, A)                                                                                          \
-  do {                                                                                                                  \
-    if (o.rec.n)                                                                                                        \
-      hipLaunchKernelGGL((k_pend_forward_sh<K, S, A, true>), dim3(g8), dim3(64 * (1 + SH_NH)), 0, stream, (const float2*)z0, theta, ts_dev, o,  \
-                         (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                                \
-    else                                                                                                                \
-      hipLaunchKernelGGL((k_pend_forward_sh<K, S, A, false>), dim3(g8), dim3(64 * (1 + SH_NH)), 0, stream, (const float2*)z0, theta, ts_dev, o, \
-                         (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                                \
-  } while (0)
-    g_pend_last[0] = lp_shape ? "k_pend_forward_lp" : "k_pend_forward_sh";
-    if (lp_shape) {
-      // the metric's shape: the stepping wave's lanes in pairs, the step as a Nyström scheme (lde_pend_lp.h; option "pend_lp" = 0: k_pend_forward_sh);
-      // four dense-output waves while at most two workgroups share a CU, three beyond
-#define LDE_LAUNCH_LP(R, NH)                                                                                                              \
-  hipLaunchKernelGGL((k_pend_forward_lp<R, NH>), dim3(g8), dim3(64 * (1 + NH)), 0, stream, (const float2*)z0, theta, ts_dev, o, (float2*)z_out, \
-                     retcode, nfe, nacc, nrej, ret)
-      if (map == lde_host::PEND_FWD_LP4) {
-        if (o.rec.n) LDE_LAUNCH_LP(true, 4);
-        else LDE_LAUNCH_LP(false, 4);
-      } else {
-        if (o.rec.n) LDE_LAUNCH_LP(true, 3);
-        else LDE_LAUNCH_LP(false, 3);
-      }
-#undef LDE_LAUNCH_LP
-    } else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5 && ad) LDE_LAUNCH_SH(0, LDE_SOLVER_TSIT5, true);
-    else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH_SH(0, LDE_SOLVER_TSIT5, false);
-    else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_RK4) LDE_LAUNCH_SH(0, LDE_SOLVER_RK4, false);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5 && ad) LDE_LAUNCH_SH(1, LDE_SOLVER_TSIT5, true);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH_SH(1, LDE_SOLVER_TSIT5, false);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_RK4) LDE_LAUNCH_SH(1, LDE_SOLVER_RK4, false);
-    else return LDE_ERR_UNSUPPORTED;
-#undef LDE_LAUNCH_SH
-    return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
-  }
-  if (map == lde_host::PEND_FWD_TL) {
-    g_pend_last[0] = "k_pend_forward_tl";
-    const bool ad = o.adaptive != 0;
-    const bool few = o.T - 1 <= 64;   // a lane serves exactly one save time: the variant without a load in the stepping loop
-#define LDE_LAUNCH_TL(K, S, A)                                                                                          \
-  do {                                                                                                                  \
-    if (few)                                                                                                            \
-      hipLaunchKernelGGL((k_pend_forward_tl<K, S, A, 1, true>), dim3(((o.B + 7) / 8) * 8), dim3(64), 0, stream, (const float2*)z0, theta, ts_dev, o, \
-                         (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                                \
-    else                                                                                                                \
-      hipLaunchKernelGGL((k_pend_forward_tl<K, S, A, 1>), dim3(((o.B + 7) / 8) * 8), dim3(64), 0, stream, (const float2*)z0, theta, ts_dev, o, \
-                         (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                                \
-  } while (0)
-    if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5 && ad) LDE_LAUNCH_TL(0, LDE_SOLVER_TSIT5, true);
-    else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH_TL(0, LDE_SOLVER_TSIT5, false);
-    else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_RK4) LDE_LAUNCH_TL(0, LDE_SOLVER_RK4, false);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5 && ad) LDE_LAUNCH_TL(1, LDE_SOLVER_TSIT5, true);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH_TL(1, LDE_SOLVER_TSIT5, false);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_RK4) LDE_LAUNCH_TL(1, LDE_SOLVER_RK4, false);
-    else return LDE_ERR_UNSUPPORTED;
-#undef LDE_LAUNCH_TL
-    return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
-  }
-  if (map == lde_host::PEND_FWD_WS) {   // (writes step records too)
-    g_pend_last[0] = "k_pend_forward_ws";
-    const size_t lds = (size_t)((o.T + 1) & ~1) * sizeof(double) + (size_t)WS_CAP * 64 * WS_RW * sizeof(float);
-    const int g64 = (o.B + 63) / 64;
-#define LDE_LAUNCH_WS(K, S, A)                                                                                         \
-  do {                                                                                                                 \
-    static bool attr = false;                                                                                          \
-    if (!attr) {                                                                                                       \
-      if (hipFuncSetAttribute((const void*)k_pend_forward_ws<K, S, A, false>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              160 * 1024 - 2048) != hipSuccess ||                                                       \
-          hipFuncSetAttribute((const void*)k_pend_forward_ws<K, S, A, true>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              160 * 1024 - 2048) != hipSuccess)                                                         \
-        return LDE_ERR_HIP;                                                                                            \
-      attr = true;                                                                                                     \
-    }                                                                                                                  \
-    if (recording)                                                                                                     \
-      hipLaunchKernelGGL((k_pend_forward_ws<K, S, A, true>), dim3(g64), dim3(WS_THREADS), lds, stream, (const float2*)z0, theta, ts_dev, \
-                         o, (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                            \
-    else                                                                                                               \
-      hipLaunchKernelGGL((k_pend_forward_ws<K, S, A, false>), dim3(g64), dim3(WS_THREADS), lds, stream, (const float2*)z0, theta, ts_dev, \
-                         o, (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                            \
-  } while (0)
-    const bool ad = o.adaptive != 0;
-    if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5 && ad) LDE_LAUNCH_WS(0, LDE_SOLVER_TSIT5, true);
-    else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH_WS(0, LDE_SOLVER_TSIT5, false);
-    else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_RK4) LDE_LAUNCH_WS(0, LDE_SOLVER_RK4, false);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5 && ad) LDE_LAUNCH_WS(1, LDE_SOLVER_TSIT5, true);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH_WS(1, LDE_SOLVER_TSIT5, false);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_RK4) LDE_LAUNCH_WS(1, LDE_SOLVER_RK4, false);
-    else return LDE_ERR_UNSUPPORTED;
-#undef LDE_LAUNCH_WS
-    return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
-  }
-  // large batches (B ≥ 2¹⁷ — option "pend_lb_min_b"; T ≤ 2048): the lanes-as-save-times kernel with 64 trajectories per wave, the row ring
-  // and the save grid in LDS (k_pend_forward_tl<…, 64, false, RING>). k_pend_forward's per-lane stores reach HBM as partial lines —
-  // 1128 MB written for 419 MB of ẑ at B = 2²⁰ — and the launch is bound by that traffic: 303 µs. With 16 ring rows and an 8-row hold
-  // 444 … 574 MB are written and the launch takes 206 µs (2.1 TB/s of ẑ; abl/pend_LB.py, abl/pend_LB_pmc.sh); 8 rows / 3 the same within the
-  // run-to-run spread, 32 rows leave 2.5 waves per SIMD (16 KB of LDS per wave) and take 258 µs. What remains is instruction issue:
-  // ≈ 8.2 k instructions per wave (5.1 k VALU), of which the wave-sequential dense-output loop is ≈ 75 × 45 and the row flush 49 × 28.
-  // options "pend_lb" = rows of the ring (8 / 16 / 32; 0: off), "pend_lb_hold" = the hold margin.
-  const int lb_ring = tn.lb_ring;   // rows of the ring; 0: off
-  if (map == lde_host::PEND_FWD_RING) {   // (the save grid in LDS beside the ring: T ≤ 2048; a recording forward: the 16-row ring)
-    g_pend_last[0] = "k_pend_forward_tl";
-    // a lane sits out while j ≥ jc + RING − hold; the slowest lane has j = jc, so hold ≤ RING − 1 keeps it (and with it jc) moving —
-    // hold ≥ RING would hold EVERY lane on every iteration and the solve loop would never end. Default: half the ring.
-    const int lb_hold_env = tn.lb_hold;
-    const int ring_rows = recording ? 16 : (lb_ring >= 32 ? 32 : (lb_ring >= 16 ? 16 : 8));
-    KOpts oh = o;
-    oh.lb_hold = std::max(0, std::min(lb_hold_env >= 0 ? lb_hold_env : ring_rows / 2, ring_rows - 1));
-    const bool ad = o.adaptive != 0;
-    const int g8 = (((o.B + 63) / 64 + 7) / 8) * 8;
-#define LDE_LAUNCH_LB(K, S, A)                                                                                          \
-  do {                                                                                                                  \
-    if (recording)                                                                                                      \
-      hipLaunchKernelGGL((k_pend_forward_tl<K, S, A, 64, false, 16, true>), dim3(g8), dim3(64), (size_t)o.T * sizeof(double), stream, (const float2*)z0, theta, ts_dev, oh, \
-                         (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                                \
-    else if (lb_ring >= 32)                                                                                             \
-      hipLaunchKernelGGL((k_pend_forward_tl<K, S, A, 64, false, 32>), dim3(g8), dim3(64), (size_t)o.T * sizeof(double), stream, (const float2*)z0, theta, ts_dev, oh, \
-                         (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                                \
-    else if (lb_ring >= 16)                                                                                             \
-      hipLaunchKernelGGL((k_pend_forward_tl<K, S, A, 64, false, 16>), dim3(g8), dim3(64), (size_t)o.T * sizeof(double), stream, (const float2*)z0, theta, ts_dev, oh, \
-                         (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                                \
-    else                                                                                                                \
-      hipLaunchKernelGGL((k_pend_forward_tl<K, S, A, 64, false, 8>), dim3(g8), dim3(64), (size_t)o.T * sizeof(double), stream, (const float2*)z0, theta, ts_dev, oh, \
-                         (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                                \
-  } while (0)
-    if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5 && ad) LDE_LAUNCH_LB(0, LDE_SOLVER_TSIT5, true);
-    else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH_LB(0, LDE_SOLVER_TSIT5, false);
-    else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_RK4) LDE_LAUNCH_LB(0, LDE_SOLVER_RK4, false);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5 && ad) LDE_LAUNCH_LB(1, LDE_SOLVER_TSIT5, true);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH_LB(1, LDE_SOLVER_TSIT5, false);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_RK4) LDE_LAUNCH_LB(1, LDE_SOLVER_RK4, false);
-    else return LDE_ERR_UNSUPPORTED;
-#undef LDE_LAUNCH_LB
-    return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
-  }
-  g_pend_last[0] = "k_pend_forward<";
-#define LDE_LAUNCH(K, S)                                                                                              \
-  do {                                                                                                                \
-    if (shm)                                                                                                          \
-      hipLaunchKernelGGL((k_pend_forward<K, S, true>), dim3(grid), dim3(block), shm, stream, (const float2*)z0, theta,  \
-                         ts_dev, o, (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                   \
-    else                                                                                                              \
-      hipLaunchKernelGGL((k_pend_forward<K, S, false>), dim3(grid), dim3(block), 0, stream, (const float2*)z0, theta,   \
-                         ts_dev, o, (float2*)z_out, retcode, nfe, nacc, nrej, ret);                                   \
-  } while (0)
-  if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH(0, LDE_SOLVER_TSIT5);
-  else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_RK4) LDE_LAUNCH(0, LDE_SOLVER_RK4);
-  else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH(1, LDE_SOLVER_TSIT5);
-  else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_RK4) LDE_LAUNCH(1, LDE_SOLVER_RK4);
-  else return LDE_ERR_UNSUPPORTED;
-#undef LDE_LAUNCH
-  return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
-}
-
-int launch_pend_adjoint(int kind, int solver, const float* z_out, const float* theta, const double* ts_dev,
-                        const KOpts& o, const float* dz_out, float* dz0, float* dtheta, int32_t* nfe, int32_t* nacc,
-                        int32_t* nrej, int32_t* ret, hipStream_t stream) {
-  const int block = pick_block(o.B), grid = (o.B + block - 1) / block;
-  const size_t shm = o.T <= TS_LDS_MAX ? (size_t)o.T * sizeof(double) : 0;
-  g_pend_last[1] = "k_pend_adjoint<";
-#define LDE_LAUNCH(K, S)                                                                                          \
-  do {                                                                                                              \
-    if (shm)                                                                                                        \
-      hipLaunchKernelGGL((k_pend_adjoint<K, S, true>), dim3(grid), dim3(block), shm, stream, (const float2*)z_out,    \
-                         theta, ts_dev, o, (const float2*)dz_out, (float2*)dz0, dtheta, nfe, nacc, nrej, ret);      \
-    else                                                                                                            \
-      hipLaunchKernelGGL((k_pend_adjoint<K, S, false>), dim3(grid), dim3(block), 0, stream, (const float2*)z_out,     \
-                         theta, ts_dev, o, (const float2*)dz_out, (float2*)dz0, dtheta, nfe, nacc, nrej, ret);      \
-  } while (0)
-  if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH(0, LDE_SOLVER_TSIT5);
-  else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_RK4) LDE_LAUNCH(0, LDE_SOLVER_RK4);
-  else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH(1, LDE_SOLVER_TSIT5);
-  else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_RK4) LDE_LAUNCH(1, LDE_SOLVER_RK4);
-  else return LDE_ERR_UNSUPPORTED;
-#undef LDE_LAUNCH
-  return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
 }
 
 // ---- discrete (exact) sensitivity: LDE_SENSE_DISCRETE ---------------------------------------------------------------------------
@@ -2465,37 +2218,11 @@ __global__ void __launch_bounds__(64) k_pend_adjoint_disc_tp(const float2* __res
   }
 }
 
-int launch_pend_adjoint_disc(int kind, int solver, const float* z_out, const float* theta, const double* ts_dev, const KOpts& o,
-                             const float* dz_out, float* dz0, float* dtheta, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret,
-                             hipStream_t stream, const PendTune& tn) {
-  if (!o.rec.n || !o.rec.y) return LDE_ERR_INVALID_ARG;
-  const int block = pick_block(o.B), grid = (o.B + block - 1) / block;
-  const size_t shm = o.T <= TS_LDS_MAX ? (size_t)o.T * sizeof(double) : 0;
-  // the steps side by side (a wave per trajectory) while the chip has waves to spare: option "pend_disc_tp_max_b"
-  const bool tp = o.T > 1 && o.T <= 3840 && o.B <= tn.disc_tp_max_b;   // (16·T + 3 168 bytes of LDS: within the 64 KB a launch gets without asking)
-  g_pend_last[1] = tp ? "k_pend_adjoint_disc_tp" : "k_pend_adjoint_disc<";
-#define LDE_LAUNCH(K, S)                                                                                                         \
-  do {                                                                                                                           \
-    if (tp)                                                                                                                      \
-      hipLaunchKernelGGL((k_pend_adjoint_disc_tp<K, S>), dim3(((o.B + 7) / 8) * 8), dim3(64), (size_t)o.T * 16 + 66 * 12 * sizeof(float), stream, (const float2*)z_out, theta, ts_dev, o, \
-                         (const float2*)dz_out, (float2*)dz0, dtheta, nfe, nacc, nrej, ret);                                     \
-    else                                                                                                                         \
-      hipLaunchKernelGGL((k_pend_adjoint_disc<K, S>), dim3(grid), dim3(block), shm, stream, (const float2*)z_out, theta, ts_dev, o, \
-                         (const float2*)dz_out, (float2*)dz0, dtheta, nfe, nacc, nrej, ret);                                     \
-  } while (0)
-  if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH(0, LDE_SOLVER_TSIT5);
-  else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_RK4) LDE_LAUNCH(0, LDE_SOLVER_RK4);
-  else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH(1, LDE_SOLVER_TSIT5);
-  else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_RK4) LDE_LAUNCH(1, LDE_SOLVER_RK4);
-  else return LDE_ERR_UNSUPPORTED;
-#undef LDE_LAUNCH
-  return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
-}
-
 // ---- time-parallel adjoint's large-batch form: the same interval-by-interval control, streamed per trajectory -------------------
 // Beyond a few 10⁴ trajectories there is no parallelism left to win from giving every save interval its own lane, and the
-// two-kernel form above pays for it: six operator planes + an info word per (trajectory, interval) written and read back —
-// 2.7 KB per trajectory against 412 B of algorithmic traffic, 344 GB/s algorithmic at B = 2²⁰ — and integrates two basis
+// two-kernel form this kernel replaced (a lane per (trajectory, interval) writing its operator to HBM, a second kernel composing
+// them; abl/HISTORY.md §4.2b) paid for it: six operator planes + an info word per (trajectory, interval) written and read back —
+// 2.7 KB per trajectory against 412 B of algorithmic traffic, 344 GB/s algorithmic at B = 2²⁰ — and integrated two basis
 // vectors of λ where one actual λ is wanted. Here a lane owns a trajectory and walks its T−1 intervals from the last to the
 // first, each exactly as pend_interval_operator treats it (z reset to the saved ẑ(t_{j+1}), first attempt = the whole
 // interval, adaptive inside, no step size carried across the save time), but on the 5-state [z | λ | g] itself: the only
@@ -2665,69 +2392,146 @@ __global__ void __launch_bounds__(256) k_pend_adjoint_stream(const float2* __res
   st_ret[b] = ret;
 }
 
-// does the time-parallel adjoint need the operator planes in HBM for this shape? (only the two-kernel form does)
-// ONE decision, ONE caching policy (the switches are read once per process) for both the buffer reservation and the launcher: two
-// readers with different caching could disagree after an environment change and send a NULL `ops` into the two-kernel form.
-enum { PEND_ADJ_FUSED = 0, PEND_ADJ_STREAM = 1, PEND_ADJ_TWO_KERNEL = 2 };
-static int pend_adjoint_form(int B, int T) {
-  constexpr int fused_max_b = 24576;   // measured (abl/adj_B.py): fused 9.5 µs vs stream 39 µs at 4096, 48 vs 41 µs at 32768
-  constexpr bool stream_on = true;
-  if (T > 1 && T - 1 <= 1024 && B <= fused_max_b) return PEND_ADJ_FUSED;
-  return stream_on ? PEND_ADJ_STREAM : PEND_ADJ_TWO_KERNEL;
-}
-bool pend_adjoint_needs_ops(int B, int T) { return pend_adjoint_form(B, T) == PEND_ADJ_TWO_KERNEL; }
+// ---- host-side launchers (called from lde_api.hip) -------------------------------------------------------------------------------
+// Which kernel serves a call is decided in csrc/lde_host.h (pend_forward_mapping, pend_ring_shape, pend_adjoint_mapping: pure host logic,
+// checked on the CPU by tests/host_logic_driver.cpp), and lde_host::pend_dispatch turns (rhs_kind, solver, adaptive) into the kernels'
+// template arguments. What is left here is each mapping's grid, block and dynamic LDS.
+static inline int pick_block(int B) { return B <= 4096 ? 64 : 256; }
+// a launcher's status: its own refusal (LDE_ERR_UNSUPPORTED, a failed hipFuncSetAttribute), else what HIP says of the launch
+static int launch_status(int rc) { return rc != LDE_OK ? rc : hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP; }
 
-int launch_pend_adjoint_par(int kind, int solver, const float* z_out, const float* theta, const double* ts_dev,
-                            const KOpts& o, const float* dz_out, float* dz0, float* dtheta, float* ops, int32_t* info,
-                            int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream) {
-  const int form = pend_adjoint_form(o.B, o.T);
-  g_pend_last[1] = form == PEND_ADJ_FUSED ? "k_pend_adjoint_fused" : (form == PEND_ADJ_STREAM ? "k_pend_adjoint_stream" : "k_pend_adjoint_par");
-  if (form == PEND_ADJ_FUSED) {   // fused: one workgroup per trajectory, one lane per interval
-    const int block = ((o.T - 1 + 63) / 64) * 64;
-#define LDE_LAUNCH(K, S)                                                                                                  \
-  hipLaunchKernelGGL((k_pend_adjoint_fused<K, S>), dim3(((o.B + 7) / 8) * 8), dim3(block), 0, stream, (const float2*)z_out, theta, ts_dev, o, \
-                     (const float2*)dz_out, (float2*)dz0, dtheta, nfe, nacc, nrej, ret)
-    if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH(0, LDE_SOLVER_TSIT5);
-    else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_RK4) LDE_LAUNCH(0, LDE_SOLVER_RK4);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH(1, LDE_SOLVER_TSIT5);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_RK4) LDE_LAUNCH(1, LDE_SOLVER_RK4);
-    else return LDE_ERR_UNSUPPORTED;
-#undef LDE_LAUNCH
-    return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
-  }
-  if (form == PEND_ADJ_STREAM) {   // large batches: one lane per trajectory, interval by interval (k_pend_adjoint_stream)
-    const int block = 256, grid = (o.B + block - 1) / block;
-#define LDE_LAUNCH(K, S)                                                                                                  \
-  hipLaunchKernelGGL((k_pend_adjoint_stream<K, S>), dim3(grid), dim3(block), 0, stream, (const float2*)z_out, theta, ts_dev, o, \
-                     (const float2*)dz_out, (float2*)dz0, dtheta, nfe, nacc, nrej, ret)
-    if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH(0, LDE_SOLVER_TSIT5);
-    else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_RK4) LDE_LAUNCH(0, LDE_SOLVER_RK4);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH(1, LDE_SOLVER_TSIT5);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_RK4) LDE_LAUNCH(1, LDE_SOLVER_RK4);
-    else return LDE_ERR_UNSUPPORTED;
-#undef LDE_LAUNCH
-    return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
-  }
-  if (!ops || !info) return LDE_ERR_INVALID_ARG;   // the two-kernel form keeps its operator planes in HBM
-  if (o.T > 1) {
-    const long long n = (long long)(o.T - 1) * o.B;
-    const int block = n <= 65536 ? 64 : 256;
-    const int grid = (int)((n + block - 1) / block);
-#define LDE_LAUNCH(K, S)                                                                                                 \
-  hipLaunchKernelGGL((k_pend_adjoint_par1<K, S>), dim3(grid), dim3(block), 0, stream, (const float2*)z_out, theta, ts_dev, o, \
-                     ops, info)
-    if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH(0, LDE_SOLVER_TSIT5);
-    else if (kind == LDE_RHS_PENDULUM && solver == LDE_SOLVER_RK4) LDE_LAUNCH(0, LDE_SOLVER_RK4);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_TSIT5) LDE_LAUNCH(1, LDE_SOLVER_TSIT5);
-    else if (kind == LDE_RHS_PENDULUM_FRICTION && solver == LDE_SOLVER_RK4) LDE_LAUNCH(1, LDE_SOLVER_RK4);
-    else return LDE_ERR_UNSUPPORTED;
-#undef LDE_LAUNCH
-    if (hipGetLastError() != hipSuccess) return LDE_ERR_HIP;
-  }
-  const int block2 = pick_block(o.B), grid2 = (o.B + block2 - 1) / block2;
-  hipLaunchKernelGGL(k_pend_adjoint_par2, dim3(grid2), dim3(block2), 0, stream, (const float2*)z_out, (const float2*)dz_out, ops,
-                     info, o.T, o.B, (float2*)dz0, dtheta, nfe, nacc, nrej, ret);
-  return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
+int launch_pend_forward(int kind, int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o,
+                        float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret,
+                        hipStream_t stream, const PendTune& tn) {
+  const bool recording = o.rec.n != nullptr;   // k_pend_forward_lp / _sh, k_pend_forward_ws, k_pend_forward and the 16-row ring form write step records
+  const lde_host::PendFwdMap map = lde_host::pend_forward_mapping(kind, solver, o.adaptive != 0, recording, o.B, o.T, tn, TS_LDS_MAX);
+  const float2* z0v = (const float2*)z0;
+  float2* zo = (float2*)z_out;
+  const int g8 = ((o.B + 7) / 8) * 8;
+  return launch_status(lde_host::pend_dispatch(kind, solver, o.adaptive != 0, [&](auto K, auto S, auto A) -> int {
+    switch (map) {
+      case lde_host::PEND_FWD_LP4:
+      case lde_host::PEND_FWD_LP3:
+        // the metric's shape: the stepping wave's lanes in pairs, the step as a Nyström scheme (lde_pend_lp.h; option "pend_lp" = 0:
+        // k_pend_forward_sh); four dense-output waves while at most two workgroups share a CU, three beyond
+        g_pend_last[0] = "k_pend_forward_lp";
+        if (map == lde_host::PEND_FWD_LP4) {
+          if (recording)
+            hipLaunchKernelGGL((k_pend_forward_lp<true, 4>), dim3(g8), dim3(64 * (1 + 4)), 0, stream, z0v, theta, ts_dev, o, zo, retcode, nfe, nacc, nrej, ret);
+          else
+            hipLaunchKernelGGL((k_pend_forward_lp<false, 4>), dim3(g8), dim3(64 * (1 + 4)), 0, stream, z0v, theta, ts_dev, o, zo, retcode, nfe, nacc, nrej, ret);
+        } else {
+          if (recording)
+            hipLaunchKernelGGL((k_pend_forward_lp<true, 3>), dim3(g8), dim3(64 * (1 + 3)), 0, stream, z0v, theta, ts_dev, o, zo, retcode, nfe, nacc, nrej, ret);
+          else
+            hipLaunchKernelGGL((k_pend_forward_lp<false, 3>), dim3(g8), dim3(64 * (1 + 3)), 0, stream, z0v, theta, ts_dev, o, zo, retcode, nfe, nacc, nrej, ret);
+        }
+        break;
+      case lde_host::PEND_FWD_SH:
+        g_pend_last[0] = "k_pend_forward_sh";
+        if (recording)
+          hipLaunchKernelGGL((k_pend_forward_sh<K, S, A, true>), dim3(g8), dim3(64 * (1 + SH_NH)), 0, stream, z0v, theta, ts_dev, o, zo, retcode, nfe, nacc, nrej, ret);
+        else
+          hipLaunchKernelGGL((k_pend_forward_sh<K, S, A, false>), dim3(g8), dim3(64 * (1 + SH_NH)), 0, stream, z0v, theta, ts_dev, o, zo, retcode, nfe, nacc, nrej, ret);
+        break;
+      case lde_host::PEND_FWD_TL:
+        g_pend_last[0] = "k_pend_forward_tl";
+        if (lde_host::pend_tl_one_save_per_lane(o.T))
+          hipLaunchKernelGGL((k_pend_forward_tl<K, S, A, 1, true>), dim3(g8), dim3(64), 0, stream, z0v, theta, ts_dev, o, zo, retcode, nfe, nacc, nrej, ret);
+        else
+          hipLaunchKernelGGL((k_pend_forward_tl<K, S, A, 1>), dim3(g8), dim3(64), 0, stream, z0v, theta, ts_dev, o, zo, retcode, nfe, nacc, nrej, ret);
+        break;
+      case lde_host::PEND_FWD_WS: {   // (writes step records too)
+        g_pend_last[0] = "k_pend_forward_ws";
+        static bool attr = false;   // once per instantiation: more dynamic LDS than a launch gets without asking
+        if (!attr) {
+          if (hipFuncSetAttribute((const void*)k_pend_forward_ws<K, S, A, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048) != hipSuccess ||
+              hipFuncSetAttribute((const void*)k_pend_forward_ws<K, S, A, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048) != hipSuccess)
+            return LDE_ERR_HIP;
+          attr = true;
+        }
+        const size_t lds = (size_t)((o.T + 1) & ~1) * sizeof(double) + (size_t)WS_CAP * 64 * WS_RW * sizeof(float);
+        const int g64 = (o.B + 63) / 64;
+        if (recording)
+          hipLaunchKernelGGL((k_pend_forward_ws<K, S, A, true>), dim3(g64), dim3(WS_THREADS), lds, stream, z0v, theta, ts_dev, o, zo, retcode, nfe, nacc, nrej, ret);
+        else
+          hipLaunchKernelGGL((k_pend_forward_ws<K, S, A, false>), dim3(g64), dim3(WS_THREADS), lds, stream, z0v, theta, ts_dev, o, zo, retcode, nfe, nacc, nrej, ret);
+        break;
+      }
+      case lde_host::PEND_FWD_RING: {
+        // large batches (B ≥ 2¹⁷ — option "pend_lb_min_b"; T ≤ 2048): the lanes-as-save-times kernel with 64 trajectories per wave, the row
+        // ring and the save grid in LDS. k_pend_forward's per-lane stores reach HBM as partial lines — 1128 MB written for 419 MB of ẑ at
+        // B = 2²⁰ — and the launch is bound by that traffic: 303 µs. With 16 ring rows and an 8-row hold 444 … 574 MB are written and the
+        // launch takes 206 µs (2.1 TB/s of ẑ; abl/pend_LB.py, abl/pend_LB_pmc.sh); 8 rows / 3 the same within the run-to-run spread, 32 rows
+        // leave 2.5 waves per SIMD (16 KB of LDS per wave) and take 258 µs. What remains is instruction issue: ≈ 8.2 k instructions per wave
+        // (5.1 k VALU), of which the wave-sequential dense-output loop is ≈ 75 × 45 and the row flush 49 × 28.
+        g_pend_last[0] = "k_pend_forward_tl";
+        const lde_host::PendRing ring = lde_host::pend_ring_shape(recording, tn);
+        KOpts oh = o;
+        oh.lb_hold = ring.hold;
+        const int gr = (((o.B + 63) / 64 + 7) / 8) * 8;
+        const size_t lds = (size_t)o.T * sizeof(double);
+        if (ring.rows == 32)
+          hipLaunchKernelGGL((k_pend_forward_tl<K, S, A, 64, false, 32>), dim3(gr), dim3(64), lds, stream, z0v, theta, ts_dev, oh, zo, retcode, nfe, nacc, nrej, ret);
+        else if (ring.rows == 8)
+          hipLaunchKernelGGL((k_pend_forward_tl<K, S, A, 64, false, 8>), dim3(gr), dim3(64), lds, stream, z0v, theta, ts_dev, oh, zo, retcode, nfe, nacc, nrej, ret);
+        else if (recording)
+          hipLaunchKernelGGL((k_pend_forward_tl<K, S, A, 64, false, 16, true>), dim3(gr), dim3(64), lds, stream, z0v, theta, ts_dev, oh, zo, retcode, nfe, nacc, nrej, ret);
+        else
+          hipLaunchKernelGGL((k_pend_forward_tl<K, S, A, 64, false, 16>), dim3(gr), dim3(64), lds, stream, z0v, theta, ts_dev, oh, zo, retcode, nfe, nacc, nrej, ret);
+        break;
+      }
+      default: {   // PEND_FWD_LANE
+        g_pend_last[0] = "k_pend_forward<";
+        const int block = pick_block(o.B), grid = (o.B + block - 1) / block;
+        if (o.T <= TS_LDS_MAX)
+          hipLaunchKernelGGL((k_pend_forward<K, S, true>), dim3(grid), dim3(block), (size_t)o.T * sizeof(double), stream, z0v, theta, ts_dev, o, zo, retcode, nfe, nacc, nrej, ret);
+        else
+          hipLaunchKernelGGL((k_pend_forward<K, S, false>), dim3(grid), dim3(block), 0, stream, z0v, theta, ts_dev, o, zo, retcode, nfe, nacc, nrej, ret);
+      }
+    }
+    return LDE_OK;
+  }));
+}
+
+int launch_pend_adjoint(int kind, int solver, int sensealg, const float* z_out, const float* theta, const double* ts_dev, const KOpts& o,
+                        const float* dz_out, float* dz0, float* dtheta, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret,
+                        hipStream_t stream, const PendTune& tn) {
+  const lde_host::PendAdjMap map = lde_host::pend_adjoint_mapping(sensealg, o.B, o.T, tn);
+  const bool disc = map == lde_host::PEND_ADJ_DISC_TP || map == lde_host::PEND_ADJ_DISC;
+  if (disc && (!o.rec.n || !o.rec.y)) return LDE_ERR_INVALID_ARG;   // the discrete pullback sweeps the forward's step record
+  const float2* zo = (const float2*)z_out;
+  const float2* dzo = (const float2*)dz_out;
+  float2* d0 = (float2*)dz0;
+  const int block = pick_block(o.B), grid = (o.B + block - 1) / block, g8 = ((o.B + 7) / 8) * 8;
+  const size_t shm = o.T <= TS_LDS_MAX ? (size_t)o.T * sizeof(double) : 0;
+  return launch_status(lde_host::pend_dispatch(kind, solver, o.adaptive != 0, [&](auto K, auto S, auto) -> int {
+    switch (map) {
+      case lde_host::PEND_ADJ_FUSED:   // a workgroup per trajectory, a lane per save interval
+        g_pend_last[1] = "k_pend_adjoint_fused";
+        hipLaunchKernelGGL((k_pend_adjoint_fused<K, S>), dim3(g8), dim3(((o.T - 1 + 63) / 64) * 64), 0, stream, zo, theta, ts_dev, o, dzo, d0, dtheta, nfe, nacc, nrej, ret);
+        break;
+      case lde_host::PEND_ADJ_STREAM:   // a lane per trajectory, interval by interval
+        g_pend_last[1] = "k_pend_adjoint_stream";
+        hipLaunchKernelGGL((k_pend_adjoint_stream<K, S>), dim3((o.B + 255) / 256), dim3(256), 0, stream, zo, theta, ts_dev, o, dzo, d0, dtheta, nfe, nacc, nrej, ret);
+        break;
+      case lde_host::PEND_ADJ_DISC_TP:
+        g_pend_last[1] = "k_pend_adjoint_disc_tp";
+        hipLaunchKernelGGL((k_pend_adjoint_disc_tp<K, S>), dim3(g8), dim3(64), (size_t)o.T * 16 + 66 * 12 * sizeof(float), stream, zo, theta, ts_dev, o, dzo, d0, dtheta, nfe, nacc, nrej, ret);
+        break;
+      case lde_host::PEND_ADJ_DISC:
+        g_pend_last[1] = "k_pend_adjoint_disc<";
+        hipLaunchKernelGGL((k_pend_adjoint_disc<K, S>), dim3(grid), dim3(block), shm, stream, zo, theta, ts_dev, o, dzo, d0, dtheta, nfe, nacc, nrej, ret);
+        break;
+      default:   // PEND_ADJ_SEQ
+        g_pend_last[1] = "k_pend_adjoint<";
+        if (shm)
+          hipLaunchKernelGGL((k_pend_adjoint<K, S, true>), dim3(grid), dim3(block), shm, stream, zo, theta, ts_dev, o, dzo, d0, dtheta, nfe, nacc, nrej, ret);
+        else
+          hipLaunchKernelGGL((k_pend_adjoint<K, S, false>), dim3(grid), dim3(block), 0, stream, zo, theta, ts_dev, o, dzo, d0, dtheta, nfe, nacc, nrej, ret);
+    }
+    return LDE_OK;
+  }));
 }
 
 }  // namespace lde

@@ -172,7 +172,85 @@ int main() {
       const PendFwdMap r = m((int)(rnd() % 2), (int)(rnd() % 2), rnd() & 1, rnd() & 1, 1 + (int)(rnd() % (1 << 21)), 1 + (int)(rnd() % 7000), h);
       assert(r >= PEND_FWD_LP4 && r <= PEND_FWD_LANE);
     }
+    // the lanes-as-save-times form: one save time per lane up to 64 save intervals
+    assert(pend_tl_one_save_per_lane(2) && pend_tl_one_save_per_lane(65) && !pend_tl_one_save_per_lane(66));
   }
-  std::printf("host logic under ASan + UBSan: %d accepted, %d refused hostile descriptions; forward mappings as measured\n", n_ok, n_bad);
+  // 5. the large-batch forward's row ring: 16 rows when recording, else 32 / 16 / 8 from "pend_lb"; the hold clamped to [0, rows − 1]
+  {
+    lde::PendTune t;
+    auto ring = [&](bool rec, int lb, int hold) { t.lb_ring = lb; t.lb_hold = hold; return pend_ring_shape(rec, t); };
+    assert(ring(false, 16, -1).rows == 16 && ring(false, 16, -1).hold == 8);                            // the defaults: 16 rows, half held
+    assert(ring(true, 8, -1).rows == 16 && ring(true, 32, -1).rows == 16 && ring(true, 32, 3).hold == 3);
+    assert(ring(false, 32, -1).rows == 32 && ring(false, 33, -1).rows == 32 && ring(false, 32, -1).hold == 16);
+    assert(ring(false, 31, -1).rows == 16 && ring(false, 15, -1).rows == 8 && ring(false, 1, -1).rows == 8 && ring(false, 8, -1).hold == 4);
+    // tests/test_gpu_pendulum.py's "lb8": 8 rows, a requested hold of 8 — clamped to 7, or no lane would ever move
+    assert(ring(false, 8, 8).rows == 8 && ring(false, 8, 8).hold == 7);
+    assert(ring(false, 8, 7).hold == 7 && ring(false, 8, 0).hold == 0 && ring(false, 32, 1 << 30).hold == 31 && ring(true, 8, 16).hold == 15);
+    for (int it = 0; it < 20000; it++) {
+      const PendRing r = ring(rnd() & 1, hostile_int(), hostile_int());
+      assert((r.rows == 8 || r.rows == 16 || r.rows == 32) && r.hold >= 0 && r.hold < r.rows);
+    }
+  }
+  // 6. which pullback serves an lde_adjoint of the analytic right-hand sides (csrc/lde_pendulum.hip's launch code switches on this)
+  {
+    const lde::PendTune def;
+    const int DI = LDE_SENSE_DISCRETE, PA = LDE_SENSE_PARALLEL_CHECKPOINTED;
+    // the time-parallel continuous pullback: fused for B ≤ 24 576 and 1 ≤ T − 1 ≤ 1024, streamed per trajectory otherwise
+    assert(pend_adjoint_mapping(PA, 256, 50, def) == PEND_ADJ_FUSED && pend_adjoint_mapping(PA, 24576, 50, def) == PEND_ADJ_FUSED);
+    assert(pend_adjoint_mapping(PA, 24577, 50, def) == PEND_ADJ_STREAM && pend_adjoint_mapping(PA, 1 << 20, 50, def) == PEND_ADJ_STREAM);
+    assert(pend_adjoint_mapping(PA, 1, 2, def) == PEND_ADJ_FUSED && pend_adjoint_mapping(PA, 64, 1025, def) == PEND_ADJ_FUSED);
+    assert(pend_adjoint_mapping(PA, 64, 1026, def) == PEND_ADJ_STREAM && pend_adjoint_mapping(PA, 1, 1, def) == PEND_ADJ_STREAM);
+    // the discrete pullback: a wave per trajectory for 1 < T ≤ 3840 and B ≤ "pend_disc_tp_max_b" (16 384), a lane per trajectory otherwise
+    assert(pend_adjoint_mapping(DI, 256, 50, def) == PEND_ADJ_DISC_TP && pend_adjoint_mapping(DI, 16384, 50, def) == PEND_ADJ_DISC_TP);
+    assert(pend_adjoint_mapping(DI, 16385, 50, def) == PEND_ADJ_DISC && pend_adjoint_mapping(DI, 1, 2, def) == PEND_ADJ_DISC_TP);
+    assert(pend_adjoint_mapping(DI, 1, 1, def) == PEND_ADJ_DISC && pend_adjoint_mapping(DI, 64, 3840, def) == PEND_ADJ_DISC_TP);
+    assert(pend_adjoint_mapping(DI, 64, 3841, def) == PEND_ADJ_DISC);
+    lde::PendTune t = def;
+    t.disc_tp_max_b = 0;
+    assert(pend_adjoint_mapping(DI, 1, 50, t) == PEND_ADJ_DISC);
+    t.disc_tp_max_b = 1 << 30;
+    assert(pend_adjoint_mapping(DI, 1 << 20, 50, t) == PEND_ADJ_DISC_TP && pend_adjoint_mapping(PA, 1 << 20, 50, t) == PEND_ADJ_STREAM);
+    // the reverse-time solve: a lane per trajectory, whatever the shape
+    for (int s : {LDE_SENSE_BACKSOLVE_CHECKPOINTED, LDE_SENSE_BACKSOLVE})
+      for (int B : {1, 256, 24577, 1 << 20}) assert(pend_adjoint_mapping(s, B, 50, def) == PEND_ADJ_SEQ && pend_adjoint_mapping(s, B, 5000, def) == PEND_ADJ_SEQ);
+    for (int it = 0; it < 20000; it++) {
+      lde::PendTune h;
+      h.disc_tp_max_b = hostile_int();
+      const PendAdjMap r = pend_adjoint_mapping((int)(rnd() % 5), hostile_int(), hostile_int(), h);
+      assert(r >= PEND_ADJ_SEQ && r <= PEND_ADJ_DISC);
+    }
+  }
+  // 7. the kernels' template arguments: exactly validate()'s six (rhs_kind, solver, adaptive) combinations reach the kernels
+  {
+    int seen[2][2][2] = {};
+    auto rec = [&](auto K, auto S, auto A) -> int {
+      static_assert(decltype(K)::value == 0 || decltype(K)::value == 1, "KIND");
+      seen[K][S][A]++;
+      return 100 * K + 10 * S + A;
+    };
+    const int P = LDE_RHS_PENDULUM, F = LDE_RHS_PENDULUM_FRICTION, TS = LDE_SOLVER_TSIT5, RK = LDE_SOLVER_RK4;
+    assert(pend_dispatch(P, TS, true, rec) == 1 && pend_dispatch(P, TS, false, rec) == 0 && pend_dispatch(P, RK, false, rec) == 10);
+    assert(pend_dispatch(F, TS, true, rec) == 101 && pend_dispatch(F, TS, false, rec) == 100 && pend_dispatch(F, RK, false, rec) == 110);
+    assert(pend_dispatch(P, RK, true, rec) == LDE_ERR_UNSUPPORTED && pend_dispatch(F, RK, true, rec) == LDE_ERR_UNSUPPORTED);   // adaptive RK4
+    assert(pend_dispatch(LDE_RHS_MLP, TS, true, rec) == LDE_ERR_UNSUPPORTED && pend_dispatch(LDE_RHS_PENDULUM_PLUS_MLP, TS, false, rec) == LDE_ERR_UNSUPPORTED);
+    assert(pend_dispatch(P, 2, false, rec) == LDE_ERR_UNSUPPORTED && pend_dispatch(-1, TS, true, rec) == LDE_ERR_UNSUPPORTED);
+    for (int k = 0; k < 2; k++)
+      for (int s = 0; s < 2; s++)
+        for (int a = 0; a < 2; a++) assert(seen[k][s][a] == (s == 1 && a == 1 ? 0 : 1));
+    // any arguments: f is called for a combination validate() admits, or not at all
+    for (int it = 0; it < 20000; it++) {
+      lde_problem_desc d = good();
+      d.rhs_kind = (rnd() & 1) ? hostile_int() : (int)(rnd() % 4);
+      d.solver = (rnd() & 1) ? hostile_int() : (int)(rnd() % 2);
+      d.adaptive = (int)(rnd() % 2);
+      d.dt = 0.05;
+      int called = 0;
+      const int rc = pend_dispatch(d.rhs_kind, d.solver, d.adaptive != 0, [&](auto, auto, auto) -> int { called++; return LDE_OK; });
+      assert(called == (rc == LDE_OK) && (rc == LDE_OK || rc == LDE_ERR_UNSUPPORTED));
+      assert(!called || (validate(&d, &why) == LDE_OK && has_pend(d) && !has_mlp(d)));
+    }
+  }
+  std::printf("host logic under ASan + UBSan: %d accepted, %d refused hostile descriptions; forward mappings as measured; "
+              "pullback mappings, ring shapes and kernel dispatch checked\n", n_ok, n_bad);
   return 0;
 }

@@ -191,7 +191,7 @@ def test_large_batch_properties(o32):
 
 @pytest.mark.parametrize("kind,tol", [(O.RHS_PENDULUM, (1e-6, 1e-3)), (O.RHS_PENDULUM_FRICTION, (1e-6, 1e-6))])
 def test_large_batch_adjoint_streams_per_trajectory(o32, o64, kind, tol):
-    """B = 2^16 + 5 > 32768: the time-parallel adjoint runs in its streaming form (k_pend_adjoint_stream: a lane per trajectory,
+    """B = 2^16 + 5 > 24576: the time-parallel adjoint runs in its streaming form (k_pend_adjoint_stream: a lane per trajectory,
     interval-by-interval control, algorithmic traffic only). Against the oracle's time-parallel adjoint and the float64 adjoint
     on a subsample (trajectories are independent), a trajectory with a NaN block (zero pullback), and bitwise determinism."""
     B, T = (1 << 16) + 5, 50
@@ -203,6 +203,7 @@ def test_large_batch_adjoint_streams_per_trajectory(o32, o64, kind, tol):
     assert (ret == 0).all()
     z[:, 77] = np.nan                                                   # a failed forward trajectory: the block is a constant
     g0, gL, _, st = nat.adjoint(z, L, ts, dz)
+    assert nat.lib.lde_last_kernel(nat.h, 1) == b"k_pend_adjoint_stream"
     assert st["nfailed"] == 1 and (g0[77] == 0).all() and gL[77] == 0
     assert st["naccept"] >= (B - 1) * (T - 1) and st["nfe"] == (B - 1) * (T - 1) + 6 * (st["naccept"] + st["nreject"]) + (T - 1)
     idx = np.concatenate([np.arange(0, B, 613), [B - 1]])
@@ -245,9 +246,9 @@ def test_torch_api_diffeq_layer(o32):
 
 @pytest.mark.parametrize("B,T", [(300, 100), (40000, 50), (64, 1300), (1, 2), (3, 65), (3, 66)])
 def test_parallel_adjoint_variants_agree_with_sequential_kernel(o32, B, T):
-    """The time-parallel adjoint has three code paths (fused one-wave, fused multi-wave via LDS, two-kernel coalesced
-    form for big batches / very long grids); each must reproduce the sequential checkpointed adjoint to solver tolerance
-    (both are the same continuous adjoint; abstol=reltol=1e-6 here ⇒ 2e-4 relative)."""
+    """The time-parallel adjoint has three code paths (fused one-wave, fused multi-wave via LDS, and the per-trajectory
+    stream for big batches / very long grids — B > 24576 or T − 1 > 1024); each must reproduce the sequential checkpointed
+    adjoint to solver tolerance (both are the same continuous adjoint; abstol=reltol=1e-6 here ⇒ 2e-4 relative)."""
     par, _ = _native(abstol=1e-6, reltol=1e-6, sensealg=O.SENSE_PARALLEL_CHECKPOINTED)
     seq, od = _native(abstol=1e-6, reltol=1e-6, sensealg=O.SENSE_BACKSOLVE_CHECKPOINTED)
     z0, L = O.pendulum_inputs(B, seed=7)
@@ -256,6 +257,8 @@ def test_parallel_adjoint_variants_agree_with_sequential_kernel(o32, B, T):
     z, ret, _ = par.forward(z0, L, ts)
     assert (ret == 0).all()
     g0, gL, _, sp = par.adjoint(z, L, ts, dz)
+    streamed = {(40000, 50), (64, 1300)}   # B > 24576, T − 1 > 1024
+    assert par.lib.lde_last_kernel(par.h, 1) == (b"k_pend_adjoint_stream" if (B, T) in streamed else b"k_pend_adjoint_fused")
     s0, sL, _, ss = seq.adjoint(z, L, ts, dz)
     assert sp["nfailed"] == 0 and sp["naccept"] >= B * (T - 1)
     assert np.abs(g0 - s0).max() <= 2e-4 * np.abs(s0).max()
@@ -296,7 +299,8 @@ def test_very_long_save_grid(o32):
     zr, _, _ = o32.forward(od, z0, L, ts)
     assert (ret == 0).all() and np.abs(z - zr).max() <= 1e-5
     dz = O.cotangent(T, B, 2)
-    g0, gL, _, _ = nat.adjoint(z, L, ts, dz)           # T−1 > 1024 ⇒ two-kernel time-parallel form
+    g0, gL, _, _ = nat.adjoint(z, L, ts, dz)           # T−1 > 1024 ⇒ the time-parallel adjoint streams per trajectory
+    assert nat.lib.lde_last_kernel(nat.h, 1) == b"k_pend_adjoint_stream"
     seq, ods = _native(abstol=1e-6, reltol=1e-6, sensealg=O.SENSE_BACKSOLVE_CHECKPOINTED)
     s0, sL, _, _ = seq.adjoint(z, L, ts, dz)           # sequential kernel, grid from L2 as well
     assert np.abs(g0 - s0).max() <= 2e-4 * np.abs(s0).max() and np.abs(gL - sL).max() <= 2e-4 * np.abs(sL).max()

@@ -1,8 +1,8 @@
 """CPU: AddressSanitizer + UndefinedBehaviorSanitizer over what runs on the CPU (SURVEY.md §5 "race detection / sanitizers"; GPU sanitizers are
 not available on this pool): (1) the oracle — everything the parity tests trust — driven at small, ragged, degenerate and failing shapes
 through every family of its entry points (oracle/asan_driver.c, f32 and f64 builds); (2) the C ABI's host-side logic — validation of a
-problem description, the weight count, the step-record layout arithmetic, the option block, grid checks (csrc/lde_host.h, which
-lde_api.hip is built from) — with 200 000 hostile descriptions (tests/host_logic_driver.cpp)."""
+problem description, the weight count, the step-record layout arithmetic, the option block, grid checks, the analytic path's kernel
+choices (csrc/lde_host.h, which lde_api.hip and the launch code are built from) — with 200 000 hostile descriptions (tests/host_logic_driver.cpp)."""
 import os
 import shutil
 import subprocess
@@ -36,6 +36,7 @@ def test_c_abi_host_logic_under_asan_ubsan(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, env=ENV, timeout=600)
     _clean(r)
     assert "accepted" in r.stdout and "forward mappings as measured" in r.stdout
+    assert "pullback mappings, ring shapes and kernel dispatch checked" in r.stdout
 
 
 def test_lde_api_is_built_from_the_checked_logic():
@@ -43,6 +44,11 @@ def test_lde_api_is_built_from_the_checked_logic():
     src = open(os.path.join(ROOT, "latentdiffeq.jl_amd", "csrc", "lde_api.hip")).read()
     assert '#include "lde_host.h"' in src and "using namespace lde_host" in src
     pend = open(os.path.join(ROOT, "latentdiffeq.jl_amd", "csrc", "lde_pendulum.hip")).read()
+    dual = open(os.path.join(ROOT, "latentdiffeq.jl_amd", "csrc", "lde_pend_dual.hip")).read()
     assert "lde_host::pend_forward_mapping(" in pend and "tn.sh_max_b" not in pend and "tn.tl_max_b" not in pend   # the launch code follows the checked function, no thresholds of its own
+    assert "lde_host::pend_adjoint_mapping(" in pend and "lde_host::pend_ring_shape(" in pend
+    assert "tn." not in pend and "24576" not in pend   # no PendTune field read and no pullback threshold outside lde_host.h
+    for s in (pend, dual):   # the (rhs_kind, solver, adaptive) → template-argument chain lives in lde_host::pend_dispatch only
+        assert "lde_host::pend_dispatch(" in s and "#define LDE_LAUNCH" not in s
     for fn in ("static int validate(", "static size_t rec_bytes(", "static lde::StepRec rec_view(", "static lde::KOpts make_opts("):
         assert fn not in src, fn
