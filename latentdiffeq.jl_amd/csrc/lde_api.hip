@@ -696,7 +696,9 @@ const char* lde_last_error(const lde_handle* h) { return h ? h->err.c_str() : "N
 
 const char* lde_last_kernel(const lde_handle* h, int which) {
   if (!h || which < 0 || which > 1) return "";
-  if (h->mlp) {   // the MLP families by the adjoint's last choice ("adjoint_family"); the forward solve runs the same family's forward instantiation
+  if (h->mlp) {   // the MLP families by the ADJOINT's last choice ("adjoint_family": lde_host::MlpFamily), whichever call is asked for: the forward is
+                  // mapped separately (lde_host::mlp_forward_mapping) and may run another family — a coupled fixed-step 8-200-200-8 solve at
+                  // B = 300 runs forward on k_mlpb and backward on k_mlpw; k_mlp4_adjoint has no forward at all (the tiles')
     static const char* fam[] = {"k_mlp_", "k_mlp64", "k_mlpb", "k_mlpc", "k_mlpw", "k_mlpv", "k_mlp4"};
     const int f = lde::mlp_last_family(h->mlp);
     return f >= 0 && f < 7 ? fam[f] : "";

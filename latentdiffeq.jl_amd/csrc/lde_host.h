@@ -225,6 +225,180 @@ enum PendDualMap {
 };
 static PendDualMap pend_dual_mapping(int B) { return B <= 4096 ? PEND_DUAL_LANE64 : PEND_DUAL_LANE256; }
 
+// ---- the MLP right-hand sides: which kernel family serves a solve / an lde_adjoint (csrc/lde_mlp.hip's launch code switches on this;
+// DESIGN.md §4.3 – §4.5). The values are what option "adjoint_family" and lde_last_kernel report. Every threshold is a measurement on the
+// MI355X (abl/, profiles/) or a residency limit of the 256 CUs; the LDS bytes arrive as numbers (lde::MlpLds).
+enum MlpFamily {
+  MLP_TILES = 0,     // k_mlp_forward / k_mlp_adjoint / k_mlp_adjoint_disc: 16 trajectories per workgroup on MFMA tiles, the weight gradient from the
+                     // staged panels (k_mlp_dw). Serves whatever nothing below takes.
+  MLP_64 = 1,        // k_mlp64: a wave per trajectory, everything in registers (three layers ≤ 64 wide, D′ ≤ 4, per-trajectory control)
+  MLP_B = 2,         // k_mlpb: four waves per trajectory, W₂ as register blocks, the weight gradient folded on the CU (H ≤ 200, D′ ≤ 16)
+  MLP_C = 3,         // k_mlpc: two trajectories per workgroup on one register copy of the weights (H ≤ 128, D′ ≤ 32, coupled control)
+  MLP_W = 4,         // k_mlpw: 2 / 4 waves per trajectory, weights and state in registers, the weight gradient staged (H ≤ 200, D′ ≤ 32)
+  MLP_V = 5,         // k_mlpv: a trajectory per workgroup, lanes = hidden units (every width ≤ 256), staged
+  MLP_4 = 6,         // k_mlp4_adjoint: four columns per wave, the weights in LDS (adjoint only; layers up to "mlp4_maxw" wide), staged
+  MLP_NOT_SERVED = 7 // LDE_ERR_UNSUPPORTED: *why says which of the two refusals
+};
+using lde::MlpLds;
+using lde::MlpShape;
+using lde::MlpTune;
+
+// The shape summary of a validated MLP problem: what the mappings below read, and which families the network fits at all (their register
+// and LDS layouts: csrc/lde_mlpv.h, lde_mlpw.h, lde_mlpb.h, lde_mlpc.h).
+static MlpShape mlp_shape(const lde_problem_desc& d) {
+  MlpShape s;
+  s.nL = d.n_layers;
+  s.Dp = d.state_dim + d.augment_dim;
+  s.P = d.param_dim;
+  for (int l = 0; l <= s.nL && l <= LDE_MAX_LAYERS; l++) s.maxw = std::max(s.maxw, d.layer_sizes[l]);
+  s.hm = s.nL == 3 ? std::max(d.layer_sizes[1], d.layer_sizes[2]) : 0;
+  s.coupled = d.batching == LDE_BATCH_COUPLED || d.batching == LDE_BATCH_COUPLED_GLOBAL;
+  s.global = d.batching == LDE_BATCH_COUPLED_GLOBAL;
+  s.disc = d.sensealg == LDE_SENSE_DISCRETE;
+  // the register families: three Dense layers, no analytic part, no per-trajectory parameters
+  const bool reg = s.nL == 3 && d.rhs_kind != LDE_RHS_PENDULUM_PLUS_MLP && s.P == 0 && s.hm >= 1;
+  s.w_ok = reg && s.Dp <= 32 && s.hm <= 200;
+  s.b_ok = reg && s.Dp <= 16 && s.hm <= 200;
+  s.c_ok = reg && s.Dp <= 32 && s.hm <= 128 && s.coupled;
+  s.w_waves = s.hm <= 128 ? 2 : 4;
+  // k_mlpv: every width ≤ 256; lanes = the widest layer rounded up to a power of two — or, with three layers and a hidden×hidden product
+  // of 17 … 128 units that stays in registers, 64 lanes (≤ 64 units) / 256 lanes (two lane groups split K) where that is no fewer
+  s.vec_ok = s.maxw <= 256;
+  int nt = 64;
+  while (nt < s.maxw && nt < 256) nt *= 2;
+  const int want = s.hm <= 64 ? 64 : 256;
+  s.v_reg = s.nL == 3 && s.hm > 16 && s.hm <= 128 && nt <= want;
+  s.v_nt = s.v_reg ? want : nt;
+  return s;
+}
+
+// one wave per trajectory: measured on the c3 shape — 0.28 + 3.9 ms against 0.61 + 5.8 for the tiles at B = 4096, 0.77 + 10.4 against 2.2 + 12.0 at 16 384
+static bool mlp64_serves(const MlpShape& s, const MlpTune& tn, int B) {
+  return tn.mlp64 && s.nL == 3 && s.hm <= 64 && s.Dp <= 4 && s.P <= 1 && !s.coupled && B <= 65536;
+}
+// k_mlp64's adjoint: workgroups of four waves (one per SIMD: the kernel takes more than 256 registers), at most 256 of them; a wave walks
+// trajectories b, b + 4·workgroups, … with ONE set of gradient sums, the four waves' sums meet in LDS, so the row workspace has one row per
+// workgroup whatever the batch
+constexpr int MLP64_NWV = 4;
+static int mlp64_adj_waves(int B) {   // = workgroups = rows
+  return (int)std::min<int64_t>(((int64_t)B + MLP64_NWV - 1) / MLP64_NWV, 256);
+}
+// k_mlpb. Option "mlpb": 0 = off (k_mlpw instead: this kernel's parity reference), 2 = also the networks of at most 128 units that k_mlpw's
+// two-wave form serves by default; "mlpw" = 0 switches BOTH register families and k_mlpc off (the tests' "tiles" / "mlpv" legs). One
+// workgroup per CU (512 registers per lane): 256 trajectories are resident at once; a solve whose workgroups may queue takes a second round.
+static bool mlpb_serves(const MlpShape& s, const MlpTune& tn, size_t lds, size_t cap, int B, bool resident) {
+  if (!s.b_ok || tn.mlpb == 0 || !tn.mlpw) return false;
+  if (s.hm <= 128 && tn.mlpb != 2) return false;
+  return lds <= cap && B <= (resident ? 256 : 512);
+}
+// k_mlpc (k_mlpb's switches). One workgroup = two trajectories per CU: 512 are resident at once.
+static bool mlpc_serves(const MlpShape& s, const MlpTune& tn, size_t lds, size_t cap, int B, bool resident) {
+  if (!s.c_ok || tn.mlpb == 0 || !tn.mlpw) return false;
+  return lds <= cap && B <= (resident ? 512 : 1024);
+}
+// k_mlpw. 4 / W workgroups share a CU's LDS (one wave per SIMD: the weights take most of the 512 registers), 1024 waves are resident at
+// once; an uncoupled solve may queue a second round.
+static bool mlpw_serves(const MlpShape& s, const MlpTune& tn, const MlpLds& l, int B, bool resident) {
+  if (!s.w_ok || !tn.mlpw || s.w_waves < 1) return false;
+  return l.w <= l.cap * (size_t)s.w_waves / 4 && (int64_t)B * s.w_waves <= (resident ? 1024 : 2048);
+}
+// k_mlpv's LDS per workgroup: everything when a CU gets one workgroup, a share otherwise (the launch code sizes the weight cache with it)
+static size_t mlpv_lds_budget(size_t cap, int B) {
+  const size_t per_cu = (size_t)std::max<int64_t>(1, ((int64_t)B + 255) / 256);
+  const size_t share = cap / per_cu;
+  return per_cu > 1 ? share - std::min<size_t>(share, 256) : share;
+}
+// k_mlpv. Measured (c2 / c3 / c4 shapes): the one-trajectory workgroups win while the chip has a SIMD per wave — B·NT/64 ≤ 1024: c2 0.88 +
+// 1.97 ms against 1.77 + 3.44 at B = 256, c3 0.36 + 4.28 against 0.63 + 5.0 at 1024, c4 0.46 + 3.77 against 0.45 + 4.3 at 512 — and lose
+// beyond (c2 at B = 1024: 1.94 + 4.5 against 1.78 + 3.9); with the register-resident layer two waves per SIMD still win. Coupled adaptive
+// control needs all B workgroups resident: their fixed part must fit the CU's share.
+static bool mlpv_serves(const MlpShape& s, const MlpTune& tn, const MlpLds& l, int B, bool resident) {
+  if (!s.vec_ok || !tn.mlpv || s.v_nt < 1) return false;
+  if (B > (s.v_reg ? 2048 : 1024) * 64 / s.v_nt || l.v_fixed > l.cap / 2) return false;
+  return !resident || mlpv_lds_budget(l.cap, B) >= l.v_fixed;
+}
+// k_mlp4_adjoint. Measured: one wave has ONE SIMD's matrix pipe and v_mfma_f32_4x4x1 costs 11 cycles per 256 MACs (the 16x16x4 form: 8), so
+// the kernel only wins while the layers are small enough for the tiles' fixed ≈ 2 000 cycles per layer to dominate: c3 (64 wide) 7.3 → 5.3 ms,
+// c4 (128 wide) 4.4 → 5.5 ms — hence "mlp4_maxw" = 64. Grid-wide sums need every workgroup resident.
+static bool mlp4_serves(const MlpShape& s, const MlpTune& tn, const MlpLds& l, bool coupled_adaptive) {
+  if (!tn.mlp4 || s.Dp > 64 || s.P > 1 || s.maxw > tn.mlp4_maxw || s.maxw > 256) return false;
+  return !(coupled_adaptive && l.mlp4_blocks > 256) && l.mlp4 <= l.cap;
+}
+static MlpFamily mlp_refuse(const char** why, const char* text) {
+  if (why) *why = text;
+  return MLP_NOT_SERVED;
+}
+static MlpFamily mlp_refuse_global(const char** why) {
+  return mlp_refuse(why, "LDE_BATCH_COUPLED_GLOBAL: this shape / batch is not served by the register kernels (three Dense layers, 2·D' ≤ 64, H ≤ 200, B·W ≤ 1024 waves)");
+}
+// the coupled adaptive tiles: 256 workgroups of 16 trajectories, one resident per CU, meet in the grid-wide sum
+static MlpFamily mlp_refuse_tiles(const char** why) {
+  return mlp_refuse(why, "coupled adaptive solve: batch per GPU limited to 4096 trajectories (one resident workgroup per CU)");
+}
+
+// The forward solve of B trajectories; `l`: the forward kernels' LDS for this save grid; `recording`: a step record is being written
+// (k_mlpw and k_mlpv write none; k_mlp64, k_mlpb, k_mlpc and the tiles do). Precedence as listed. A coupled ADAPTIVE solve of more than one
+// trajectory needs every workgroup resident (the grid-wide sum of the step control): that — not "coupled" — halves the limits here.
+static MlpFamily mlp_forward_mapping(const MlpShape& s, const MlpTune& tn, const MlpLds& l, int B, bool adaptive, bool recording, const char** why = nullptr) {
+  if (mlp64_serves(s, tn, B)) return MLP_64;
+  const bool ca = s.coupled && adaptive && B > 1;
+  if (mlpb_serves(s, tn, l.b, l.cap, B, ca)) return MLP_B;
+  if (mlpc_serves(s, tn, l.c, l.cap, B, ca)) return MLP_C;
+  if (!recording && mlpw_serves(s, tn, l, B, ca)) return MLP_W;
+  if (s.global) return mlp_refuse_global(why);   // only the register kernels exchange their sums across ranks
+  if (!recording && mlpv_serves(s, tn, l, B, ca)) return MLP_V;
+  if (s.coupled && adaptive && B > 4096) return mlp_refuse_tiles(why);
+  return MLP_TILES;
+}
+
+// lde_adjoint on B trajectories; `l`: the adjoint kernels' LDS for this save grid. Precedence as listed. Three different readings of
+// "coupled", each as measured / as the kernel needs it:
+//  · the continuous adjoint of k_mlpb / k_mlpc takes the resident limits (256 / 512) for EVERY coupled solve, fixed-step ones included —
+//    where the forward (above) takes them for adaptive ones only: a coupled fixed-step 8-200-200-8 solve at B = 300 runs forward on k_mlpb
+//    and backward on k_mlpw;
+//  · k_mlpw, k_mlpv: coupled && adaptive && B > 1, as in the forward; k_mlp4_adjoint: coupled && adaptive;
+//  · LDE_SENSE_DISCRETE sweeps a record without step control, hence without a grid-wide sum: workgroups may queue, and the register
+//    kernels take the shapes of the continuous adjoint (its LDS test at a batch within the limit) up to what a row of the workspace per
+//    workgroup costs in memory — B ≤ 1024 (k_mlpb) / 2048 (k_mlpc) — and what their sweeps' LDS allows; everything else runs on the tiles,
+//    and nothing is refused.
+static MlpFamily mlp_adjoint_mapping(const MlpShape& s, const MlpTune& tn, const MlpLds& l, int B, bool adaptive, const char** why = nullptr) {
+  if (mlp64_serves(s, tn, B)) return MLP_64;
+  if (s.disc) {
+    if (mlpb_serves(s, tn, l.b, l.cap, std::min(B, 256), false) && B <= 1024 && l.b_disc <= l.cap) return MLP_B;
+    if (mlpc_serves(s, tn, l.c, l.cap, std::min(B, 512), false) && B <= 2048 && l.c_disc <= l.cap) return MLP_C;
+    return MLP_TILES;
+  }
+  if (mlpb_serves(s, tn, l.b, l.cap, B, s.coupled)) return MLP_B;
+  if (mlpc_serves(s, tn, l.c, l.cap, B, s.coupled)) return MLP_C;
+  if (s.coupled && adaptive && B > 4096) return mlp_refuse_tiles(why);   // (the tile kernel runs behind the three staged families below)
+  const bool ca = s.coupled && adaptive && B > 1;
+  if (mlpw_serves(s, tn, l, B, ca)) return MLP_W;
+  if (s.global) return mlp_refuse_global(why);
+  if (mlpv_serves(s, tn, l, B, ca)) return MLP_V;
+  if (mlp4_serves(s, tn, l, s.coupled && adaptive)) return MLP_4;
+  return MLP_TILES;
+}
+
+// The adjoint's workspace follows from its family: k_mlp64, k_mlpb and k_mlpc fold the weight gradient in the solve kernel and leave rows
+// of it for k_sum_rows; every other family stages panels for k_mlp_dw. Rows the family WRITES for a batch (0: the staging area) …
+static int mlp_adjoint_rows(MlpFamily f, int B) {
+  return f == MLP_64 ? mlp64_adj_waves(B) : f == MLP_B ? B : f == MLP_C ? (int)(((int64_t)B + 1) / 2) : 0;
+}
+// … and rows lde_reserve sizes for it (k_mlpc: per trajectory). lde_reserve knows the batch and the grid but not the call: it asks the
+// mapping with adaptive = false — the three row families do not depend on `adaptive`
+static int mlp_reserved_rows(MlpFamily f, int B) {
+  return f == MLP_64 ? mlp64_adj_waves(B) : (f == MLP_B || f == MLP_C) ? B : 0;
+}
+
+// The template argument of the MLP kernels: calls f(SOLVER) with a std::integral_constant for the two solvers validate() admits and
+// returns what f returns; anything else is LDE_ERR_UNSUPPORTED.
+template <class F>
+static int mlp_dispatch(int solver, F&& f) {
+  if (solver == LDE_SOLVER_TSIT5) return f(std::integral_constant<int, LDE_SOLVER_TSIT5>{});
+  if (solver == LDE_SOLVER_RK4) return f(std::integral_constant<int, LDE_SOLVER_RK4>{});
+  return LDE_ERR_UNSUPPORTED;
+}
+
 static KOpts make_opts(const lde_problem_desc& d, const double* ts, int T, int B) {
   KOpts o;
   o.abstol = (float)d.abstol;

@@ -42,11 +42,13 @@
 #include <cmath>
 #include <cstdint>
 #include <initializer_list>
+#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
 
 #include "lde_device.h"
+#include "lde_host.h"
 #include "lde_mfma.h"
 
 namespace lde {
@@ -1372,17 +1374,14 @@ __global__ void __launch_bounds__(NT) k_mlp_adjoint(MlpDims dm, KOpts o, BwdArgs
 // ================================================ host side =================================================
 struct MlpPlan {
   MlpDims dm;
+  lde_host::MlpShape sh;       // what the kernel-family choice reads (lde_host::mlp_forward_mapping / mlp_adjoint_mapping)
   VecDims vd;                  // small-batch kernels (lde_mlpv.h): geometry and the swizzled weight copies
-  bool vec_ok = false;
   float* vecw = nullptr;
   WDims wd;                    // W-waves-per-trajectory register kernels (lde_mlpw.h)
-  bool w_ok = false;
   float* wpack = nullptr;
   BDims bd;                    // block-layout register kernels (lde_mlpb.h)
-  bool b_ok = false;
   float* bpack = nullptr;
   CDims cd;                    // two trajectories per workgroup, networks up to 128 wide (lde_mlpc.h)
-  bool c_ok = false;
   float* cpack = nullptr;
   unsigned epoch = 0;          // launch counter of k_mlpw's tagged grid-sum words
   float* wslots = nullptr;     // k_mlpw's own [2][nWG][4] words ({value, tag} pairs): never shared with the float partials of grid_sum4
@@ -1416,8 +1415,7 @@ struct MlpPlan {
   float* rows = nullptr;       // [waves][rows_stride]
   size_t rows_cap = 0;
   int rows_stride = 0;
-  // LDE_BATCH_COUPLED_GLOBAL: the cross-rank exchange of the step-control sums (lde_set_global_sum_hook)
-  bool global_mode = false;
+  // LDE_BATCH_COUPLED_GLOBAL (sh.global): the cross-rank exchange of the step-control sums (lde_set_global_sum_hook)
   lde_sum_hook sum_hook = nullptr;
   void* sum_user = nullptr;
   int64_t global_batch = 0;
@@ -1431,19 +1429,11 @@ struct MlpPlan {
   // lde_set_phase_timing: HIP events around the adjoint's solve kernel and its weight-gradient tail (bench.py's per-kernel roofline)
   bool phase_on = false;
   hipEvent_t ph_ev[3] = {nullptr, nullptr, nullptr};
-  bool disc = false;           // LDE_SENSE_DISCRETE: lde_adjoint sweeps the forward solve's step record (lde_mlpd.h)
   MlpTune tune;                // kernel-family switches and thresholds (lde_set_option)
-  int last_family = -1;        // the kernel family of the last lde_adjoint: 0 tiles (gW in the tail: k_mlp_dw), 1 k_mlp64, 2 k_mlpb, 3 k_mlpc (gW folded
-                               // in the solve kernel), 4 k_mlpw, 5 k_mlpv, 6 k_mlp4 (staged, tail)
+  int last_family = -1;        // the kernel family of the last lde_adjoint (lde_host::MlpFamily; −1: none yet)
 };
 
 void mlp_plan_destroy(MlpPlan* p);
-static bool mlp64_applicable(const MlpPlan* p, int B);
-static int mlp64_adj_waves(int B);
-static bool b_applicable(const MlpPlan* p, int B, int T, bool adj, bool coupled_adaptive);
-static bool c_applicable(const MlpPlan* p, int B, int T, bool adj, bool coupled_adaptive);
-enum { DISC_TILES = 0, DISC_64 = 1, DISC_B = 2, DISC_C = 3 };
-static int disc_family(const MlpPlan* p, int B, int T);
 
 int mlp_plan_create(const lde_problem_desc& d, MlpPlan** out, std::string& err) {
   MlpPlan* p = new MlpPlan();
@@ -1457,9 +1447,9 @@ int mlp_plan_create(const lde_problem_desc& d, MlpPlan** out, std::string& err) 
   dm.P = d.param_dim;
   dm.has_pend = d.rhs_kind == LDE_RHS_PENDULUM_PLUS_MLP;
   dm.coupled = d.batching == LDE_BATCH_COUPLED || d.batching == LDE_BATCH_COUPLED_GLOBAL;
-  p->global_mode = d.batching == LDE_BATCH_COUPLED_GLOBAL;
-  p->disc = d.sensealg == LDE_SENSE_DISCRETE;
   dm.solver = d.solver;
+  p->sh = lde_host::mlp_shape(d);   // which families the network fits, and what their choice reads
+  const lde_host::MlpShape& sh = p->sh;
   int hmax = 16;
   for (int l = 0; l + 1 < dm.nL; l++) hmax = std::max(hmax, dm.sizes[l + 1]);
   fill_layer_offsets(dm, &p->nfrag, &p->nfragT);
@@ -1485,28 +1475,13 @@ int mlp_plan_create(const lde_problem_desc& d, MlpPlan** out, std::string& err) 
   }
   {   // one-trajectory-per-workgroup kernels: every width ≤ 256
     VecDims& vd = p->vd;
-    int maxw = dm.Dp;
-    for (int l = 0; l <= dm.nL; l++) maxw = std::max(maxw, dm.sizes[l]);
-    p->vec_ok = maxw <= 256;
-    if (p->vec_ok) {
-      int nt = 64;
-      while (nt < maxw) nt *= 2;
+    const int maxw = sh.maxw;
+    if (sh.vec_ok) {
       // Register-resident hidden layer (lde_mlpv.h: vec_matvec_reg): three Dense layers with a hidden×hidden product of at
-      // most 128×128 — the workgroup takes S·r lanes so that a lane's share of a row is VREG_K groups
-      vd.reg_l = -1;
-      int reg_r = 0, reg_s = 0;
-      {
-        const int hm = dm.nL == 3 ? std::max(dm.sizes[1], dm.sizes[2]) : 0;
-        if (dm.nL == 3 && hm <= 128 && hm > 16) {
-          reg_r = hm <= 64 ? 64 : 128;
-          reg_s = reg_r / 64;                 // 64 → one wave holds the rows whole; 128 → two lane groups split K
-          const int want = reg_r * reg_s;     // 64 or 256 lanes
-          if (nt <= want) {
-            nt = want;
-            vd.reg_l = 1;
-          }
-        }
-      }
+      // most 128×128 — the workgroup takes S·r lanes (lde_host::mlp_shape) so that a lane's share of a row is VREG_K groups
+      const int nt = sh.v_nt;
+      vd.reg_l = sh.v_reg ? 1 : -1;
+      const int reg_r = sh.hm <= 64 ? 64 : 128, reg_s = reg_r / 64;   // 64 → one wave holds the rows whole; 128 → two lane groups split K
       vd.NT = nt;
       auto geom = [&](int rows, int K, int* rp, int* lg, int* k4, int* S) {
         int r = 4, g = 2;
@@ -1557,13 +1532,12 @@ int mlp_plan_create(const lde_problem_desc& d, MlpPlan** out, std::string& err) 
     }
   }
   {   // W waves per trajectory, weights in registers (lde_mlpw.h): three layers, no analytic part, H ≤ 200, D′ ≤ 32
-    const int hm = dm.nL == 3 ? std::max(dm.sizes[1], dm.sizes[2]) : 0;
-    p->w_ok = dm.nL == 3 && !dm.has_pend && dm.P == 0 && dm.Dp <= 32 && hm >= 1 && hm <= 200;
-    if (p->w_ok) {
+    const int hm = sh.hm;
+    if (sh.w_ok) {
       WDims& wd = p->wd;
       wd.DP = dm.Dp <= 8 ? 8 : 32;
       wd.HP = hm <= 128 ? 128 : 200;
-      wd.W = hm <= 128 ? 2 : 4;
+      wd.W = sh.w_waves;
       wd.UT = 64 * wd.W;
       wd.SEG = 64 / wd.DP;
       wd.GS = (wd.HP / wd.SEG + 3) / 4;   // = the kernel's compile-time GS
@@ -1586,9 +1560,7 @@ int mlp_plan_create(const lde_problem_desc& d, MlpPlan** out, std::string& err) 
     }
   }
   {   // four waves per trajectory, W₂ as 2-D register blocks, the weight gradient on the CU (lde_mlpb.h): three layers, H ≤ 200, D′ ≤ 16
-    const int hm = dm.nL == 3 ? std::max(dm.sizes[1], dm.sizes[2]) : 0;
-    p->b_ok = dm.nL == 3 && !dm.has_pend && dm.P == 0 && dm.Dp <= 16 && hm >= 1 && hm <= 200;
-    if (p->b_ok) {
+    if (sh.b_ok) {
       BDims& bd = p->bd;
       bd.DP = dm.Dp <= 8 ? 8 : 16;
       bd.SEG = 64 / bd.DP;
@@ -1608,9 +1580,7 @@ int mlp_plan_create(const lde_problem_desc& d, MlpPlan** out, std::string& err) 
     }
   }
   {   // two trajectories per workgroup on one register copy of the weights (lde_mlpc.h): three layers, H ≤ 128, D′ ≤ 32, coupled control
-    const int hm = dm.nL == 3 ? std::max(dm.sizes[1], dm.sizes[2]) : 0;
-    p->c_ok = dm.nL == 3 && !dm.has_pend && dm.P == 0 && dm.Dp <= 32 && hm >= 1 && hm <= 128 && dm.coupled;
-    if (p->c_ok) {
+    if (sh.c_ok) {
       CDims& cd = p->cd;
       cd.o_wb = 0;
       cd.o_w3b = cd.o_wb + mlpc::RB * mlpc::CB * mlpc::UT;
@@ -1685,85 +1655,12 @@ int mlp_reserve(MlpPlan* p, int B, int T, std::string& err) {
   return LDE_OK;
 }
 
-// Workspace of the adjoint for batches up to B with T save points. `steps_hint` > 0: step attempts known in advance
-// (fixed step size). Staging slots per workgroup: stages × (3 step attempts per save interval + 32) — doubled whenever
-// the previous call reported an overflow — bounded by a memory budget
-// (24 GiB of the 288); a workgroup that needs more folds its slots into its private slab
-// (slow but correct). option "mlp_stage_slots" forces the slot count (tests).
-int mlp_reserve_adjoint(MlpPlan* p, int B, int T, int64_t steps_hint, std::string& err) {
-  const MlpDims& dm = p->dm;
-  if (mlp64_applicable(p, B)) {   // no staging area: a slab row per wave is the kernel's only workspace (continuous and discrete adjoint alike)
-    p->rows_stride = (dm.nW + 63) & ~63;
-    if (!grow(&p->rows, &p->rows_cap, (size_t)mlp64_adj_waves(B) * p->rows_stride)) {
-      err = "MLP plan: hipMalloc of the weight-gradient rows failed";
-      return LDE_ERR_ALLOC;
-    }
-    return LDE_OK;
-  }
-  const int dfam = p->disc ? disc_family(p, B, T) : -1;
-  if (p->disc ? (dfam == DISC_B || dfam == DISC_C)
-              : (b_applicable(p, B, T, true, dm.coupled != 0) || c_applicable(p, B, T, true, dm.coupled != 0))) {   // no staging area either: one slab row per workgroup
-    p->rows_stride = (dm.nW + 63) & ~63;
-    if (!grow(&p->rows, &p->rows_cap, (size_t)B * p->rows_stride)) {
-      err = "MLP plan: hipMalloc of the weight-gradient rows failed";
-      return LDE_ERR_ALLOC;
-    }
-    return LDE_OK;
-  }
-  const int nwg = cdiv(B, NB);
-  const int nst = dm.solver == LDE_SOLVER_RK4 ? 4 : 6;
-  constexpr long budget_mb = 24576L;
-  const int slots_force = p->tune.stage_slots;
-  if (p->fb_pending) {
-    if (hipEventQuery(p->fb_ev) == hipSuccess) {
-      p->fb_pending = false;
-      if (p->fb_host[0] > 0 && p->cap_scale < 64) p->cap_scale *= 2;
-    } else
-      (void)hipGetLastError();   // hipErrorNotReady is not an error of the caller's
-  }
-  int64_t want = (int64_t)nst * (steps_hint > 0 ? steps_hint + 2 : p->cap_scale * (3 * (int64_t)(T > 1 ? T - 1 : 1) + 32));
-  const int64_t fit = ((int64_t)budget_mb << 20) / ((int64_t)(nwg + 1) * dm.blk_floats * (int64_t)sizeof(float));
-  if (want > fit) want = fit;
-  if (slots_force > 0) want = slots_force;
-  if (want < nst) want = nst;
-  if (want > (1 << 24)) want = 1 << 24;
-  int ks = cdiv(768, nwg * dw_jobs(dm, dw_pick_ndw(dm)));
-  ks = ks < 1 ? 1 : (ks > 16 ? 16 : ks);
-  size_t nsl = (size_t)p->nslots_cap;
-  // the staging area is the large allocation: if the device cannot give it (another allocator holds the memory, a smaller
-  // device), halve the slot count down to one step's worth — a workgroup that runs out of slots folds them into its private
-  // slab inside the solve kernel (exact), so fewer slots cost time, never correctness
-  int cap = (int)want;
-  const size_t stage_before = p->stage_cap;
-  for (;;) {
-    if (grow(&p->stage, &p->stage_cap, (size_t)(nwg + 1) * cap * dm.blk_floats)) break;
-    (void)hipGetLastError();
-    if (cap <= nst || slots_force > 0 || steps_hint > 0) { cap = 0; break; }
-    cap = cap / 2 < nst ? nst : cap / 2;
-  }
-  if (cap == 0 || !grow(&p->wts, &p->wts_cap, (size_t)(nwg + 1) * cap * NB) ||
-      !grow(&p->slab, &p->slab_cap, ((size_t)(nwg + 1) * (1 + ks) + 1) * dm.slab_n) || !grow(&p->nslots, &nsl, (size_t)2 * (nwg + 1))) {
-    err = "MLP plan: hipMalloc of the adjoint workspace failed";
-    return LDE_ERR_ALLOC;
-  }
-  // a fresh staging area holds arbitrary bits; the one-trajectory-per-workgroup kernel fills a tile's slots column by column,
-  // and a column that never reaches a slot carries weight 0 there — its a-panel must still be finite (0·NaN) for k_mlp_dw
-  if (p->stage_cap != stage_before && hipMemset(p->stage, 0, p->stage_cap * sizeof(float)) != hipSuccess) {
-    err = "MLP plan: hipMemset(stage) failed";
-    return LDE_ERR_HIP;
-  }
-  p->nslots_cap = (int)nsl;
-  p->adj_cap = cap;
-  p->adj_ks = ks;
-  return LDE_OK;
-}
-
 int mlp_set_weights(MlpPlan* p, const float* W_dev, hipStream_t stream, std::string& err) {
   hipLaunchKernelGGL(k_build_frags, dim3(64, p->dm.nL), dim3(256), 0, stream, W_dev, p->dm, p->frag, p->fragT, (float*)nullptr, (__bf16*)nullptr, (__bf16*)nullptr);
-  if (p->vec_ok) hipLaunchKernelGGL(k_build_vec, dim3(64, p->dm.nL), dim3(256), 0, stream, W_dev, p->dm, p->vd, p->vecw);
-  if (p->w_ok) hipLaunchKernelGGL(k_build_wpack, dim3(128), dim3(256), 0, stream, W_dev, p->dm, p->wd, p->wpack);
-  if (p->b_ok) hipLaunchKernelGGL(k_build_bpack, dim3(128), dim3(256), 0, stream, W_dev, p->dm, p->bd, p->bpack);
-  if (p->c_ok) hipLaunchKernelGGL(k_build_cpack, dim3(128), dim3(256), 0, stream, W_dev, p->dm, p->cd, p->cpack);
+  if (p->sh.vec_ok) hipLaunchKernelGGL(k_build_vec, dim3(64, p->dm.nL), dim3(256), 0, stream, W_dev, p->dm, p->vd, p->vecw);
+  if (p->sh.w_ok) hipLaunchKernelGGL(k_build_wpack, dim3(128), dim3(256), 0, stream, W_dev, p->dm, p->wd, p->wpack);
+  if (p->sh.b_ok) hipLaunchKernelGGL(k_build_bpack, dim3(128), dim3(256), 0, stream, W_dev, p->dm, p->bd, p->bpack);
+  if (p->sh.c_ok) hipLaunchKernelGGL(k_build_cpack, dim3(128), dim3(256), 0, stream, W_dev, p->dm, p->cd, p->cpack);
   if (hipGetLastError() != hipSuccess) {
     err = "k_build_frags launch failed";
     return LDE_ERR_HIP;
@@ -1819,10 +1716,9 @@ static size_t with_cache(size_t fixed, size_t want_floats) {
 template <class... A>
 static int launch_maybe_coop(bool coop, const void* fn, dim3 grid, dim3 block, size_t lds, hipStream_t stream, std::string& err,
                              const char* what, A&... args) {
-  constexpr bool coop_on = true;
   void* argv[] = {(void*)&args...};
   hipError_t rc;
-  if (coop && coop_on) {
+  if (coop) {
     rc = hipLaunchCooperativeKernel(fn, grid, block, argv, (unsigned)lds, stream);
     if (rc == hipErrorCooperativeLaunchTooLarge) {
       (void)hipGetLastError();
@@ -1839,62 +1735,61 @@ static int launch_maybe_coop(bool coop, const void* fn, dim3 grid, dim3 block, s
   return LDE_OK;
 }
 
+// Dynamic LDS beyond the 64 KB a launch gets without asking needs the attribute, once per instantiation (= function pointer): the whole
+// LDS, or what the kernel's static LDS leaves of it. Two handles may launch from two host threads at once: the list is locked.
+enum LdsLimit { LDS_WHOLE, LDS_MINUS_STATIC };
+static int raise_lds_limit(const void* fn, LdsLimit limit, const char* what, std::string& err) {
+  static std::mutex mu;
+  static std::vector<const void*> done;
+  std::lock_guard<std::mutex> lock(mu);
+  if (std::find(done.begin(), done.end(), fn) != done.end()) return LDE_OK;
+  hipFuncAttributes fa{};
+  (void)hipFuncGetAttributes(&fa, fn);
+  const int bytes = (int)LDS_MAX - (limit == LDS_MINUS_STATIC ? (int)fa.sharedSizeBytes : 0);
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    err = std::string("hipFuncSetAttribute(") + what + ") failed: " + hipGetErrorString(e) + " static=" + std::to_string(fa.sharedSizeBytes) +
+          " regs=" + std::to_string(fa.numRegs);
+    return LDE_ERR_HIP;
+  }
+  done.push_back(fn);
+  return LDE_OK;
+}
+
+// Which family serves a call is decided in csrc/lde_host.h (mlp_forward_mapping, mlp_adjoint_mapping: pure host logic with every threshold,
+// checked on the CPU by tests/host_logic_driver.cpp); lde_host::mlp_dispatch turns the solver into the kernels' template argument. Below:
+// per family, the LDS bytes of its carve-up (what the mappings compare: mlp_lds_numbers) and its launch.
+
 // ---- one wave per trajectory, everything in registers (lde_mlp64.h): small networks on small states, per-trajectory control
-static bool mlp64_applicable(const MlpPlan* p, int B) {
-  const MlpDims& dm = p->dm;
-  if (!p->tune.mlp64) return false;
-  const int maxb = 65536;   // measured (c3 shape): 0.28 + 3.9 ms vs 0.61 + 5.8 for the tile kernels at B = 4096, 0.77 + 10.4 vs 2.2 + 12.0 at 16384
-  return dm.nL == 3 && dm.sizes[1] <= 64 && dm.sizes[2] <= 64 && dm.Dp <= 4 && dm.P <= 1 && !dm.coupled && B <= maxb;
-}
-// waves of the adjoint launch: one per SIMD (the kernel takes more than 256 registers); a wave walks trajectories b, b + waves, …
-// with ONE set of gradient sums, so the slab the final sum reads has `waves` rows whatever the batch
-// workgroups of the adjoint launch: four waves each (one per SIMD of a CU — the kernel takes more than 256 registers), ≤ 256 of them; a
-// wave walks trajectories b, b + 4·workgroups, … with ONE set of gradient sums, the four waves' sums meet in LDS, and the slab the final
-// sum reads has one row per workgroup whatever the batch
-constexpr int MLP64_NWV = 4;
-static int mlp64_adj_waves(int B) {   // = workgroups = slab rows
-  constexpr int maxw = 256;
-  const int need = (B + MLP64_NWV - 1) / MLP64_NWV;
-  return need < maxw ? need : maxw;
-}
-template <bool ADJ, bool DISC = false>
+using lde_host::MLP64_NWV;
+using lde_host::mlp64_adj_waves;
+template <int SOLVER, bool ADJ, bool DISC = false>
 static int launch_mlp64(const MlpDims& dm, const KOpts& o, const VArgs& a, hipStream_t stream, std::string& err) {
-  const bool rk4 = dm.solver == LDE_SOLVER_RK4, d2 = dm.Dp <= 2;
+  const bool d2 = dm.Dp <= 2;
+  MlpDims dmv = dm;
+  KOpts ov = o;
+  VArgs av = a;
+  void* argv[] = {(void*)&dmv, (void*)&ov, (void*)&av};
+  hipError_t rc;
   if (ADJ) {
-    const dim3 grid(mlp64_adj_waves(o.B));
+    const void* fn = DISC ? (d2 ? (const void*)k_mlp64_disc<SOLVER, 2> : (const void*)k_mlp64_disc<SOLVER, 4>)
+                          : (d2 ? (const void*)k_mlp64_adj<SOLVER, 2> : (const void*)k_mlp64_adj<SOLVER, 4>);
+    const int rca = raise_lds_limit(fn, LDS_MINUS_STATIC, "k_mlp64_adj", err);
+    if (rca) return rca;
     const size_t lds = (size_t)MLP64_NWV * a.cap * sizeof(float);   // the four waves' rows (c3: 4 × 17.9 KB)
-    const void* fn = DISC ? (rk4 ? (d2 ? (const void*)k_mlp64_disc<LDE_SOLVER_RK4, 2> : (const void*)k_mlp64_disc<LDE_SOLVER_RK4, 4>)
-                                 : (d2 ? (const void*)k_mlp64_disc<LDE_SOLVER_TSIT5, 2> : (const void*)k_mlp64_disc<LDE_SOLVER_TSIT5, 4>))
-                          : (rk4 ? (d2 ? (const void*)k_mlp64_adj<LDE_SOLVER_RK4, 2> : (const void*)k_mlp64_adj<LDE_SOLVER_RK4, 4>)
-                                 : (d2 ? (const void*)k_mlp64_adj<LDE_SOLVER_TSIT5, 2> : (const void*)k_mlp64_adj<LDE_SOLVER_TSIT5, 4>));
-    static bool attr_set[2][2] = {{false, false}, {false, false}};
-    if (!attr_set[rk4][d2]) {
-      hipFuncAttributes fa{};
-      (void)hipFuncGetAttributes(&fa, fn);
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX - (int)fa.sharedSizeBytes) != hipSuccess) {
-        (void)hipGetLastError();
-        err = "hipFuncSetAttribute(k_mlp64_adj) failed";
-        return LDE_ERR_HIP;
-      }
-      attr_set[rk4][d2] = true;
-    }
-    MlpDims dmv = dm;
-    KOpts ov = o;
-    VArgs av = a;
-    void* argv[] = {(void*)&dmv, (void*)&ov, (void*)&av};
-    (void)hipLaunchKernel(fn, grid, dim3(64 * MLP64_NWV), argv, lds, stream);
-  } else if (rk4 && d2) hipLaunchKernelGGL((k_mlp64<LDE_SOLVER_RK4, 2>), dim3(o.B), dim3(64), 0, stream, dm, o, a);
-  else if (rk4) hipLaunchKernelGGL((k_mlp64<LDE_SOLVER_RK4, 4>), dim3(o.B), dim3(64), 0, stream, dm, o, a);
-  else if (d2) hipLaunchKernelGGL((k_mlp64<LDE_SOLVER_TSIT5, 2>), dim3(o.B), dim3(64), 0, stream, dm, o, a);
-  else hipLaunchKernelGGL((k_mlp64<LDE_SOLVER_TSIT5, 4>), dim3(o.B), dim3(64), 0, stream, dm, o, a);
-  if (hipGetLastError() != hipSuccess) {
+    rc = hipLaunchKernel(fn, dim3(mlp64_adj_waves(o.B)), dim3(64 * MLP64_NWV), argv, lds, stream);
+  } else
+    rc = hipLaunchKernel(d2 ? (const void*)k_mlp64<SOLVER, 2> : (const void*)k_mlp64<SOLVER, 4>, dim3(o.B), dim3(64), argv, 0, stream);
+  if (rc != hipSuccess) {
+    (void)hipGetLastError();
     err = "k_mlp64 launch failed";
     return LDE_ERR_HIP;
   }
   return LDE_OK;
 }
 
-// ---- the one-trajectory-per-workgroup kernels (lde_mlpv.h): applicability, LDS budget, launch -------------------------------------
+// ---- the one-trajectory-per-workgroup kernels (lde_mlpv.h)
 static size_t vec_lds_fixed(const MlpDims& dm, const VecDims& vd, int T, bool adj) {
   const int nsp = adj ? vd.nsp_b : vd.nsp_f;
   size_t b = (sizeof(VCtl) + 15) & ~size_t(15);
@@ -1902,48 +1797,20 @@ static size_t vec_lds_fixed(const MlpDims& dm, const VecDims& vd, int T, bool ad
   b += (size_t)(11 * nsp + vd.htotal + MAXL * vd.maxw4 + vd.NT + ((dm.nbias + 3) & ~3) + 2 * MAXL * (sizeof(VLayer) / 4)) * sizeof(float);
   return (b + 15) & ~size_t(15);
 }
-// Which batches run there: see the measurement below. Option "mlpv" = 0 switches the kernels off.
-static bool vec_applicable(const MlpPlan* p, int B, int T, bool adj, bool coupled_adaptive, size_t* lds, std::string& why) {
-  if (!p->vec_ok || !p->tune.mlpv) return false;
-  // measured (MI355X, c2 / c3 / c4 shapes, abl/ + profiles/): the one-trajectory workgroups win while the chip has a SIMD per
-  // wave (B·NT/64 ≤ 1024: c2 0.88 + 1.97 ms vs 1.77 + 3.44 at B = 256, c3 0.36 + 4.28 vs 0.63 + 5.0 at 1024, c4 0.46 + 3.77 vs
-  // 0.45 + 4.3 at 512) and lose beyond (c2 at B = 1024: 1.94 + 4.5 vs 1.78 + 3.9) — the tiles then have enough columns
-  const int maxb = (p->vd.reg_l >= 0 ? 2048 : 1024) * 64 / p->vd.NT;   // register-resident layer: two waves per SIMD still win
-  if (B > maxb) return false;
-  const size_t fixed = vec_lds_fixed(p->dm, p->vd, T, adj);
-  if (fixed > LDS_MAX / 2) return false;
-  // LDS per workgroup: everything when a CU gets one workgroup, a share otherwise (coupled adaptive control needs all B resident)
-  const int per_cu = cdiv(B, 256);
-  size_t budget = LDS_MAX / (size_t)per_cu;
-  if (per_cu > 1) budget -= 256;
-  if (budget < fixed) {
-    if (coupled_adaptive) return false;
-    budget = fixed;
-  }
-  const size_t want = fixed + (size_t)p->vd.total4 * 16;
-  *lds = (std::min(want, budget)) & ~size_t(15);
-  (void)why;
-  return true;
-}
-
 template <int SOLVER, bool ADJ>
-static int launch_vec(const MlpPlan* p, const KOpts& o, VArgs& a, size_t lds, bool coop, hipStream_t stream, std::string& err) {
+static int launch_vec(const MlpPlan* p, const KOpts& o, VArgs& a, bool coop, hipStream_t stream, std::string& err) {
   MlpDims dmv = p->dm;
   VecDims vdv = p->vd;
   KOpts ov = o;
   constexpr int KB = ADJ ? VREG_K : 0;
-  const bool reg = p->vd.reg_l >= 0;
-  const void* fn = reg ? (p->vd.NT == 64 ? (const void*)k_mlpv<SOLVER, 64, ADJ, VREG_K, KB> : (const void*)k_mlpv<SOLVER, 256, ADJ, VREG_K, KB>)
-                       : (p->vd.NT == 64 ? (const void*)k_mlpv<SOLVER, 64, ADJ> : p->vd.NT == 128 ? (const void*)k_mlpv<SOLVER, 128, ADJ> : (const void*)k_mlpv<SOLVER, 256, ADJ>);
-  static bool attr_set[5] = {false, false, false, false, false};
-  const int ki = reg ? (p->vd.NT == 64 ? 3 : 4) : (p->vd.NT == 64 ? 0 : (p->vd.NT == 128 ? 1 : 2));
-  if (!attr_set[ki]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) {
-      err = "hipFuncSetAttribute(k_mlpv) failed";
-      return LDE_ERR_HIP;
-    }
-    attr_set[ki] = true;
-  }
+  const void* fn = p->vd.reg_l >= 0 ? (p->vd.NT == 64 ? (const void*)k_mlpv<SOLVER, 64, ADJ, VREG_K, KB> : (const void*)k_mlpv<SOLVER, 256, ADJ, VREG_K, KB>)
+                                    : (p->vd.NT == 64 ? (const void*)k_mlpv<SOLVER, 64, ADJ> : p->vd.NT == 128 ? (const void*)k_mlpv<SOLVER, 128, ADJ> : (const void*)k_mlpv<SOLVER, 256, ADJ>);
+  const int rca = raise_lds_limit(fn, LDS_WHOLE, "k_mlpv", err);
+  if (rca) return rca;
+  // the fixed part, then as much of the swizzled weights as the workgroup's share of its CU holds (a solve that need not be resident
+  // takes its fixed part even beyond that share)
+  const size_t fixed = vec_lds_fixed(p->dm, p->vd, o.T, ADJ);
+  const size_t lds = std::min(fixed + (size_t)p->vd.total4 * 16, std::max(lde_host::mlpv_lds_budget(LDS_MAX, o.B), fixed)) & ~size_t(15);
   a.lds_bytes = (int)lds;
 #if LDE_PROF
   prof_reset();
@@ -1955,18 +1822,7 @@ static int launch_vec(const MlpPlan* p, const KOpts& o, VArgs& a, size_t lds, bo
   return rcl;
 }
 
-// ---- W waves per trajectory, weights and state in registers (lde_mlpw.h)
-static size_t w_lds_base(const WDims& wd, int T, bool adj) {   // save times, state copies, exchange buffers, narrow slices
-  return (((size_t)T * 8 + 15) & ~size_t(15)) + (size_t)(wd.W * 64 + 2 * wd.HX) * 4 + (size_t)wd.GS * 64 * 16 * (adj ? 2 : 1) + 16;
-}
-static bool w_applicable(const MlpPlan* p, int B, int T, bool adj, bool coupled_adaptive) {
-  if (!p->w_ok || !p->tune.mlpw) return false;
-  if (w_lds_base(p->wd, T, adj) > LDS_MAX * p->wd.W / 4) return false;   // 4/W workgroups share a CU's LDS (one wave per SIMD)
-  // one wave per SIMD (the weights take most of the 512 registers): 1024 waves are resident at once; an uncoupled solve may
-  // queue a second round, a coupled one needs every trajectory resident
-  const int maxw = coupled_adaptive ? 1024 : 2048;
-  return (long long)B * p->wd.W <= maxw;
-}
+// ---- the register families (lde_mlpw.h, lde_mlpb.h, lde_mlpc.h)
 // tagged grid-sum words of w_grid_sum: an own buffer (zeroed: no tag is 0), a fresh epoch per launch, cleared when the epoch wraps
 static int grid_words_prepare(MlpPlan* p, int B, VArgs& a, hipStream_t stream, std::string& err) {
   const size_t bytes = (size_t)2 * (B + 1) * 4 * sizeof(float);
@@ -1994,184 +1850,165 @@ static int grid_words_prepare(MlpPlan* p, int B, VArgs& a, hipStream_t stream, s
   a.gs.slots = p->wslots;
   return LDE_OK;
 }
+// their common launch: the LDS limit, the grid-sum words of a solve that sums over the grid, the (cooperative) launch
+template <class Dims>
+static int launch_reg(MlpPlan* p, const void* fn, const char* what, bool adj, const Dims& dims, const KOpts& o, VArgs& a, int nwg, int nt,
+                      size_t lds, bool coop, hipStream_t stream, std::string& err) {
+  const int rca = raise_lds_limit(fn, LDS_MINUS_STATIC, what, err);
+  if (rca) return rca;
+  const bool relay = a.gs.cross();   // LDE_BATCH_COUPLED_GLOBAL: sums leave the device; a plain launch (two ranks' cooperative launches on
+                                     // one device could be serialised by the runtime — each would wait for the other's sums)
+  if (coop || relay) {
+    const int rcw = grid_words_prepare(p, o.B, a, stream, err);
+    if (rcw) return rcw;
+  }
+#if LDE_PROF
+  prof_reset();
+#endif
+  MlpDims dmv = p->dm;
+  Dims dv = dims;
+  KOpts ov = o;
+  const int rcl = launch_maybe_coop(coop && !relay, fn, dim3(nwg), dim3(nt), lds, stream, err, what, dmv, dv, ov, a);
+#if LDE_PROF
+  prof_dump((std::string(what) + (adj ? " adjoint" : " forward")).c_str(), stream);
+#endif
+  (void)adj;
+  return rcl;
+}
+
+// W waves per trajectory, weights and state in registers (lde_mlpw.h)
+static size_t w_lds_base(const WDims& wd, int T, bool adj) {   // save times, state copies, exchange buffers, narrow slices
+  return (((size_t)T * 8 + 15) & ~size_t(15)) + (size_t)(wd.W * 64 + 2 * wd.HX) * 4 + (size_t)wd.GS * 64 * 16 * (adj ? 2 : 1) + 16;
+}
 template <int SOLVER, bool ADJ>
 static int launch_w(MlpPlan* p, const KOpts& o, VArgs& a, bool coop, hipStream_t stream, std::string& err) {
-  MlpDims dmv = p->dm;
-  WDims wdv = p->wd;
-  KOpts ov = o;
-  const bool d8 = wdv.DP == 8, w2 = wdv.W == 2;
-  const void* fn = w2 ? (d8 ? (const void*)k_mlpw<SOLVER, 8, 128, 2, ADJ> : (const void*)k_mlpw<SOLVER, 32, 128, 2, ADJ>)
-                      : (d8 ? (const void*)k_mlpw<SOLVER, 8, 200, 4, ADJ> : (const void*)k_mlpw<SOLVER, 32, 200, 4, ADJ>);
-  size_t lds = w_lds_base(wdv, o.T, ADJ);
-  const size_t cot = ADJ ? (size_t)o.T * dmv.Dp * 4 * (o.checkpoint ? 2 : 1) : 0;
-  a.cot_lds = ADJ && cot <= 40 * 1024 && lds + cot <= LDS_MAX * wdv.W / 4;   // the trajectory's dẑ (and saved ẑ) by save time: no global load inside the solve
+  const WDims& wd = p->wd;
+  const bool d8 = wd.DP == 8;
+  const void* fn = wd.W == 2 ? (d8 ? (const void*)k_mlpw<SOLVER, 8, 128, 2, ADJ> : (const void*)k_mlpw<SOLVER, 32, 128, 2, ADJ>)
+                             : (d8 ? (const void*)k_mlpw<SOLVER, 8, 200, 4, ADJ> : (const void*)k_mlpw<SOLVER, 32, 200, 4, ADJ>);
+  size_t lds = w_lds_base(wd, o.T, ADJ);
+  const size_t cot = ADJ ? (size_t)o.T * p->dm.Dp * 4 * (o.checkpoint ? 2 : 1) : 0;
+  a.cot_lds = ADJ && cot <= 40 * 1024 && lds + cot <= LDS_MAX * wd.W / 4;   // the trajectory's dẑ (and saved ẑ) by save time: no global load inside the solve
   if (a.cot_lds) lds += cot;
   if (lds > LDS_MAX) {
     err = "k_mlpw: the save-time grid does not fit LDS";
     return LDE_ERR_UNSUPPORTED;
   }
-  {   // dynamic LDS beyond the default limit needs the attribute, once per instantiation
-    static bool attr_set[2][2] = {{false, false}, {false, false}};
-    if (!attr_set[d8][w2]) {
-      hipFuncAttributes fa{};
-      (void)hipFuncGetAttributes(&fa, fn);
-      const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX - (int)fa.sharedSizeBytes);
-      if (ea != hipSuccess) {
-        (void)hipGetLastError();
-        err = std::string("hipFuncSetAttribute(k_mlpw) failed: ") + hipGetErrorString(ea) + " d8=" + std::to_string(d8) + " w2=" + std::to_string(w2) +
-              " adj=" + std::to_string(ADJ) + " static=" + std::to_string(fa.sharedSizeBytes) + " regs=" + std::to_string(fa.numRegs);
-        return LDE_ERR_HIP;
-      }
-      attr_set[d8][w2] = true;
-    }
-  }
   a.wpack = p->wpack;
-  const bool relay = a.gs.cross();   // LDE_BATCH_COUPLED_GLOBAL: sums leave the device; a plain launch (two ranks' cooperative
-                                                 // launches on one device could be serialised by the runtime — each would wait for the other's sums)
-  if (coop || relay) {
-    const int rcw = grid_words_prepare(p, o.B, a, stream, err);
-    if (rcw) return rcw;
-  }
-#if LDE_PROF
-  prof_reset();
-#endif
-  const int rcl = launch_maybe_coop(coop && !relay, fn, dim3(o.B), dim3(wdv.UT), lds, stream, err, "k_mlpw", dmv, wdv, ov, a);
-#if LDE_PROF
-  prof_dump(ADJ ? "w adjoint" : "w forward", stream);
-#endif
-  return rcl;
+  const int rc = launch_reg(p, fn, "k_mlpw", ADJ, wd, o, a, o.B, wd.UT, lds, coop, stream, err);
+  if (rc == LDE_ERR_HIP) err += " (k_mlpw: DP=" + std::to_string(wd.DP) + " W=" + std::to_string(wd.W) + " adj=" + std::to_string(ADJ) + ")";
+  return rc;
 }
 
-// ---- four waves per trajectory, W₂ as register blocks, the weight gradient folded on the CU (lde_mlpb.h)
+// four waves per trajectory, W₂ as register blocks, the weight gradient folded on the CU (lde_mlpb.h)
 static size_t b_lds_base(const BDims& bd, int T, bool adj, int nst) {   // save times, ring (+ partial sums), narrow slices
   const int nsl = adj ? nst + 1 : 1;
   return (((size_t)T * 8 + 15) & ~size_t(15)) + (size_t)(nsl * mlpb::SLOT + (adj ? 16 * mlpb::HV : 0)) * 4 +
          (size_t)bd.GS * 64 * 16 * (adj ? 2 : 1) + (size_t)mlpb::HV * (2 * bd.DP + 4) * 4 + 16 + ((adj && bd.DP == 16) ? 2 * mlpb::W * 16 * 4 : 0);
 }
-static bool b_applicable(const MlpPlan* p, int B, int T, bool adj, bool coupled_adaptive) {
-  // option "mlpb": 0 = off (k_mlpw: the parity reference of this kernel), 2 = also the networks of at most 128 units that k_mlpw's
-  // two-wave form serves by default; "mlpw" = 0 switches BOTH register families off (the tests' "tiles" / "k_mlpv" legs)
-  const int mode = p->tune.mlpb;
-  if (!p->b_ok || mode == 0 || !p->tune.mlpw) return false;
-  const int hm = std::max(p->dm.sizes[1], p->dm.sizes[2]);
-  if (hm <= 128 && mode != 2) return false;
-  if (b_lds_base(p->bd, T, adj, p->dm.solver == LDE_SOLVER_RK4 ? 4 : 6) > LDS_MAX) return false;
-  // one workgroup per CU (512 registers per lane): 256 trajectories are resident at once; an uncoupled solve may queue a second
-  // round, a coupled adaptive one needs every trajectory resident
-  return B <= (coupled_adaptive ? 256 : 512);
-}
 template <int SOLVER, bool ADJ, bool DISC = false>
 static int launch_b(MlpPlan* p, const KOpts& o, VArgs& a, bool coop, hipStream_t stream, std::string& err) {
-  MlpDims dmv = p->dm;
-  BDims bdv = p->bd;
-  KOpts ov = o;
-  const bool d8 = bdv.DP == 8;
-  const bool tanh_ = dmv.act == LDE_ACT_TANH;
-  const size_t cot = ADJ ? (size_t)o.T * dmv.Dp * 4 * (o.checkpoint ? 2 : 1) : 0;
-  const void* fn = tanh_ ? (d8 ? (const void*)k_mlpb<SOLVER, 8, LDE_ACT_TANH, DISC, ADJ> : (const void*)k_mlpb<SOLVER, 16, LDE_ACT_TANH, DISC, ADJ>)
-                         : (d8 ? (const void*)k_mlpb<SOLVER, 8, LDE_ACT_RELU, DISC, ADJ> : (const void*)k_mlpb<SOLVER, 16, LDE_ACT_RELU, DISC, ADJ>);
-  size_t lds = b_lds_base(bdv, o.T, ADJ, SOLVER == LDE_SOLVER_RK4 ? 4 : 6);
+  const bool d8 = p->bd.DP == 8;
+  const void* fn = p->dm.act == LDE_ACT_TANH ? (d8 ? (const void*)k_mlpb<SOLVER, 8, LDE_ACT_TANH, DISC, ADJ> : (const void*)k_mlpb<SOLVER, 16, LDE_ACT_TANH, DISC, ADJ>)
+                                             : (d8 ? (const void*)k_mlpb<SOLVER, 8, LDE_ACT_RELU, DISC, ADJ> : (const void*)k_mlpb<SOLVER, 16, LDE_ACT_RELU, DISC, ADJ>);
+  size_t lds = b_lds_base(p->bd, o.T, ADJ, SOLVER == LDE_SOLVER_RK4 ? 4 : 6);
+  const size_t cot = ADJ ? (size_t)o.T * p->dm.Dp * 4 * (o.checkpoint ? 2 : 1) : 0;
   a.cot_lds = ADJ && cot <= 40 * 1024 && lds + cot <= LDS_MAX;   // the trajectory's dẑ (and saved ẑ) by save time: no global load inside the solve
   if (a.cot_lds) lds += cot;
-  {   // dynamic LDS beyond the default limit needs the attribute, once per instantiation
-    static bool attr_set[2][2] = {};
-    if (!attr_set[d8][tanh_]) {
-      hipFuncAttributes fa{};
-      (void)hipFuncGetAttributes(&fa, fn);
-      const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX - (int)fa.sharedSizeBytes);
-      if (ea != hipSuccess) {
-        (void)hipGetLastError();
-        err = std::string("hipFuncSetAttribute(k_mlpb) failed: ") + hipGetErrorString(ea);
-        return LDE_ERR_HIP;
-      }
-      attr_set[d8][tanh_] = true;
-    }
-  }
   a.wpack = p->bpack;
-  const bool relay = a.gs.cross();   // LDE_BATCH_COUPLED_GLOBAL: sums leave the device; a plain launch (see launch_w)
-  if (coop || relay) {
-    const int rcw = grid_words_prepare(p, o.B, a, stream, err);
-    if (rcw) return rcw;
-  }
-#if LDE_PROF
-  prof_reset();
-#endif
-  const int rcl = launch_maybe_coop(coop && !relay, fn, dim3(o.B), dim3(mlpb::UT), lds, stream, err, "k_mlpb", dmv, bdv, ov, a);
-#if LDE_PROF
-  prof_dump(ADJ ? "b adjoint" : "b forward", stream);
-#endif
-  return rcl;
+  return launch_reg(p, fn, "k_mlpb", ADJ, p->bd, o, a, o.B, mlpb::UT, lds, coop, stream, err);
 }
 
-// ---- two trajectories per workgroup, networks up to 128 wide (lde_mlpc.h)
+// two trajectories per workgroup, networks up to 128 wide (lde_mlpc.h)
 static size_t c_lds_base(int T, bool adj, int nst, bool disc = false) {
   const int nsl = disc ? 2 * nst + 1 : (adj ? nst + 1 : 1);   // (the discrete sweep: three rotating first-stage slots + two banks of nst − 1)
   return (((size_t)T * 8 + 15) & ~size_t(15)) + (size_t)(nsl * mlpc::SLOT + (adj ? 16 * mlpc::HV : 0) + 16 * 16 * 4) * 4 +
          (size_t)128 * mlpc::W13S * 4 + (adj ? (size_t)mlpc::GS * 64 * 16 + 4 * mlpc::DP * 2 * 4 : 0) + 16;
 }
-static bool c_applicable(const MlpPlan* p, int B, int T, bool adj, bool coupled_adaptive) {
-  if (!p->c_ok || p->tune.mlpb == 0 || !p->tune.mlpw) return false;   // (the switches of k_mlpb: 0 = k_mlpw instead — the parity reference)
-  if (c_lds_base(T, adj, p->dm.solver == LDE_SOLVER_RK4 ? 4 : 6) > LDS_MAX) return false;
-  // one workgroup (two trajectories) per CU: 512 trajectories are resident at once, which a coupled adaptive solve needs
-  return B <= (coupled_adaptive ? 512 : 1024);
-}
-// LDE_SENSE_DISCRETE: the kernel family that sweeps the step record. The register kernels take the shapes they serve in the continuous
-// adjoint — without that path's residency limit (no grid-wide sum here: workgroups may queue) — up to what one slab row per workgroup
-// costs in memory; everything else runs on the tiles (lde_mlpd.h).
-static int disc_family(const MlpPlan* p, int B, int T) {
-  const MlpDims& dm = p->dm;
-  if (mlp64_applicable(p, B)) return DISC_64;
-  const int nst = dm.solver == LDE_SOLVER_RK4 ? 4 : 6;
-  if (b_applicable(p, std::min(B, 256), T, true, false) && B <= 1024 && b_lds_base(p->bd, T, true, nst) + (size_t)T * dm.Dp * 4 <= LDS_MAX) return DISC_B;
-  if (c_applicable(p, std::min(B, 512), T, true, false) && B <= 2048 && c_lds_base(T, true, nst, true) <= LDS_MAX) return DISC_C;
-  return DISC_TILES;
-}
-
 template <int SOLVER, bool ADJ, bool DISC = false>
 static int launch_c(MlpPlan* p, const KOpts& o, VArgs& a, bool coop, hipStream_t stream, std::string& err) {
-  MlpDims dmv = p->dm;
-  CDims cdv = p->cd;
-  KOpts ov = o;
-  const bool tanh_ = dmv.act == LDE_ACT_TANH;
-  const void* fn = tanh_ ? (const void*)k_mlpc<SOLVER, LDE_ACT_TANH, DISC, ADJ> : (const void*)k_mlpc<SOLVER, LDE_ACT_RELU, DISC, ADJ>;
+  const void* fn = p->dm.act == LDE_ACT_TANH ? (const void*)k_mlpc<SOLVER, LDE_ACT_TANH, DISC, ADJ> : (const void*)k_mlpc<SOLVER, LDE_ACT_RELU, DISC, ADJ>;
   size_t lds = c_lds_base(o.T, ADJ, SOLVER == LDE_SOLVER_RK4 ? 4 : 6, DISC);
   if (lds > LDS_MAX) {
     err = "k_mlpc: the save-time grid does not fit LDS";
     return LDE_ERR_UNSUPPORTED;
   }
-  const size_t cot = ADJ ? (size_t)2 * o.T * dmv.Dp * 4 * ((o.checkpoint && !DISC) ? 2 : 1) : 0;
+  const size_t cot = ADJ ? (size_t)2 * o.T * p->dm.Dp * 4 * ((o.checkpoint && !DISC) ? 2 : 1) : 0;
   a.cot_lds = ADJ && lds + cot <= LDS_MAX;   // the two trajectories' dẑ (and saved ẑ) by save time: no global load inside the solve
   if (a.cot_lds) lds += cot;
-  {   // dynamic LDS beyond the default limit needs the attribute, once per instantiation
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[tanh_]) {
-      hipFuncAttributes fa{};
-      (void)hipFuncGetAttributes(&fa, fn);
-      const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX - (int)fa.sharedSizeBytes);
-      if (ea != hipSuccess) {
-        (void)hipGetLastError();
-        err = std::string("hipFuncSetAttribute(k_mlpc) failed: ") + hipGetErrorString(ea);
-        return LDE_ERR_HIP;
-      }
-      attr_set[tanh_] = true;
-    }
-  }
   a.wpack = p->cpack;
   const int nwg = (o.B + 1) / 2;
   a.gs.nwg = a.gs.nwg > 1 ? nwg : a.gs.nwg;   // (grid-wide sums: one word pair per workgroup)
-  const bool relay = a.gs.cross();   // LDE_BATCH_COUPLED_GLOBAL: sums leave the device; a plain launch (see launch_w)
-  if (coop || relay) {
-    const int rcw = grid_words_prepare(p, o.B, a, stream, err);
-    if (rcw) return rcw;
+  return launch_reg(p, fn, "k_mlpc", ADJ, p->cd, o, a, nwg, mlpc::UT, lds, coop, stream, err);
+}
+
+// ---- the tile adjoint (16 columns per workgroup) and the 4-columns-per-wave adjoint in front of it (lde_mlp4.h)
+template <int SOLVER>
+static int launch_adjoint(MlpPlan* p, const KOpts& o, const BwdArgs& a, int nwg, size_t lds, hipStream_t stream, std::string& err, bool coop) {
+  const void* fn = (const void*)k_mlp_adjoint<SOLVER, 512>;
+  const int rca = raise_lds_limit(fn, LDS_WHOLE, "k_mlp_adjoint", err);
+  if (rca) return rca;
+  MlpDims dmv = p->dm;
+  KOpts ov = o;
+  BwdArgs av = a;
+  return launch_maybe_coop(coop, fn, dim3(nwg), dim3(512), lds, stream, err, "k_mlp_adjoint", dmv, ov, av);
+}
+// k_mlp4_adjoint's LDS layout, bytes and workgroups for a batch
+static void mlp4_layout(const MlpDims& dm, int T, int B, Mlp4Dims* md, size_t* lds, int* nblocks) {
+  int maxw = 0;
+  for (int l = 0; l <= dm.nL; l++) maxw = std::max(maxw, dm.sizes[l]);
+  int off = 0;
+  for (int l = 0; l < dm.nL; l++) {
+    int v = (dm.sizes[l] + 3) & ~3;
+    if (((v >> 2) & 1) == 0) v += 4;   // (ldw/4) odd ⇒ the row-segment reads of 16 consecutive rows hit distinct banks
+    md->ldw[l] = v;
+    md->wl_off[l] = off;
+    off += dm.sizes[l + 1] * v;
   }
-#if LDE_PROF
-  prof_reset();
-#endif
-  const int rcl = launch_maybe_coop(coop && !relay, fn, dim3(nwg), dim3(mlpc::UT), lds, stream, err, "k_mlpc", dmv, cdv, ov, a);
-#if LDE_PROF
-  prof_dump(ADJ ? "c adjoint" : "c forward", stream);
-#endif
-  return rcl;
+  for (int l = 0; l < dm.nL; l++) {
+    md->bl_off[l] = off;
+    off += (dm.sizes[l + 1] + 63) & ~63;
+  }
+  md->w_total = off;
+  md->ldx = ((maxw + 63) & ~63) + 8;   // +8: the 4 columns of a panel start 8 banks apart (broadcast b128 reads, b128 writes: conflict-free)
+  const int nwaves = cdiv(B, 4);
+  int wpb = cdiv(nwaves, 256);
+  wpb = wpb < 1 ? 1 : (wpb > 4 ? 4 : wpb);
+  md->wpb = wpb;
+  *nblocks = cdiv(nwaves, wpb);
+  *lds = ((size_t)md->w_total + (size_t)wpb * (dm.nL + 1) * 4 * md->ldx + (size_t)wpb * 4 + 8) * sizeof(float) + (size_t)T * sizeof(double) + 64 + 8 * 264 * sizeof(float);   // tail slack: operand prefetch reads ≤ 8 rows past the end
+}
+template <int SOLVER, int NTH>
+static int launch_mlp4(const MlpDims& dm, const Mlp4Dims& md, const KOpts& o, const BwdArgs& a, int nblocks, size_t lds,
+                       hipStream_t stream, std::string& err, bool coop) {
+  const void* fn = (const void*)k_mlp4_adjoint<SOLVER, NTH>;
+  const int rca = raise_lds_limit(fn, LDS_WHOLE, "k_mlp4_adjoint", err);
+  if (rca) return rca;
+  MlpDims dmv = dm;
+  Mlp4Dims mdv = md;
+  KOpts ov = o;
+  BwdArgs av = a;
+  return launch_maybe_coop(coop, fn, dim3(nblocks), dim3(64 * md.wpb), lds, stream, err, "k_mlp4_adjoint", dmv, mdv, ov, av);
+}
+
+// The candidate families' LDS bytes for B trajectories on T save times, forward or adjoint (`md`: k_mlp4_adjoint's layout with them)
+static lde_host::MlpLds mlp_lds_numbers(const MlpPlan* p, int B, int T, bool adj, Mlp4Dims* md = nullptr) {
+  const MlpDims& dm = p->dm;
+  const lde_host::MlpShape& sh = p->sh;
+  const int nst = dm.solver == LDE_SOLVER_RK4 ? 4 : 6;
+  lde_host::MlpLds l;
+  l.cap = LDS_MAX;
+  if (sh.vec_ok) l.v_fixed = vec_lds_fixed(dm, p->vd, T, adj);
+  if (sh.w_ok) l.w = w_lds_base(p->wd, T, adj);
+  if (sh.b_ok) l.b = b_lds_base(p->bd, T, adj, nst);
+  if (sh.c_ok) l.c = c_lds_base(T, adj, nst);
+  if (adj) {
+    l.b_disc = l.b + (size_t)T * dm.Dp * 4;
+    if (sh.c_ok) l.c_disc = c_lds_base(T, true, nst, true);
+    Mlp4Dims own;
+    mlp4_layout(dm, T, B, md ? md : &own, &l.mlp4, &l.mlp4_blocks);
+  }
+  return l;
 }
 
 int mlp_last_family(const MlpPlan* p) { return p->last_family; }
@@ -2251,7 +2088,7 @@ static int global_arm(MlpPlan* p, VArgs& a, hipStream_t stream, std::string& err
   a.gs.xlaunch = 0;
   a.gs.xspin_k = p->tune.peer_spin_k > 0 ? p->tune.peer_spin_k : 8192;
   a.Bnorm = 0;
-  if (p->global_mode && p->peer_n > 0) {   // device to device: nothing for the host to serve, the call stays asynchronous
+  if (p->sh.global && p->peer_n > 0) {   // device to device: nothing for the host to serve, the call stays asynchronous
     if (hipMemsetAsync(p->mbox_dev, 0, 16 * sizeof(unsigned long long), stream) != hipSuccess) {
       err = "hipMemsetAsync(mailbox) failed";
       return LDE_ERR_HIP;
@@ -2265,7 +2102,7 @@ static int global_arm(MlpPlan* p, VArgs& a, hipStream_t stream, std::string& err
     a.Bnorm = p->global_batch;
     return LDE_OK;
   }
-  if (!p->global_mode || !p->sum_hook) return LDE_OK;
+  if (!p->sh.global || !p->sum_hook) return LDE_OK;
   for (int i = 0; i < 16; i++) p->mbox[i] = 0;
   if (hipMemsetAsync(p->mbox_dev, 0, 16 * sizeof(unsigned long long), stream) != hipSuccess) {
     err = "hipMemsetAsync(mailbox) failed";
@@ -2284,7 +2121,7 @@ static int global_arm(MlpPlan* p, VArgs& a, hipStream_t stream, std::string& err
 }
 // … and serve it until the kernel has finished: every request {count, tag} is answered with the sums over all ranks
 static int global_serve(MlpPlan* p, hipStream_t stream, std::string& err) {
-  if (!p->global_mode || !p->sum_hook) return LDE_OK;
+  if (!p->sh.global || !p->sum_hook) return LDE_OK;
   if (hipEventRecord(p->mbox_ev, stream) != hipSuccess) {
     err = "hipEventRecord(mailbox) failed";
     return LDE_ERR_HIP;
@@ -2359,253 +2196,185 @@ static bool zero_regions(hipStream_t stream, std::initializer_list<std::pair<voi
   return hipGetLastError() == hipSuccess;
 }
 
+// Workspace of the adjoint for batches up to B with T save points. `steps_hint` > 0: step attempts known in advance
+// (fixed step size). Staging slots per workgroup: stages × (3 step attempts per save interval + 32) — doubled whenever
+// the previous call reported an overflow — bounded by a memory budget
+// (24 GiB of the 288); a workgroup that needs more folds its slots into its private slab
+// (slow but correct). option "mlp_stage_slots" forces the slot count (tests).
+int mlp_reserve_adjoint(MlpPlan* p, int B, int T, int64_t steps_hint, std::string& err) {
+  const MlpDims& dm = p->dm;
+  // the families that fold the weight gradient inside the solve kernel leave rows of it (continuous and discrete adjoint alike): no staging area
+  const lde_host::MlpFamily fam = lde_host::mlp_adjoint_mapping(p->sh, p->tune, mlp_lds_numbers(p, B, T, true), B, false);
+  if (const int rows = lde_host::mlp_reserved_rows(fam, B)) {
+    p->rows_stride = (dm.nW + 63) & ~63;
+    if (!grow(&p->rows, &p->rows_cap, (size_t)rows * p->rows_stride)) {
+      err = "MLP plan: hipMalloc of the weight-gradient rows failed";
+      return LDE_ERR_ALLOC;
+    }
+    return LDE_OK;
+  }
+  const int nwg = cdiv(B, NB);
+  const int nst = dm.solver == LDE_SOLVER_RK4 ? 4 : 6;
+  constexpr long budget_mb = 24576L;
+  const int slots_force = p->tune.stage_slots;
+  if (p->fb_pending) {
+    if (hipEventQuery(p->fb_ev) == hipSuccess) {
+      p->fb_pending = false;
+      if (p->fb_host[0] > 0 && p->cap_scale < 64) p->cap_scale *= 2;
+    } else
+      (void)hipGetLastError();   // hipErrorNotReady is not an error of the caller's
+  }
+  int64_t want = (int64_t)nst * (steps_hint > 0 ? steps_hint + 2 : p->cap_scale * (3 * (int64_t)(T > 1 ? T - 1 : 1) + 32));
+  const int64_t fit = ((int64_t)budget_mb << 20) / ((int64_t)(nwg + 1) * dm.blk_floats * (int64_t)sizeof(float));
+  if (want > fit) want = fit;
+  if (slots_force > 0) want = slots_force;
+  if (want < nst) want = nst;
+  if (want > (1 << 24)) want = 1 << 24;
+  int ks = cdiv(768, nwg * dw_jobs(dm, dw_pick_ndw(dm)));
+  ks = ks < 1 ? 1 : (ks > 16 ? 16 : ks);
+  size_t nsl = (size_t)p->nslots_cap;
+  // the staging area is the large allocation: if the device cannot give it (another allocator holds the memory, a smaller
+  // device), halve the slot count down to one step's worth — a workgroup that runs out of slots folds them into its private
+  // slab inside the solve kernel (exact), so fewer slots cost time, never correctness
+  int cap = (int)want;
+  const size_t stage_before = p->stage_cap;
+  for (;;) {
+    if (grow(&p->stage, &p->stage_cap, (size_t)(nwg + 1) * cap * dm.blk_floats)) break;
+    (void)hipGetLastError();
+    if (cap <= nst || slots_force > 0 || steps_hint > 0) { cap = 0; break; }
+    cap = cap / 2 < nst ? nst : cap / 2;
+  }
+  if (cap == 0 || !grow(&p->wts, &p->wts_cap, (size_t)(nwg + 1) * cap * NB) ||
+      !grow(&p->slab, &p->slab_cap, ((size_t)(nwg + 1) * (1 + ks) + 1) * dm.slab_n) || !grow(&p->nslots, &nsl, (size_t)2 * (nwg + 1))) {
+    err = "MLP plan: hipMalloc of the adjoint workspace failed";
+    return LDE_ERR_ALLOC;
+  }
+  // a fresh staging area holds arbitrary bits; the one-trajectory-per-workgroup kernel fills a tile's slots column by column,
+  // and a column that never reaches a slot carries weight 0 there — its a-panel must still be finite (0·NaN) for k_mlp_dw
+  if (p->stage_cap != stage_before && hipMemset(p->stage, 0, p->stage_cap * sizeof(float)) != hipSuccess) {
+    err = "MLP plan: hipMemset(stage) failed";
+    return LDE_ERR_HIP;
+  }
+  p->nslots_cap = (int)nsl;
+  p->adj_cap = cap;
+  p->adj_ks = ks;
+  return LDE_OK;
+}
+
+// The part every family's argument block shares (VArgs, FwdArgs, BwdArgs): the call's pointers, the statistics, a grid-sum block of one
+// workgroup — no sum; a solve that sums over the grid sets gs.nwg, global_arm the cross-rank words
+template <class Args>
+static Args args_common(const MlpPlan* p, const float* theta, const double* ts_dev, const float* W_dev, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret) {
+  Args a{};
+  a.theta = theta; a.ts = ts_dev; a.Wflat = W_dev;
+  a.st_nfe = nfe; a.st_nacc = nacc; a.st_nrej = nrej; a.st_ret = ret;
+  a.gs.counter = p->counter; a.gs.slots = p->slots; a.gs.abort_flag = p->abort_flag; a.gs.nwg = 1;
+  a.gs.xspin_k = 8192;
+  return a;
+}
+static bool zero_grid_sum(MlpPlan* p, hipStream_t stream, std::string& err) {   // counter + abort flag of the grid-wide sums
+  if (zero_regions(stream, {{p->counter, sizeof(unsigned)}, {p->abort_flag, sizeof(int)}})) return true;
+  err = "k_zero_regions(counter) failed";
+  return false;
+}
+
 int mlp_forward(MlpPlan* p, const float* W_dev, const float* z0, const float* theta, const double* ts_dev,
                 const KOpts& o, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret,
                 hipStream_t stream, std::string& err) {
+  using namespace lde_host;
   const MlpDims& dm = p->dm;
-  const bool recording = o.rec.n != nullptr;   // the step record is written by k_mlp64 and by k_mlp_forward (the tiles)
-  if (mlp64_applicable(p, o.B)) {   // small network, small state: one wave per trajectory, registers only (lde_mlp64.h)
-    VArgs va{};
-    va.z0 = z0; va.theta = theta; va.ts = ts_dev; va.Wflat = W_dev; va.z_out = z_out; va.retcode = retcode;
-    va.st_nfe = nfe; va.st_nacc = nacc; va.st_nrej = nrej; va.st_ret = ret;
-    return launch_mlp64<false>(dm, o, va, stream, err);
+  const bool recording = o.rec.n != nullptr;   // k_mlp64, k_mlpb, k_mlpc and the tiles write the step record; k_mlpw and k_mlpv do not (the mapping knows)
+  const char* why = "";
+  const MlpFamily fam = lde_host::mlp_forward_mapping(p->sh, p->tune, mlp_lds_numbers(p, o.B, o.T, false), o.B, o.adaptive != 0, recording, &why);
+  if (fam == MLP_NOT_SERVED) {
+    err = why;
+    return LDE_ERR_UNSUPPORTED;
   }
-  {   // small batches: one trajectory per workgroup, lanes = hidden units (lde_mlpv.h)
-    size_t ldsv = 0;
-    const bool ca = dm.coupled && o.adaptive && o.B > 1;
-    const bool use_b = b_applicable(p, o.B, o.T, false, ca);
-    const bool use_c = !use_b && c_applicable(p, o.B, o.T, false, ca);
-    const bool use_w = use_b || use_c || (!recording && w_applicable(p, o.B, o.T, false, ca));   // (k_mlpw / k_mlpv write no step record)
-    if (p->global_mode && !use_w) {
-      err = "LDE_BATCH_COUPLED_GLOBAL: this shape / batch is not served by the register kernels (three Dense layers, 2·D' ≤ 64, H ≤ 200, B·W ≤ 1024 waves)";
-      return LDE_ERR_UNSUPPORTED;
-    }
-    if (use_w || (!recording && vec_applicable(p, o.B, o.T, false, ca, &ldsv, err))) {
-      VArgs va{};
-      va.z0 = z0; va.theta = theta; va.ts = ts_dev; va.vecw = p->vecw; va.Wflat = W_dev; va.z_out = z_out; va.retcode = retcode;
-      va.st_nfe = nfe; va.st_nacc = nacc; va.st_nrej = nrej; va.st_ret = ret;
-      va.gs.counter = p->counter; va.gs.slots = p->slots; va.gs.abort_flag = p->abort_flag; va.gs.nwg = ca ? o.B : 1;
-      if (ca && !zero_regions(stream, {{p->counter, sizeof(unsigned)}, {p->abort_flag, sizeof(int)}})) {
-        err = "k_zero_regions(counter) failed";
-        return LDE_ERR_HIP;
-      }
-      if (use_w) {
-        const int rca = global_arm(p, va, stream, err);
-        if (rca) return rca;
-        const int rcw = use_b ? (dm.solver == LDE_SOLVER_RK4 ? launch_b<LDE_SOLVER_RK4, false>(p, o, va, ca, stream, err)
-                                                             : launch_b<LDE_SOLVER_TSIT5, false>(p, o, va, ca, stream, err))
-                        : use_c ? (dm.solver == LDE_SOLVER_RK4 ? launch_c<LDE_SOLVER_RK4, false>(p, o, va, ca, stream, err)
-                                                               : launch_c<LDE_SOLVER_TSIT5, false>(p, o, va, ca, stream, err))
-                              : (dm.solver == LDE_SOLVER_RK4 ? launch_w<LDE_SOLVER_RK4, false>(p, o, va, ca, stream, err)
-                                                             : launch_w<LDE_SOLVER_TSIT5, false>(p, o, va, ca, stream, err));
-        return rcw ? rcw : global_serve(p, stream, err);
-      }
-      return dm.solver == LDE_SOLVER_RK4 ? launch_vec<LDE_SOLVER_RK4, false>(p, o, va, ldsv, ca, stream, err)
-                                         : launch_vec<LDE_SOLVER_TSIT5, false>(p, o, va, ldsv, ca, stream, err);
-    }
+  if (fam != MLP_TILES) {
+    VArgs va = args_common<VArgs>(p, theta, ts_dev, W_dev, nfe, nacc, nrej, ret);
+    va.z0 = z0; va.vecw = p->vecw; va.z_out = z_out; va.retcode = retcode;
+    if (fam == MLP_64) return mlp_dispatch(dm.solver, [&](auto S) { return launch_mlp64<decltype(S)::value, false>(dm, o, va, stream, err); });
+    const bool ca = dm.coupled && o.adaptive && o.B > 1;   // every trajectory's workgroup meets in the grid-wide sum of the step control
+    va.gs.nwg = ca ? o.B : 1;
+    if (ca && !zero_grid_sum(p, stream, err)) return LDE_ERR_HIP;
+    const bool reg = fam != MLP_V;   // the register families exchange their sums across ranks (LDE_BATCH_COUPLED_GLOBAL)
+    int rc = reg ? global_arm(p, va, stream, err) : LDE_OK;
+    if (rc) return rc;
+    rc = mlp_dispatch(dm.solver, [&](auto S) {
+      constexpr int SV = decltype(S)::value;
+      return fam == MLP_B ? launch_b<SV, false>(p, o, va, ca, stream, err)
+           : fam == MLP_C ? launch_c<SV, false>(p, o, va, ca, stream, err)
+           : fam == MLP_W ? launch_w<SV, false>(p, o, va, ca, stream, err)
+                          : launch_vec<SV, false>(p, o, va, ca, stream, err);
+    });
+    return rc || !reg ? rc : global_serve(p, stream, err);
   }
   const int nwg = cdiv(o.B, NB);
   const bool sync = dm.coupled && o.adaptive && nwg > 1;
-  if (sync && nwg > 256) {
-    err = "coupled adaptive solve: batch per GPU limited to 4096 trajectories (one resident workgroup per CU)";
-    return LDE_ERR_UNSUPPORTED;
-  }
   constexpr int NTF = 512;   // forward: 8 waves (2 per SIMD) — the second wave hides the first one's LDS/barrier waits
   const size_t fixed = fwd_lds_fixed(dm, o.T, NTF);
   if (fixed > LDS_MAX) {
     err = "MLP forward: tile state does not fit the 160 KiB LDS";
     return LDE_ERR_UNSUPPORTED;
   }
-  const bool rk4 = dm.solver == LDE_SOLVER_RK4;
-  const void* kfn = rk4 ? (const void*)k_mlp_forward<LDE_SOLVER_RK4, NTF> : (const void*)k_mlp_forward<LDE_SOLVER_TSIT5, NTF>;
-  static bool attr_set[2] = {false, false};
-  const int ki = rk4 ? 1 : 0;
-  if (!attr_set[ki]) {
-    if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) {
-      err = "hipFuncSetAttribute(k_mlp_forward) failed";
-      return LDE_ERR_HIP;
-    }
-    attr_set[ki] = true;
-  }
-  FwdArgs a;
-  a.z0 = z0; a.theta = theta; a.ts = ts_dev; a.frag = p->frag; a.Wflat = W_dev; a.z_out = z_out; a.retcode = retcode;
-  a.st_nfe = nfe; a.st_nacc = nacc; a.st_nrej = nrej; a.st_ret = ret;
-  a.gs.counter = p->counter; a.gs.slots = p->slots; a.gs.abort_flag = p->abort_flag; a.gs.nwg = sync ? nwg : 1;
-  const size_t lds = with_cache(fixed, p->nfrag);
-  a.lds_bytes = (int)lds;
-  if (sync && !zero_regions(stream, {{p->counter, sizeof(unsigned)}, {p->abort_flag, sizeof(int)}})) {
-    err = "k_zero_regions(counter) failed";
-    return LDE_ERR_HIP;
-  }
+  return mlp_dispatch(dm.solver, [&](auto S) {
+    const void* kfn = (const void*)k_mlp_forward<decltype(S)::value, NTF>;
+    const int rca = raise_lds_limit(kfn, LDS_WHOLE, "k_mlp_forward", err);
+    if (rca) return rca;
+    FwdArgs a = args_common<FwdArgs>(p, theta, ts_dev, W_dev, nfe, nacc, nrej, ret);
+    a.z0 = z0; a.frag = p->frag; a.z_out = z_out; a.retcode = retcode;
+    a.gs.nwg = sync ? nwg : 1;
+    const size_t lds = with_cache(fixed, p->nfrag);
+    a.lds_bytes = (int)lds;
+    if (sync && !zero_grid_sum(p, stream, err)) return (int)LDE_ERR_HIP;
 #if LDE_PROF
-  prof_reset();
+    prof_reset();
 #endif
-  MlpDims dmv = dm;
-  KOpts ov = o;
-  const int rcl = launch_maybe_coop(sync, kfn, dim3(nwg), dim3(NTF), lds, stream, err, "k_mlp_forward", dmv, ov, a);
+    MlpDims dmv = dm;
+    KOpts ov = o;
+    const int rcl = launch_maybe_coop(sync, kfn, dim3(nwg), dim3(NTF), lds, stream, err, "k_mlp_forward", dmv, ov, a);
 #if LDE_PROF
-  prof_dump("forward", stream);
+    prof_dump("forward", stream);
 #endif
-  return rcl;
+    return rcl;
+  });
 }
 
-template <int SOLVER>
-static int launch_adjoint(MlpPlan* p, const KOpts& o, const BwdArgs& a, int nwg, size_t lds, hipStream_t stream,
-                          std::string& err, bool coop) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)k_mlp_adjoint<SOLVER, 512>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)LDS_MAX) != hipSuccess) {
-      err = "hipFuncSetAttribute(k_mlp_adjoint) failed";
-      return LDE_ERR_HIP;
-    }
-    attr_set = true;
-  }
-  MlpDims dmv = p->dm;
-  KOpts ov = o;
-  BwdArgs av = a;
-  return launch_maybe_coop(coop, (const void*)k_mlp_adjoint<SOLVER, 512>, dim3(nwg), dim3(512), lds, stream, err, "k_mlp_adjoint", dmv, ov, av);
-}
-
-// ---- the 4-columns-per-wave adjoint (lde_mlp4.h): applicability, LDS layout, launch --------------------------------
-static bool mlp4_layout(const MlpTune& tune, const MlpDims& dm, int T, int B, bool coupled_adaptive, Mlp4Dims* md, size_t* lds, int* nblocks) {
-  if (!tune.mlp4 || dm.Dp > 64 || dm.P > 1) return false;
-  int maxw = 0;
-  for (int l = 0; l <= dm.nL; l++) maxw = std::max(maxw, dm.sizes[l]);
-  // measured (MI355X): one wave has ONE SIMD's matrix pipe and v_mfma_f32_4x4x1 costs 11 cycles per 256 MACs (the
-  // 16x16x4 form: 8), so the 4-column kernel only wins while the layers are small enough for the 16-column kernel's
-  // fixed ≈ 2 000 cycles per layer to dominate: config 3 (64 wide) 7.3 → 5.3 ms, config 4 (128 wide) 4.4 → 5.5 ms.
-  const int maxw_lim = tune.mlp4_maxw;
-  if (maxw > maxw_lim || maxw > 256) return false;
-  int off = 0;
-  for (int l = 0; l < dm.nL; l++) {
-    int v = (dm.sizes[l] + 3) & ~3;
-    if (((v >> 2) & 1) == 0) v += 4;   // (ldw/4) odd ⇒ the row-segment reads of 16 consecutive rows hit distinct banks
-    md->ldw[l] = v;
-    md->wl_off[l] = off;
-    off += dm.sizes[l + 1] * v;
-  }
-  for (int l = 0; l < dm.nL; l++) {
-    md->bl_off[l] = off;
-    off += (dm.sizes[l + 1] + 63) & ~63;
-  }
-  md->w_total = off;
-  md->ldx = ((maxw + 63) & ~63) + 8;   // +8: the 4 columns of a panel start 8 banks apart (broadcast b128 reads, b128 writes: conflict-free)
-  const int nwaves = cdiv(B, 4);
-  int wpb = cdiv(nwaves, 256);
-  wpb = wpb < 1 ? 1 : (wpb > 4 ? 4 : wpb);
-  md->wpb = wpb;
-  *nblocks = cdiv(nwaves, wpb);
-  if (coupled_adaptive && *nblocks > 256) return false;   // grid-wide sums need every workgroup resident
-  *lds = ((size_t)md->w_total + (size_t)wpb * (dm.nL + 1) * 4 * md->ldx + (size_t)wpb * 4 + 8) * sizeof(float) + (size_t)T * sizeof(double) + 64 + 8 * 264 * sizeof(float);   // tail slack: operand prefetch reads ≤ 8 rows past the end
-  return *lds <= LDS_MAX;
-}
-
-template <int SOLVER, int NTH>
-static int launch_mlp4(const MlpDims& dm, const Mlp4Dims& md, const KOpts& o, const BwdArgs& a, int nblocks, size_t lds,
-                       hipStream_t stream, std::string& err, bool coop) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)k_mlp4_adjoint<SOLVER, NTH>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)LDS_MAX) != hipSuccess) {
-      err = "hipFuncSetAttribute(k_mlp4_adjoint) failed";
-      return LDE_ERR_HIP;
-    }
-    attr_set = true;
-  }
-  MlpDims dmv = dm;
-  Mlp4Dims mdv = md;
-  KOpts ov = o;
-  BwdArgs av = a;
-  return launch_maybe_coop(coop, (const void*)k_mlp4_adjoint<SOLVER, NTH>, dim3(nblocks), dim3(64 * md.wpb), lds, stream, err,
-                           "k_mlp4_adjoint", dmv, mdv, ov, av);
-}
-
-// LDE_SENSE_DISCRETE: the reverse sweep over the forward solve's step record (lde_mlpd.h), then the weight gradient from the staged panels
-static int mlp_adjoint_disc(MlpPlan* p, const float* W_dev, const float* z_out, const float* theta, const double* ts_dev,
-                            const KOpts& o, const float* dz_out, float* dz0, float* dtheta, float* dW, int32_t* nfe, int32_t* nacc,
-                            int32_t* nrej, int32_t* ret, hipStream_t stream, std::string& err) {
+// The adjoint of the families that fold the weight gradient inside the solve kernel (k_mlp64, k_mlpb, k_mlpc; continuous and discrete
+// alike): the workspace check, the launch between its phase marks, k_sum_rows over the rows the kernel wrote. No staging area.
+static int rows_adjoint(MlpPlan* p, lde_host::MlpFamily fam, VArgs& va, const KOpts& o, float* dW, hipStream_t stream, std::string& err) {
+  using namespace lde_host;
   const MlpDims& dm = p->dm;
-  if (!o.rec.n || !o.rec.y) {
-    err = "MLP adjoint (LDE_SENSE_DISCRETE): no step record";
-    return LDE_ERR_INVALID_ARG;
-  }
-  const int fam = disc_family(p, o.B, o.T);
-  p->last_family = fam == DISC_B ? 2 : (fam == DISC_C ? 3 : 0);
-  if (fam == DISC_B || fam == DISC_C) {   // W₂ as register blocks, the weight gradient folded on the CU: two launches, no staging area, no grid-wide sum
-    const int nrows = fam == DISC_B ? o.B : (o.B + 1) / 2;
-    if (!p->rows || p->rows_cap < (size_t)o.B * p->rows_stride || p->rows_stride < dm.nW) {
-      err = "MLP adjoint: workspace not reserved";
-      return LDE_ERR_INVALID_ARG;
-    }
-    VArgs va{};
-    va.theta = theta; va.ts = ts_dev; va.Wflat = W_dev; va.z_out = const_cast<float*>(z_out); va.dz_out = dz_out;
-    va.dz0 = dz0; va.dtheta = dtheta; va.stage = p->rows; va.cap = p->rows_stride;
-    va.st_nfe = nfe; va.st_nacc = nacc; va.st_nrej = nrej; va.st_ret = ret;
-    va.gs.counter = p->counter; va.gs.slots = p->slots; va.gs.abort_flag = p->abort_flag; va.gs.nwg = 1;
-    va.gs.host_req = nullptr; va.gs.host_rep = nullptr; va.gs.dev_rep = nullptr; va.gs.nranks = 0; va.gs.rank = 0; va.gs.xlaunch = 0; va.gs.xspin_k = 8192; va.Bnorm = 0;
-    phase_mark(p, 0, stream);
-    const bool rk4 = dm.solver == LDE_SOLVER_RK4;
-    const int rcb = fam == DISC_B ? (rk4 ? launch_b<LDE_SOLVER_RK4, true, true>(p, o, va, false, stream, err)
-                                         : launch_b<LDE_SOLVER_TSIT5, true, true>(p, o, va, false, stream, err))
-                                  : (rk4 ? launch_c<LDE_SOLVER_RK4, true, true>(p, o, va, false, stream, err)
-                                         : launch_c<LDE_SOLVER_TSIT5, true, true>(p, o, va, false, stream, err));
-    if (rcb) return rcb;
-    phase_mark(p, 1, stream);
-    if (dW) {
-      hipLaunchKernelGGL(k_sum_rows, dim3(cdiv(dm.nW, 64)), dim3(1024), 0, stream, p->rows, nrows, p->rows_stride, dm.nW, dW, o.dw_overwrite);
-      if (hipGetLastError() != hipSuccess) {
-        err = "k_sum_rows launch failed";
-        return LDE_ERR_HIP;
-      }
-    }
-    phase_mark(p, 2, stream);
-    return LDE_OK;
-  }
-  const int nwg = cdiv(o.B, NB);
-  const size_t fixed = disc_lds_fixed(dm, o.T, 512);
-  if (fixed > LDS_MAX) {
-    err = "MLP adjoint (LDE_SENSE_DISCRETE): tile state does not fit the 160 KiB LDS";
-    return LDE_ERR_UNSUPPORTED;
-  }
-  if (!p->stage || p->adj_cap < 1) {
+  const bool disc = p->sh.disc;
+  if (!p->rows || p->rows_cap < (size_t)mlp_reserved_rows(fam, o.B) * p->rows_stride || p->rows_stride < dm.nW) {
     err = "MLP adjoint: workspace not reserved";
     return LDE_ERR_INVALID_ARG;
   }
-  BwdArgs a{};
-  a.z_out = z_out; a.dz_out = dz_out; a.theta = theta; a.ts = ts_dev; a.frag = p->frag; a.fragT = p->fragT; a.Wflat = W_dev;
-  a.dz0 = dz0; a.dtheta = dtheta; a.slab = p->slab;
-  a.stage = p->stage; a.wts = p->wts; a.nslots = p->nslots; a.nflush = p->nslots + (nwg + 1); a.cap = p->adj_cap;
-  a.ovf = p->fb_dev + 1; a.fallback = 0;
-  a.st_nfe = nfe; a.st_nacc = nacc; a.st_nrej = nrej; a.st_ret = ret;
-  a.gs.counter = p->counter; a.gs.slots = p->slots; a.gs.abort_flag = p->abort_flag; a.gs.nwg = 1;
-  const size_t lds = with_cache(fixed, p->nfrag + p->nfragT);
-  a.lds_bytes = (int)lds;
-  if (!zero_regions(stream, {{p->fb_dev, 2 * sizeof(int32_t)}, {p->nslots, (size_t)2 * (nwg + 1) * sizeof(int32_t)}})) {
-    err = "k_zero_regions failed";
-    return LDE_ERR_HIP;
-  }
-  const bool rk4 = dm.solver == LDE_SOLVER_RK4;
-  const void* fn = rk4 ? (const void*)k_mlp_adjoint_disc<LDE_SOLVER_RK4, 512> : (const void*)k_mlp_adjoint_disc<LDE_SOLVER_TSIT5, 512>;
-  static bool attr_set[2] = {false, false};
-  if (!attr_set[rk4]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) {
-      err = "hipFuncSetAttribute(k_mlp_adjoint_disc) failed";
-      return LDE_ERR_HIP;
-    }
-    attr_set[rk4] = true;
-  }
-  MlpDims dmv = dm;
-  KOpts ov = o;
+  va.stage = p->rows; va.cap = p->rows_stride;
+  // the continuous adjoint of k_mlpb / k_mlpc has step control: grid-wide sums when coupled and adaptive, cross-rank ones under
+  // LDE_BATCH_COUPLED_GLOBAL. k_mlp64 is per-trajectory; a discrete sweep controls nothing.
+  const bool control = !disc && fam != MLP_64;
+  const bool ca = control && dm.coupled && o.adaptive && o.B > 1;
+  va.gs.nwg = ca ? o.B : 1;
+  if (ca && !zero_grid_sum(p, stream, err)) return LDE_ERR_HIP;
+  int rc = control ? global_arm(p, va, stream, err) : LDE_OK;
+  if (rc) return rc;
   phase_mark(p, 0, stream);
-  int rc = launch_maybe_coop(false, fn, dim3(nwg), dim3(512), lds, stream, err, "k_mlp_adjoint_disc", dmv, ov, a);
+  rc = mlp_dispatch(dm.solver, [&](auto S) {
+    constexpr int SV = decltype(S)::value;
+    if (fam == MLP_64) return disc ? launch_mlp64<SV, true, true>(dm, o, va, stream, err) : launch_mlp64<SV, true>(dm, o, va, stream, err);
+    if (fam == MLP_B) return disc ? launch_b<SV, true, true>(p, o, va, false, stream, err) : launch_b<SV, true>(p, o, va, ca, stream, err);
+    return disc ? launch_c<SV, true, true>(p, o, va, false, stream, err) : launch_c<SV, true>(p, o, va, ca, stream, err);
+  });
+  if (!rc && control) rc = global_serve(p, stream, err);
   if (rc) return rc;
   phase_mark(p, 1, stream);
-  DwArgs da;
-  da.stage = p->stage; da.wts = p->wts; da.nslots = p->nslots; da.slab = p->slab + (size_t)(nwg + 1) * dm.slab_n; da.cap = p->adj_cap; da.total = 0;
   if (dW) {
-    rc = launch_weight_gradient(dm, da, nwg, p->adj_ks, p->slab, p->nslots + (nwg + 1), nwg, dW, p->fb_dev, stream, err, o.dw_overwrite != 0);
-    if (rc) return rc;
+    hipLaunchKernelGGL(k_sum_rows, dim3(cdiv(dm.nW, 64)), dim3(1024), 0, stream, p->rows, mlp_adjoint_rows(fam, o.B), p->rows_stride, dm.nW, dW, o.dw_overwrite);
+    if (hipGetLastError() != hipSuccess) {
+      err = "k_sum_rows launch failed";
+      return LDE_ERR_HIP;
+    }
   }
   phase_mark(p, 2, stream);
   return LDE_OK;
@@ -2614,208 +2383,140 @@ static int mlp_adjoint_disc(MlpPlan* p, const float* W_dev, const float* z_out, 
 int mlp_adjoint(MlpPlan* p, const float* W_dev, const float* z_out, const float* theta, const double* ts_dev,
                 const KOpts& o, const float* dz_out, float* dz0, float* dtheta, float* dW, int32_t* nfe, int32_t* nacc,
                 int32_t* nrej, int32_t* ret, hipStream_t stream, std::string& err) {
+  using namespace lde_host;
   const MlpDims& dm = p->dm;
-  if (p->disc && !mlp64_applicable(p, o.B))
-    return mlp_adjoint_disc(p, W_dev, z_out, theta, ts_dev, o, dz_out, dz0, dtheta, dW, nfe, nacc, nrej, ret, stream, err);
-  if (mlp64_applicable(p, o.B)) {   // one wave per trajectory, registers only, the weight gradient included (lde_mlp64.h): two launches
-    p->last_family = 1;
-    const int waves = mlp64_adj_waves(o.B);
-    if (!p->rows || p->rows_cap < (size_t)waves * p->rows_stride || p->rows_stride < dm.nW) {
-      err = "MLP adjoint: workspace not reserved";
-      return LDE_ERR_INVALID_ARG;
-    }
-    VArgs va{};
-    va.theta = theta; va.ts = ts_dev; va.Wflat = W_dev; va.z_out = const_cast<float*>(z_out); va.dz_out = dz_out;
-    va.dz0 = dz0; va.dtheta = dtheta; va.stage = p->rows; va.cap = p->rows_stride;
-    va.st_nfe = nfe; va.st_nacc = nacc; va.st_nrej = nrej; va.st_ret = ret;
-    phase_mark(p, 0, stream);
-    if (p->disc && (!o.rec.n || !o.rec.y)) {
-      err = "MLP adjoint (LDE_SENSE_DISCRETE): no step record";
-      return LDE_ERR_INVALID_ARG;
-    }
-    const int rc6 = p->disc ? launch_mlp64<true, true>(dm, o, va, stream, err) : launch_mlp64<true>(dm, o, va, stream, err);
-    if (rc6) return rc6;
-    phase_mark(p, 1, stream);
-    if (dW) {
-      hipLaunchKernelGGL(k_sum_rows, dim3(cdiv(dm.nW, 64)), dim3(1024), 0, stream, p->rows, waves, p->rows_stride, dm.nW, dW, o.dw_overwrite);
-      if (hipGetLastError() != hipSuccess) {
-        err = "k_sum_rows launch failed";
-        return LDE_ERR_HIP;
-      }
-    }
-    phase_mark(p, 2, stream);
-    return LDE_OK;
+  const bool disc = p->sh.disc;   // LDE_SENSE_DISCRETE: the reverse sweep over the forward solve's step record (lde_mlpd.h and the DISC instantiations)
+  if (disc && (!o.rec.n || !o.rec.y)) {
+    err = "MLP adjoint (LDE_SENSE_DISCRETE): no step record";
+    return LDE_ERR_INVALID_ARG;
   }
-  {   // W₂ as register blocks, the weight gradient folded on the CU (lde_mlpb.h): two launches, no staging area
-    const bool ca = dm.coupled && o.adaptive && o.B > 1;
-    const bool use_b = b_applicable(p, o.B, o.T, true, dm.coupled != 0);
-    const bool use_c = !use_b && c_applicable(p, o.B, o.T, true, dm.coupled != 0);
-    if (use_b || use_c) {
-      p->last_family = use_b ? 2 : 3;
-      const int nrows = use_b ? o.B : (o.B + 1) / 2;
-      if (!p->rows || p->rows_cap < (size_t)o.B * p->rows_stride || p->rows_stride < dm.nW) {
-        err = "MLP adjoint: workspace not reserved";
-        return LDE_ERR_INVALID_ARG;
-      }
-      VArgs va{};
-      va.theta = theta; va.ts = ts_dev; va.Wflat = W_dev; va.z_out = const_cast<float*>(z_out); va.dz_out = dz_out;
-      va.dz0 = dz0; va.dtheta = dtheta; va.stage = p->rows; va.cap = p->rows_stride;
-      va.st_nfe = nfe; va.st_nacc = nacc; va.st_nrej = nrej; va.st_ret = ret;
-      va.gs.counter = p->counter; va.gs.slots = p->slots; va.gs.abort_flag = p->abort_flag; va.gs.nwg = ca ? o.B : 1;
-      if (ca && !zero_regions(stream, {{p->counter, sizeof(unsigned)}, {p->abort_flag, sizeof(int)}})) {
-        err = "k_zero_regions(counter) failed";
-        return LDE_ERR_HIP;
-      }
-      const int rca = global_arm(p, va, stream, err);
-      if (rca) return rca;
-      phase_mark(p, 0, stream);
-      int rcb = use_b ? (dm.solver == LDE_SOLVER_RK4 ? launch_b<LDE_SOLVER_RK4, true>(p, o, va, ca, stream, err)
-                                                     : launch_b<LDE_SOLVER_TSIT5, true>(p, o, va, ca, stream, err))
-                      : (dm.solver == LDE_SOLVER_RK4 ? launch_c<LDE_SOLVER_RK4, true>(p, o, va, ca, stream, err)
-                                                     : launch_c<LDE_SOLVER_TSIT5, true>(p, o, va, ca, stream, err));
-      if (!rcb) rcb = global_serve(p, stream, err);
-      if (rcb) return rcb;
-      phase_mark(p, 1, stream);
-      if (dW) {
-        hipLaunchKernelGGL(k_sum_rows, dim3(cdiv(dm.nW, 64)), dim3(1024), 0, stream, p->rows, nrows, p->rows_stride, dm.nW, dW, o.dw_overwrite);
-        if (hipGetLastError() != hipSuccess) {
-          err = "k_sum_rows launch failed";
-          return LDE_ERR_HIP;
-        }
-      }
-      phase_mark(p, 2, stream);
-      return LDE_OK;
-    }
-  }
-  const int nwg = cdiv(o.B, NB);
-  const bool sync = dm.coupled && o.adaptive && nwg > 1;
-  if (sync && nwg > 256) {
-    err = "coupled adaptive solve: batch per GPU limited to 4096 trajectories (one resident workgroup per CU)";
+  Mlp4Dims md;
+  const MlpLds l = mlp_lds_numbers(p, o.B, o.T, true, &md);
+  const char* why = "";
+  const MlpFamily fam = lde_host::mlp_adjoint_mapping(p->sh, p->tune, l, o.B, o.adaptive != 0, &why);
+  if (fam == MLP_NOT_SERVED) {
+    err = why;
     return LDE_ERR_UNSUPPORTED;
   }
-  const size_t fixed = bwd_lds_fixed(dm, o.T, 512);
+  p->last_family = fam;
+  if (mlp_adjoint_rows(fam, o.B) > 0) {
+    VArgs va = args_common<VArgs>(p, theta, ts_dev, W_dev, nfe, nacc, nrej, ret);
+    va.z_out = const_cast<float*>(z_out); va.dz_out = dz_out; va.dz0 = dz0; va.dtheta = dtheta;
+    return rows_adjoint(p, fam, va, o, dW, stream, err);
+  }
+  // the staged families: the solve kernel leaves (a_l, δ_l) panels and their quadrature weights, k_mlp_dw forms the weight gradient
+  const int nwg = cdiv(o.B, NB);
+  const size_t fixed = disc ? disc_lds_fixed(dm, o.T, 512) : bwd_lds_fixed(dm, o.T, 512);
   if (fixed > LDS_MAX) {
-    err = "MLP adjoint: tile state does not fit the 160 KiB LDS";
+    err = disc ? "MLP adjoint (LDE_SENSE_DISCRETE): tile state does not fit the 160 KiB LDS" : "MLP adjoint: tile state does not fit the 160 KiB LDS";
     return LDE_ERR_UNSUPPORTED;
   }
   if (!p->stage || p->adj_cap < 1) {
     err = "MLP adjoint: workspace not reserved";
     return LDE_ERR_INVALID_ARG;
   }
-  const int ks = p->adj_ks;
-  BwdArgs a;
-  a.z_out = z_out; a.dz_out = dz_out; a.theta = theta; a.ts = ts_dev; a.frag = p->frag; a.fragT = p->fragT; a.Wflat = W_dev;
-  a.dz0 = dz0; a.dtheta = dtheta; a.slab = p->slab;
+  BwdArgs a = args_common<BwdArgs>(p, theta, ts_dev, W_dev, nfe, nacc, nrej, ret);
+  a.z_out = z_out; a.dz_out = dz_out; a.frag = p->frag; a.fragT = p->fragT; a.dz0 = dz0; a.dtheta = dtheta; a.slab = p->slab;
   a.stage = p->stage; a.wts = p->wts; a.nslots = p->nslots; a.nflush = p->nslots + (nwg + 1); a.cap = p->adj_cap;
   a.ovf = p->fb_dev + 1; a.fallback = 0;
-  a.st_nfe = nfe; a.st_nacc = nacc; a.st_nrej = nrej; a.st_ret = ret;
-  a.gs.counter = p->counter; a.gs.slots = p->slots; a.gs.abort_flag = p->abort_flag; a.gs.nwg = sync ? nwg : 1;
   const size_t lds = with_cache(fixed, p->nfrag + p->nfragT);
   a.lds_bytes = (int)lds;
-  bool ctl_zeroed = false;   // counter + abort flag of the grid-wide sums: zeroed together with whatever else the first solve kernel needs
+  DwArgs da;
+  da.stage = p->stage; da.wts = p->wts; da.nslots = p->nslots; da.slab = p->slab + (size_t)(nwg + 1) * dm.slab_n; da.cap = p->adj_cap; da.total = 0;
+  if (disc) {   // (the tiles: no step control, no grid-wide sum, no overflow feedback)
+    if (!zero_regions(stream, {{p->fb_dev, 2 * sizeof(int32_t)}, {p->nslots, (size_t)2 * (nwg + 1) * sizeof(int32_t)}})) {
+      err = "k_zero_regions failed";
+      return LDE_ERR_HIP;
+    }
+    int rc = mlp_dispatch(dm.solver, [&](auto S) {
+      const void* fn = (const void*)k_mlp_adjoint_disc<decltype(S)::value, 512>;
+      const int rca = raise_lds_limit(fn, LDS_WHOLE, "k_mlp_adjoint_disc", err);
+      if (rca) return rca;
+      MlpDims dmv = dm;
+      KOpts ov = o;
+      phase_mark(p, 0, stream);
+      return launch_maybe_coop(false, fn, dim3(nwg), dim3(512), lds, stream, err, "k_mlp_adjoint_disc", dmv, ov, a);
+    });
+    if (rc) return rc;
+    phase_mark(p, 1, stream);
+    if (dW) {
+      rc = launch_weight_gradient(dm, da, nwg, p->adj_ks, p->slab, p->nslots + (nwg + 1), nwg, dW, p->fb_dev, stream, err, o.dw_overwrite != 0);
+      if (rc) return rc;
+    }
+    phase_mark(p, 2, stream);
+    return LDE_OK;
+  }
+  const bool sync = dm.coupled && o.adaptive && nwg > 1;   // the tiles' grid-wide sum
+  a.gs.nwg = sync ? nwg : 1;
 #if LDE_PROF
   prof_reset();
 #endif
+  // k_mlpw, k_mlpv and k_mlp4_adjoint run IN FRONT of the tile kernel: a trajectory (a wave) that runs out of staging slots sets *ovf, and
+  // k_mlp_adjoint — which folds its slots into a private slab — then redoes the whole call; otherwise it returns at once. The decision is
+  // taken on the device: the host never waits.
   int ntile_dw = nwg;
-  bool vec_done = false;
-  p->last_family = 0;
-  if (!vec_done) {   // small batches: one trajectory per workgroup, lanes = hidden units (lde_mlpv.h)
-    size_t ldsv = 0;
+  const bool small = fam == MLP_W || fam == MLP_V;   // small batches: a trajectory per workgroup
+  if (small) {
     const bool ca = dm.coupled && o.adaptive && o.B > 1;
-    const bool use_w = w_applicable(p, o.B, o.T, true, ca);
-    if (p->global_mode && !use_w) {
-      err = "LDE_BATCH_COUPLED_GLOBAL: this shape / batch is not served by the register kernels (three Dense layers, 2·D' ≤ 64, H ≤ 200, B·W ≤ 1024 waves)";
-      return LDE_ERR_UNSUPPORTED;
+    if (!zero_regions(stream, {{p->fb_dev, 2 * sizeof(int32_t)}, {p->nslots, (size_t)2 * (nwg + 1) * sizeof(int32_t)},
+                               {p->wts, (size_t)nwg * p->adj_cap * NB * sizeof(float)},
+                               {(ca || sync) ? p->counter : nullptr, sizeof(unsigned)}, {(ca || sync) ? p->abort_flag : nullptr, sizeof(int)}})) {
+      err = "k_zero_regions(staging weights) failed";
+      return LDE_ERR_HIP;
     }
-    if (use_w || vec_applicable(p, o.B, o.T, true, ca, &ldsv, err)) {
-      p->last_family = use_w ? 4 : 5;
-      if (!zero_regions(stream, {{p->fb_dev, 2 * sizeof(int32_t)}, {p->nslots, (size_t)2 * (nwg + 1) * sizeof(int32_t)},
-                                 {p->wts, (size_t)nwg * p->adj_cap * NB * sizeof(float)},
-                                 {(ca || sync) ? p->counter : nullptr, sizeof(unsigned)}, {(ca || sync) ? p->abort_flag : nullptr, sizeof(int)}})) {
-        err = "k_zero_regions(staging weights) failed";
-        return LDE_ERR_HIP;
-      }
-      ctl_zeroed = true;
-      VArgs va{};
-      va.theta = theta; va.ts = ts_dev; va.vecw = p->vecw; va.Wflat = W_dev; va.z_out = const_cast<float*>(z_out); va.dz_out = dz_out;
-      va.dz0 = dz0; va.dtheta = dtheta; va.stage = p->stage; va.wts = p->wts; va.nslots = p->nslots; va.cap = p->adj_cap; va.ovf = p->fb_dev + 1;
-      va.st_nfe = nfe; va.st_nacc = nacc; va.st_nrej = nrej; va.st_ret = ret;
-      va.gs.counter = p->counter; va.gs.slots = p->slots; va.gs.abort_flag = p->abort_flag; va.gs.nwg = ca ? o.B : 1;
-      if (use_w) {
-        const int rca = global_arm(p, va, stream, err);
-        if (rca) return rca;
-      }
-      phase_mark(p, 0, stream);
-      int rcv = use_w ? (dm.solver == LDE_SOLVER_RK4 ? launch_w<LDE_SOLVER_RK4, true>(p, o, va, ca, stream, err)
-                                                     : launch_w<LDE_SOLVER_TSIT5, true>(p, o, va, ca, stream, err))
-                      : (dm.solver == LDE_SOLVER_RK4 ? launch_vec<LDE_SOLVER_RK4, true>(p, o, va, ldsv, ca, stream, err)
-                                                     : launch_vec<LDE_SOLVER_TSIT5, true>(p, o, va, ldsv, ca, stream, err));
-      if (!rcv && use_w) rcv = global_serve(p, stream, err);
-      if (rcv) return rcv;
-      phase_mark(p, 1, stream);
-      // a trajectory that ran out of staging slots sets *ovf: k_mlp_adjoint (which folds its slots into a private slab) then
-      // redoes the whole call; otherwise it returns at once. The decision is taken on the device.
-      vec_done = true;
-      a.fallback = 1;
-      if (sync && hipMemsetAsync(p->counter, 0, sizeof(unsigned), stream) != hipSuccess) {
-        err = "hipMemsetAsync(counter) failed";
-        return LDE_ERR_HIP;
-      }
+    VArgs va = args_common<VArgs>(p, theta, ts_dev, W_dev, nfe, nacc, nrej, ret);
+    va.vecw = p->vecw; va.z_out = const_cast<float*>(z_out); va.dz_out = dz_out; va.dz0 = dz0; va.dtheta = dtheta;
+    va.stage = p->stage; va.wts = p->wts; va.nslots = p->nslots; va.cap = p->adj_cap; va.ovf = p->fb_dev + 1;
+    va.gs.nwg = ca ? o.B : 1;
+    int rcv = fam == MLP_W ? global_arm(p, va, stream, err) : LDE_OK;
+    if (rcv) return rcv;
+    phase_mark(p, 0, stream);
+    rcv = mlp_dispatch(dm.solver, [&](auto S) {
+      constexpr int SV = decltype(S)::value;
+      return fam == MLP_W ? launch_w<SV, true>(p, o, va, ca, stream, err) : launch_vec<SV, true>(p, o, va, ca, stream, err);
+    });
+    if (!rcv && fam == MLP_W) rcv = global_serve(p, stream, err);
+    if (rcv) return rcv;
+    phase_mark(p, 1, stream);
+  } else
+    phase_mark(p, 0, stream);
+  if (fam == MLP_4) {   // networks whose weights fit LDS once: four columns per wave, no barriers
+    const int nblocks = l.mlp4_blocks;
+    const bool sync4 = dm.coupled && o.adaptive && nblocks > 1;
+    ntile_dw = cdiv(nblocks * md.wpb, 4);   // ≤ nwg + 1: the workspace is sized for that
+    if (!zero_regions(stream, {{p->fb_dev, 2 * sizeof(int32_t)}, {p->nslots, (size_t)2 * (nwg + 1) * sizeof(int32_t)},
+                               {p->wts, (size_t)ntile_dw * p->adj_cap * NB * sizeof(float)},
+                               {(sync4 || sync) ? p->counter : nullptr, sizeof(unsigned)}, {(sync4 || sync) ? p->abort_flag : nullptr, sizeof(int)}})) {
+      err = "k_zero_regions(staging weights) failed";
+      return LDE_ERR_HIP;
     }
+    a.gs.nwg = sync4 ? nblocks : 1;
+    int hmaxw = 0;
+    for (int i = 1; i < dm.nL; i++) hmaxw = std::max(hmaxw, dm.sizes[i]);
+    const int rc4 = mlp_dispatch(dm.solver, [&](auto S) {
+      constexpr int SV = decltype(S)::value;
+      return hmaxw <= 64    ? launch_mlp4<SV, 1>(dm, md, o, a, nblocks, l.mlp4, stream, err, sync4)
+             : hmaxw <= 128 ? launch_mlp4<SV, 2>(dm, md, o, a, nblocks, l.mlp4, stream, err, sync4)
+                            : launch_mlp4<SV, 4>(dm, md, o, a, nblocks, l.mlp4, stream, err, sync4);
+    });
+    if (rc4) return rc4;
+    a.gs.nwg = sync ? nwg : 1;
   }
-  if (!vec_done) phase_mark(p, 0, stream);
-  // networks whose weights fit LDS once: four columns per wave, no barriers (lde_mlp4.h)
-  if (!vec_done) {
-    Mlp4Dims md;
-    size_t lds4 = 0;
-    int nblocks = 0;
-    if (mlp4_layout(p->tune, dm, o.T, o.B, dm.coupled && o.adaptive, &md, &lds4, &nblocks)) {
-      const bool sync4 = dm.coupled && o.adaptive && nblocks > 1;
-      p->last_family = 6;
-      const int ntile4 = cdiv(nblocks * md.wpb, 4);   // ≤ nwg + 1: the workspace is sized for that
-      if (!zero_regions(stream, {{p->fb_dev, 2 * sizeof(int32_t)}, {p->nslots, (size_t)2 * (nwg + 1) * sizeof(int32_t)},
-                                 {p->wts, (size_t)ntile4 * p->adj_cap * NB * sizeof(float)},
-                                 {(sync4 || sync) ? p->counter : nullptr, sizeof(unsigned)}, {(sync4 || sync) ? p->abort_flag : nullptr, sizeof(int)}})) {
-        err = "k_zero_regions(staging weights) failed";
-        return LDE_ERR_HIP;
-      }
-      ctl_zeroed = true;
-      a.gs.nwg = sync4 ? nblocks : 1;
-      int hmaxw = 0;
-      for (int l = 1; l < dm.nL; l++) hmaxw = std::max(hmaxw, dm.sizes[l]);
-      const int nth = hmaxw <= 64 ? 1 : (hmaxw <= 128 ? 2 : 4);
-      const bool rk4 = dm.solver == LDE_SOLVER_RK4;
-      int rc4;
-      if (nth == 1) rc4 = rk4 ? launch_mlp4<LDE_SOLVER_RK4, 1>(dm, md, o, a, nblocks, lds4, stream, err, sync4) : launch_mlp4<LDE_SOLVER_TSIT5, 1>(dm, md, o, a, nblocks, lds4, stream, err, sync4);
-      else if (nth == 2) rc4 = rk4 ? launch_mlp4<LDE_SOLVER_RK4, 2>(dm, md, o, a, nblocks, lds4, stream, err, sync4) : launch_mlp4<LDE_SOLVER_TSIT5, 2>(dm, md, o, a, nblocks, lds4, stream, err, sync4);
-      else rc4 = rk4 ? launch_mlp4<LDE_SOLVER_RK4, 4>(dm, md, o, a, nblocks, lds4, stream, err, sync4) : launch_mlp4<LDE_SOLVER_TSIT5, 4>(dm, md, o, a, nblocks, lds4, stream, err, sync4);
-      if (rc4) return rc4;
-      // A wave that ran out of staging slots sets *ovf: k_mlp_adjoint (which can fold its slots into a private slab) then
-      // redoes the whole call; otherwise it returns at once. The host never waits: the decision is taken on the device.
-      ntile_dw = cdiv(nblocks * md.wpb, 4);
-      a.fallback = 1;
-      a.gs.nwg = sync ? nwg : 1;
-      if (sync && hipMemsetAsync(p->counter, 0, sizeof(unsigned), stream) != hipSuccess) {
-        err = "hipMemsetAsync(counter) failed";
-        return LDE_ERR_HIP;
-      }
+  if (fam != MLP_TILES) {   // the tile kernel as the fallback behind one of the three: its control words start from zero again
+    a.fallback = 1;
+    if (sync && hipMemsetAsync(p->counter, 0, sizeof(unsigned), stream) != hipSuccess) {
+      err = "hipMemsetAsync(counter) failed";
+      return LDE_ERR_HIP;
     }
-  }
-  if (sync && !ctl_zeroed && !zero_regions(stream, {{p->counter, sizeof(unsigned)}, {p->abort_flag, sizeof(int)}})) {
-    err = "k_zero_regions(counter) failed";
+  } else if (sync && !zero_grid_sum(p, stream, err))
     return LDE_ERR_HIP;
-  }
-  int rc = dm.solver == LDE_SOLVER_RK4 ? launch_adjoint<LDE_SOLVER_RK4>(p, o, a, nwg, lds, stream, err, sync)
-                                       : launch_adjoint<LDE_SOLVER_TSIT5>(p, o, a, nwg, lds, stream, err, sync);
+  int rc = mlp_dispatch(dm.solver, [&](auto S) { return launch_adjoint<decltype(S)::value>(p, o, a, nwg, lds, stream, err, sync); });
 #if LDE_PROF
   prof_dump("adjoint", stream);
 #endif
   if (rc) return rc;
-  // the weight gradient from the staged panels
-  DwArgs da;
-  da.stage = p->stage; da.wts = p->wts; da.nslots = p->nslots; da.slab = p->slab + (size_t)(nwg + 1) * dm.slab_n; da.cap = p->adj_cap; da.total = 0;
-  if (!vec_done) phase_mark(p, 1, stream);   // (the tile kernels: the solve is the launch above; the small-batch kernels marked theirs already)
-  rc = launch_weight_gradient(dm, da, ntile_dw, ks, p->slab, p->nslots + (nwg + 1), nwg, dW, p->fb_dev, stream, err, o.dw_overwrite != 0);
+  if (!small) phase_mark(p, 1, stream);   // (the solve is the launch above; the small-batch kernels marked theirs already)
+  rc = launch_weight_gradient(dm, da, ntile_dw, p->adj_ks, p->slab, p->nslots + (nwg + 1), nwg, dW, p->fb_dev, stream, err, o.dw_overwrite != 0);
   if (rc) return rc;
   phase_mark(p, 2, stream);
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;

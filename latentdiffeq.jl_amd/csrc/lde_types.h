@@ -2,6 +2,7 @@
 // block handed to every kernel. No HIP in here: csrc/lde_host.h (the C ABI's argument / workspace / record logic) includes this file and
 // is compiled by an ordinary host compiler too — under AddressSanitizer + UBSan in tests/host_logic_driver.cpp.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/lde.h"
@@ -48,6 +49,31 @@ struct MlpTune {
   int mlp4_maxw = 64;         // "mlp4_maxw": widest layer k_mlp4_adjoint takes
   int stage_slots = 0;        // "mlp_stage_slots": staging slots per workgroup (0: automatic)
   int peer_spin_k = 0;        // "peer_spin_k": lde_set_global_sum_peers' cross-rank wait gives up after this many × 1024 polls (0: 8192 ≈ 10 s)
+};
+
+// What the kernel-family choice of the MLP path knows about a plan (csrc/lde_host.h: mlp_forward_mapping / mlp_adjoint_mapping); filled
+// once by mlp_plan_create (csrc/lde_mlp.hip).
+struct MlpShape {
+  int nL = 0, Dp = 0, P = 0;  // Dense layers, state rows D′ = D + augment_dim, per-trajectory parameters
+  int hm = 0;                 // the wider of the two hidden layers of a three-layer network (0: another depth)
+  int maxw = 0;               // the widest layer, input and output included
+  bool coupled = false;       // LDE_BATCH_COUPLED[_GLOBAL]: one step sequence for the batch
+  bool global = false;        // LDE_BATCH_COUPLED_GLOBAL: the batch is sharded over ranks
+  bool disc = false;          // LDE_SENSE_DISCRETE: lde_adjoint sweeps the forward solve's step record
+  bool vec_ok = false, w_ok = false, b_ok = false, c_ok = false;   // the network fits k_mlpv / k_mlpw / k_mlpb / k_mlpc
+  int v_nt = 0;               // k_mlpv: lanes per workgroup (64 / 128 / 256)
+  bool v_reg = false;         // k_mlpv: the hidden×hidden product keeps its weights in registers
+  int w_waves = 0;            // k_mlpw: waves per trajectory (2 / 4)
+};
+// LDS bytes of the candidate families for one (save grid, forward or adjoint), from the formulas beside the kernels whose carve-up they
+// describe (csrc/lde_mlp.hip: mlp_lds_numbers); the mappings only compare them. 0 where the network does not fit the family.
+struct MlpLds {
+  size_t cap = 0;             // what a workgroup can get (LDS_MAX)
+  size_t v_fixed = 0;         // k_mlpv without its weight cache
+  size_t w = 0, b = 0, c = 0; // k_mlpw, k_mlpb, k_mlpc without the cotangent copies
+  size_t b_disc = 0, c_disc = 0;   // the discrete sweeps of k_mlpb (with its cotangent copy) and k_mlpc (with its second slot bank)
+  size_t mlp4 = 0;            // k_mlp4_adjoint
+  int mlp4_blocks = 0;        // … and its workgroups
 };
 
 // Options handed to every kernel by value (mirrors the `kwargs...` splat into solve()).

@@ -100,6 +100,13 @@ class Native:
     def set_option(self, key, value):
         L.check(self.lib.lde_set_option(self.h, key.encode(), float(value)), self.h, "lde_set_option")
 
+    def adjoint_family(self):
+        """The MLP kernel family the last lde_adjoint ran (option "adjoint_family": 0 tiles, 1 k_mlp64, 2 k_mlpb, 3 k_mlpc, 4 k_mlpw, 5 k_mlpv,
+        6 k_mlp4_adjoint; −1: none)."""
+        v = C.c_double(-2.0)
+        L.check(self.lib.lde_get_option(self.h, b"adjoint_family", C.byref(v)), self.h, "lde_get_option")
+        return int(v.value)
+
     def step_record(self, which, B, cap=None):
         """Host copy of the last call's step sequences as the oracle's `rec` dict: t, dt [nseq, cap], n [nseq]."""
         nseq = B if self.d.batching == L.BATCH_PER_TRAJECTORY else 1

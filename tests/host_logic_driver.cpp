@@ -250,7 +250,234 @@ int main() {
       assert(!called || (validate(&d, &why) == LDE_OK && has_pend(d) && !has_mlp(d)));
     }
   }
+  // 8. which kernel family serves the MLP right-hand sides (csrc/lde_mlp.hip's launch code switches on this). Expected values: the constants
+  //    of the predicates this mapping replaced (mlp64_applicable, vec_applicable, w_applicable, b_applicable, c_applicable, disc_family,
+  //    mlp4_layout), in their order of precedence.
+  {
+    const int RK = LDE_SOLVER_RK4, PT = LDE_BATCH_PER_TRAJECTORY, CO = LDE_BATCH_COUPLED, GL = LDE_BATCH_COUPLED_GLOBAL;
+    const int CONT = LDE_SENSE_BACKSOLVE_CHECKPOINTED, DISC = LDE_SENSE_DISCRETE;
+    auto net = [&](std::vector<int> layers, int batching, int sense, int kind = LDE_RHS_MLP, int solver = LDE_SOLVER_TSIT5) {
+      lde_problem_desc d = good();
+      d.rhs_kind = kind; d.batching = batching; d.sensealg = sense; d.solver = solver;
+      if (solver == LDE_SOLVER_RK4) { d.adaptive = 0; d.dt = 0.05; }
+      if (kind == LDE_RHS_MLP) { d.state_dim = layers[0]; d.param_dim = 0; }
+      d.n_layers = (int)layers.size() - 1;
+      for (size_t i = 0; i < layers.size(); i++) d.layer_sizes[i] = layers[i];
+      assert(validate(&d, &why) == LDE_OK);
+      return mlp_shape(d);
+    };
+    const size_t CAP = 160 * 1024;
+    auto roomy = [&](int B) {   // LDS that never binds; k_mlp4_adjoint's workgroups as its layout counts them
+      lde::MlpLds l;
+      l.cap = CAP;
+      l.v_fixed = l.w = l.b = l.c = l.b_disc = l.c_disc = l.mlp4 = 4096;
+      const int nwaves = (B + 3) / 4, wpb = std::max(1, std::min(4, (nwaves + 255) / 256));
+      l.mlp4_blocks = (nwaves + wpb - 1) / wpb;
+      return l;
+    };
+    const lde::MlpTune def;
+    auto fwd = [&](const lde::MlpShape& s, const lde::MlpTune& tn, int B, bool ad, bool rec = false) { return mlp_forward_mapping(s, tn, roomy(B), B, ad, rec); };
+    auto adj = [&](const lde::MlpShape& s, const lde::MlpTune& tn, int B, bool ad) { return mlp_adjoint_mapping(s, tn, roomy(B), B, ad); };
+    // the values option "adjoint_family" reports
+    static_assert(MLP_TILES == 0 && MLP_64 == 1 && MLP_B == 2 && MLP_C == 3 && MLP_W == 4 && MLP_V == 5 && MLP_4 == 6 && MLP_NOT_SERVED == 7, "adjoint_family");
+
+    // the shapes' summaries
+    const lde::MlpShape c2 = net({8, 200, 200, 8}, CO, CONT, LDE_RHS_MLP, RK), c3 = net({2, 64, 64, 2}, PT, CONT, LDE_RHS_PENDULUM_PLUS_MLP);
+    const lde::MlpShape c4 = net({32, 128, 128, 32}, CO, CONT), ref = net({16, 200, 200, 16}, CO, CONT), c4pt = net({32, 128, 128, 32}, PT, CONT);
+    assert(c2.b_ok && c2.w_ok && !c2.c_ok && c2.vec_ok && c2.v_nt == 256 && !c2.v_reg && c2.w_waves == 4 && c2.hm == 200 && c2.maxw == 200);
+    assert(!c3.b_ok && !c3.w_ok && !c3.c_ok && c3.vec_ok && c3.v_nt == 64 && c3.v_reg && c3.P == 1 && c3.Dp == 2);
+    assert(!c4.b_ok && c4.w_ok && c4.c_ok && c4.v_nt == 256 && c4.v_reg && c4.w_waves == 2 && !c4pt.c_ok && c4pt.w_ok);
+    assert(ref.b_ok && ref.w_ok && !ref.c_ok && ref.v_nt == 256 && !ref.v_reg);
+    assert(net({6, 40, 24, 40, 6}, PT, CONT).v_nt == 64 && !net({6, 40, 24, 40, 6}, PT, CONT).v_reg && !net({6, 40, 24, 40, 6}, PT, CONT).w_ok);
+    assert(net({6, 100, 24, 100, 6}, PT, CONT).v_nt == 128 && net({8, 16, 16, 8}, PT, CONT).v_nt == 64 && !net({8, 16, 16, 8}, PT, CONT).v_reg);
+    assert(net({8, 17, 16, 8}, PT, CONT).v_reg && net({8, 129, 16, 8}, PT, CONT).v_nt == 256 && !net({8, 129, 16, 8}, PT, CONT).v_reg);
+    assert(!net({8, 300, 16, 8}, PT, CONT).vec_ok && !net({8, 201, 16, 8}, PT, CONT).w_ok && net({33, 64, 64, 33}, CO, CONT).vec_ok && !net({33, 64, 64, 33}, CO, CONT).c_ok);
+    assert(net({17, 64, 64, 17}, CO, CONT).c_ok && !net({17, 64, 64, 17}, CO, CONT).b_ok && !net({8, 129, 128, 8}, CO, CONT).c_ok && net({8, 128, 128, 8}, CO, CONT).c_ok);
+
+    // the five bench shapes: c2 B = 256, c3 B = 1024, c4 B = 512 and 4096, the reference NODE B = 64 — forward and adjoint
+    assert(fwd(c2, def, 256, false) == MLP_B && adj(c2, def, 256, false) == MLP_B);
+    assert(fwd(c3, def, 1024, true) == MLP_64 && adj(c3, def, 1024, true) == MLP_64);
+    assert(fwd(c4, def, 512, true) == MLP_C && adj(c4, def, 512, true) == MLP_C);
+    assert(fwd(c4, def, 4096, true) == MLP_TILES && adj(c4, def, 4096, true) == MLP_TILES);
+    assert(fwd(ref, def, 64, true) == MLP_B && adj(ref, def, 64, true) == MLP_B);
+
+    // k_mlp64: B ≤ 65 536, per-trajectory control only, hidden layers ≤ 64, D′ ≤ 4; beyond, c3 falls to the tiles (forward) / k_mlp4_adjoint
+    assert(fwd(c3, def, 65536, true) == MLP_64 && fwd(c3, def, 65537, true) == MLP_TILES && adj(c3, def, 65536, true) == MLP_64 && adj(c3, def, 65537, true) == MLP_4);
+    assert(fwd(net({4, 64, 64, 4}, PT, CONT), def, 100, true) == MLP_64 && fwd(net({5, 64, 64, 5}, PT, CONT), def, 100, true) != MLP_64);
+    assert(fwd(net({4, 65, 64, 4}, PT, CONT), def, 100, true) != MLP_64 && fwd(net({4, 64, 64, 4}, CO, CONT), def, 100, true) != MLP_64);
+    assert(fwd(net({4, 64, 64, 64, 4}, PT, CONT), def, 100, true) != MLP_64);
+    lde::MlpTune t = def;
+    t.mlp64 = 0;
+    // k_mlpv: B·NT/64 ≤ 1024, twice that with the register-resident hidden layer (c3: NT = 64 → 2048; c4: 256 → 512; deep: 64, plain → 1024)
+    assert(fwd(c3, t, 2048, true) == MLP_V && fwd(c3, t, 2049, true) == MLP_TILES && adj(c3, t, 2048, true) == MLP_V && adj(c3, t, 2049, true) == MLP_4);
+    const lde::MlpShape deep = net({6, 40, 24, 40, 6}, PT, CONT), deep128 = net({6, 100, 24, 100, 6}, PT, CONT);
+    assert(adj(deep, def, 1024, true) == MLP_V && adj(deep, def, 1025, true) == MLP_4 && fwd(deep, def, 1024, true) == MLP_V && fwd(deep, def, 1025, true) == MLP_TILES);
+    assert(adj(deep128, def, 512, true) == MLP_V && adj(deep128, def, 513, true) == MLP_TILES);
+    t = def; t.mlpv = 0;
+    assert(adj(deep, t, 100, true) == MLP_4 && fwd(deep, t, 100, true) == MLP_TILES);
+
+    // k_mlpb: 512 trajectories, 256 when they must all be resident — the forward: coupled AND adaptive AND B > 1; the continuous adjoint: coupled
+    assert(fwd(c2, def, 512, false) == MLP_B && fwd(c2, def, 513, false) == MLP_TILES);                  // (fixed step: the forward may queue)
+    assert(adj(c2, def, 257, false) == MLP_W && adj(c2, def, 512, false) == MLP_W && adj(c2, def, 513, false) == MLP_TILES);
+    assert(fwd(c2, def, 300, false) == MLP_B && adj(c2, def, 300, false) == MLP_W);                      // the split at B = 300: forward k_mlpb, adjoint k_mlpw
+    assert(fwd(ref, def, 256, true) == MLP_B && fwd(ref, def, 257, true) == MLP_TILES && adj(ref, def, 256, true) == MLP_B && adj(ref, def, 257, true) == MLP_TILES);
+    const lde::MlpShape c2pt = net({8, 200, 200, 8}, PT, CONT);
+    assert(fwd(c2pt, def, 512, true) == MLP_B && adj(c2pt, def, 512, true) == MLP_B && adj(c2pt, def, 513, true) == MLP_TILES);
+    // "mlpb": 0 = k_mlpw instead, 1 = networks wider than 128 only, 2 = the narrower ones too
+    const lde::MlpShape h70 = net({8, 70, 65, 8}, PT, CONT);
+    assert(adj(h70, def, 26, true) == MLP_W && fwd(h70, def, 26, true) == MLP_W);
+    t = def; t.mlpb = 2;
+    assert(adj(h70, t, 26, true) == MLP_B && adj(h70, t, 512, true) == MLP_B && adj(h70, t, 513, true) == MLP_W);
+    t.mlpb = 0;
+    assert(adj(h70, t, 26, true) == MLP_W && adj(c2, t, 256, false) == MLP_W && fwd(c2, t, 256, false) == MLP_W && adj(c4, t, 512, true) == MLP_W);
+    // "mlpw" = 0 switches k_mlpw, k_mlpb AND k_mlpc off
+    t = def; t.mlpw = 0;
+    assert(adj(c2, t, 256, false) == MLP_V && fwd(c2, t, 256, false) == MLP_V && adj(c2, t, 257, false) == MLP_TILES && adj(c4, t, 512, true) == MLP_V && adj(ref, t, 64, true) == MLP_V);
+    assert(adj(c4, t, 513, true) == MLP_TILES && fwd(c4, t, 512, true) == MLP_V && fwd(c4, t, 513, true) == MLP_TILES);   // (register-resident layer at NT = 256: 2048·64/256)
+    t.mlpv = 0; t.mlp64 = 0;   // the tests' "tiles" leg
+    assert(adj(c2, t, 48, false) == MLP_TILES && adj(c3, t, 80, true) == MLP_4 && adj(c4, t, 40, true) == MLP_TILES && fwd(c3, t, 80, true) == MLP_TILES);
+
+    // k_mlpc: 1024 trajectories, 512 resident (the same two readings of "coupled")
+    assert(fwd(c4, def, 513, true) == MLP_TILES && adj(c4, def, 513, true) == MLP_TILES && fwd(c4, def, 1, true) == MLP_C);
+    assert(fwd(c4, def, 1024, false) == MLP_C && fwd(c4, def, 1025, false) == MLP_TILES);                // (coupled, fixed step)
+    assert(adj(c4, def, 512, false) == MLP_C && adj(c4, def, 513, false) == MLP_W && adj(c4, def, 1024, false) == MLP_W && adj(c4, def, 1025, false) == MLP_TILES);
+    // k_mlpw: 2048 waves, 1024 resident (W = 2 up to 128 units, 4 beyond)
+    assert(adj(c4pt, def, 1024, true) == MLP_W && adj(c4pt, def, 1025, true) == MLP_TILES && fwd(c4pt, def, 1024, true) == MLP_W);
+    t = def; t.mlpb = 0;
+    assert(fwd(c4, t, 512, true) == MLP_W && fwd(c4, t, 513, true) == MLP_TILES && fwd(ref, t, 256, true) == MLP_W && fwd(ref, t, 257, true) == MLP_TILES);
+    assert(fwd(c2, t, 512, false) == MLP_W && fwd(c2, t, 513, false) == MLP_TILES);
+
+    // a forward that writes a step record: never k_mlpw / k_mlpv; k_mlp64, k_mlpb, k_mlpc and the tiles write it
+    assert(fwd(c4pt, def, 512, true, true) == MLP_TILES && fwd(deep, def, 100, true, true) == MLP_TILES && fwd(h70, def, 26, true, true) == MLP_TILES);
+    assert(fwd(c3, def, 1024, true, true) == MLP_64 && fwd(c2, def, 256, false, true) == MLP_B && fwd(c4, def, 512, true, true) == MLP_C);
+
+    // k_mlp4_adjoint: layers up to "mlp4_maxw" (64) and 256 wide, D′ ≤ 64, P ≤ 1; coupled adaptive: at most 256 workgroups
+    const lde::MlpShape n48 = net({4, 48, 33, 4}, PT, CONT);
+    t = def; t.mlp64 = 0; t.mlpv = 0; t.mlpw = 0;
+    assert(adj(n48, t, 37, true) == MLP_4);
+    t.mlp4_maxw = 47;
+    assert(adj(n48, t, 37, true) == MLP_TILES);
+    t.mlp4_maxw = 48;
+    assert(adj(n48, t, 37, true) == MLP_4);
+    t.mlp4 = 0;
+    assert(adj(n48, t, 37, true) == MLP_TILES);
+    t.mlp4 = 1; t.mlp4_maxw = 1 << 20;
+    assert(adj(c2, t, 48, false) == MLP_4 && adj(net({8, 257, 16, 8}, PT, CONT), t, 48, true) == MLP_TILES && adj(net({65, 70, 16, 65}, PT, CONT), t, 48, true) == MLP_TILES);
+    {
+      lde::MlpShape p2 = n48;
+      p2.P = 2;
+      assert(adj(p2, t, 37, true) == MLP_TILES);
+      lde::MlpLds l = roomy(64);
+      const lde::MlpShape co48 = net({4, 48, 33, 4}, CO, CONT);
+      l.mlp4_blocks = 256;
+      assert(mlp_adjoint_mapping(co48, t, l, 64, true) == MLP_4);
+      l.mlp4_blocks = 257;
+      assert(mlp_adjoint_mapping(co48, t, l, 64, true) == MLP_TILES && mlp_adjoint_mapping(co48, t, l, 64, false) == MLP_4 && mlp_adjoint_mapping(n48, t, l, 64, true) == MLP_4);
+      l.mlp4 = CAP + 1;
+      assert(mlp_adjoint_mapping(n48, t, l, 64, true) == MLP_TILES);
+    }
+
+    // LDE_SENSE_DISCRETE: k_mlp64 first, then k_mlpb up to 1024 and k_mlpc up to 2048 trajectories (coupled or not, adaptive or not), else the tiles
+    const lde::MlpShape c2d = net({8, 200, 200, 8}, CO, DISC, LDE_RHS_MLP, RK), c3d = net({2, 64, 64, 2}, PT, DISC, LDE_RHS_PENDULUM_PLUS_MLP), c4d = net({32, 128, 128, 32}, CO, DISC);
+    assert(c2d.disc && adj(c3d, def, 1024, true) == MLP_64 && adj(c3d, def, 65537, true) == MLP_TILES);
+    assert(adj(c2d, def, 256, false) == MLP_B && adj(c2d, def, 1024, false) == MLP_B && adj(c2d, def, 1025, false) == MLP_TILES);
+    assert(adj(c4d, def, 512, true) == MLP_C && adj(c4d, def, 2048, true) == MLP_C && adj(c4d, def, 2049, true) == MLP_TILES && adj(c4d, def, 5000, true) == MLP_TILES);
+    assert(adj(net({8, 200, 200, 8}, PT, DISC), def, 1024, true) == MLP_B && adj(net({16, 200, 200, 16}, CO, DISC), def, 64, true) == MLP_B);
+    t = def; t.mlpb = 0;
+    assert(adj(c2d, t, 256, false) == MLP_TILES && adj(c4d, t, 512, true) == MLP_TILES);
+    t = def; t.mlpw = 0;
+    assert(adj(c2d, t, 256, false) == MLP_TILES && adj(c4d, t, 512, true) == MLP_TILES);
+
+    // the two refusals, and which comes first
+    const char* msg = nullptr;
+    assert(fwd(c4, def, 4096, true) == MLP_TILES && mlp_forward_mapping(c4, def, roomy(4097), 4097, true, false, &msg) == MLP_NOT_SERVED && std::strstr(msg, "4096 trajectories"));
+    msg = nullptr;
+    assert(mlp_adjoint_mapping(c4, def, roomy(4097), 4097, true, &msg) == MLP_NOT_SERVED && std::strstr(msg, "4096 trajectories") && adj(c4, def, 4097, false) == MLP_TILES);
+    const lde::MlpShape c4g = net({32, 128, 128, 32}, GL, CONT), c4gd = net({32, 128, 128, 32}, GL, DISC);
+    assert(c4g.global && c4g.coupled && fwd(c4g, def, 512, true) == MLP_C && adj(c4g, def, 512, true) == MLP_C);
+    msg = nullptr;
+    assert(mlp_forward_mapping(c4g, def, roomy(513), 513, true, false, &msg) == MLP_NOT_SERVED && std::strstr(msg, "LDE_BATCH_COUPLED_GLOBAL"));
+    msg = nullptr;
+    assert(mlp_adjoint_mapping(c4g, def, roomy(513), 513, true, &msg) == MLP_NOT_SERVED && std::strstr(msg, "LDE_BATCH_COUPLED_GLOBAL"));
+    assert(mlp_forward_mapping(c4g, def, roomy(5000), 5000, true, false, &msg) == MLP_NOT_SERVED && std::strstr(msg, "LDE_BATCH_COUPLED_GLOBAL"));
+    assert(mlp_adjoint_mapping(c4g, def, roomy(5000), 5000, true, &msg) == MLP_NOT_SERVED && std::strstr(msg, "4096 trajectories"));
+    assert(adj(c4gd, def, 2049, true) == MLP_TILES);   // the discrete sweep exchanges nothing: nothing to refuse
+
+    // the LDS comparisons: k_mlpw shares a CU's LDS between 4 / W workgroups, k_mlpv takes at most half of it and — resident — its CU's share
+    {
+      lde::MlpLds l = roomy(512);
+      l.c = CAP + 1;
+      assert(mlp_forward_mapping(c4, def, l, 512, true, false) == MLP_W);
+      l.w = CAP * 2 / 4;
+      assert(mlp_forward_mapping(c4, def, l, 512, true, false) == MLP_W);
+      l.w += 1;
+      assert(mlp_forward_mapping(c4, def, l, 512, true, false) == MLP_V);
+      l.v_fixed = CAP / 2 - 256;   // two workgroups per CU: half the LDS less 256 bytes each
+      assert(mlpv_lds_budget(CAP, 512) == CAP / 2 - 256 && mlpv_lds_budget(CAP, 256) == CAP && mlp_forward_mapping(c4, def, l, 512, true, false) == MLP_V);
+      l.v_fixed += 1;
+      assert(mlp_forward_mapping(c4, def, l, 512, true, false) == MLP_TILES && mlp_forward_mapping(c4, def, l, 512, false, false) == MLP_V);
+      l.v_fixed = CAP / 2 + 1;
+      assert(mlp_forward_mapping(c4, def, l, 512, false, false) == MLP_TILES);
+      l = roomy(256);
+      l.b = CAP + 1;
+      assert(mlp_adjoint_mapping(c2, def, l, 256, false) == MLP_W && mlp_adjoint_mapping(c2d, def, l, 256, false) == MLP_TILES);
+      l = roomy(256);
+      l.b_disc = CAP + 1;
+      assert(mlp_adjoint_mapping(c2d, def, l, 256, false) == MLP_TILES && mlp_adjoint_mapping(c2, def, l, 256, false) == MLP_B);
+      l = roomy(512);
+      l.c_disc = CAP + 1;
+      assert(mlp_adjoint_mapping(c4d, def, l, 512, true) == MLP_TILES && mlp_adjoint_mapping(c4, def, l, 512, true) == MLP_C);
+    }
+
+    // the adjoint's workspace: rows of the weight gradient for k_mlp64 (a row per workgroup of four waves, at most 256), k_mlpb (a row per
+    // trajectory) and k_mlpc (a row per pair; sized per trajectory), the staging area (0 rows) for everything else
+    assert(mlp64_adj_waves(1) == 1 && mlp64_adj_waves(4) == 1 && mlp64_adj_waves(5) == 2 && mlp64_adj_waves(1024) == 256 && mlp64_adj_waves(1 << 20) == 256);
+    auto reserve = [&](const lde::MlpShape& s, int B) { return mlp_reserved_rows(adj(s, def, B, false), B); };   // as lde_reserve asks
+    assert(reserve(c3, 1024) == 256 && mlp_adjoint_rows(MLP_64, 100) == 25 && reserve(c3d, 100) == 25);
+    assert(reserve(c2, 256) == 256 && mlp_adjoint_rows(MLP_B, 256) == 256 && reserve(c2, 300) == 0);
+    assert(reserve(c4, 511) == 511 && mlp_adjoint_rows(MLP_C, 511) == 256 && reserve(c4d, 2048) == 2048);
+    assert(mlp_reserved_rows(MLP_TILES, 64) == 0 && mlp_reserved_rows(MLP_W, 64) == 0 && mlp_reserved_rows(MLP_V, 64) == 0 && mlp_reserved_rows(MLP_4, 64) == 0 && mlp_reserved_rows(MLP_NOT_SERVED, 64) == 0);
+    assert(mlp_adjoint_rows(MLP_TILES, 64) == 0 && mlp_adjoint_rows(MLP_W, 64) == 0 && mlp_adjoint_rows(MLP_V, 64) == 0 && mlp_adjoint_rows(MLP_4, 64) == 0);
+
+    // ANY shape, knobs, LDS numbers and batch: one of the enum's values (the forward never k_mlp4_adjoint), and lde_reserve — which does not
+    // know whether the call will be adaptive — sizes at least the rows the adjoint's family writes
+    for (int it = 0; it < 100000; it++) {
+      lde::MlpShape s;
+      lde::MlpTune h;
+      lde::MlpLds l;
+      s.nL = (rnd() & 1) ? 3 : hostile_int(); s.Dp = hostile_int(); s.P = hostile_int(); s.hm = hostile_int(); s.maxw = hostile_int();
+      s.coupled = rnd() & 1; s.global = rnd() & 1; s.disc = rnd() & 1; s.vec_ok = rnd() & 1; s.w_ok = rnd() & 1; s.b_ok = rnd() & 1; s.c_ok = rnd() & 1;
+      s.v_nt = (rnd() & 1) ? 64 << (rnd() % 3) : hostile_int(); s.v_reg = rnd() & 1; s.w_waves = (rnd() & 1) ? 2 + 2 * (int)(rnd() & 1) : hostile_int();
+      h.mlp64 = (int)(rnd() % 2); h.mlpv = (int)(rnd() % 2); h.mlpw = (int)(rnd() % 2); h.mlp4 = (int)(rnd() % 2); h.mlpb = (int)(rnd() % 3); h.mlp4_maxw = hostile_int();
+      auto bytes = [&]() { return (rnd() & 1) ? (size_t)(rnd() % (2 * CAP)) : (size_t)rnd(); };
+      l.cap = (rnd() & 3) ? CAP : bytes();
+      l.v_fixed = bytes(); l.w = bytes(); l.b = bytes(); l.c = bytes(); l.b_disc = bytes(); l.c_disc = bytes(); l.mlp4 = bytes(); l.mlp4_blocks = hostile_int();
+      const int B = (rnd() & 1) ? 1 + (int)(rnd() % 5000) : hostile_int();
+      const MlpFamily f = mlp_forward_mapping(s, h, l, B, rnd() & 1, rnd() & 1);
+      assert(f >= MLP_TILES && f <= MLP_NOT_SERVED && f != MLP_4);
+      for (int ad = 0; ad < 2; ad++) {
+        const MlpFamily a = mlp_adjoint_mapping(s, h, l, B, ad != 0);
+        assert(a >= MLP_TILES && a <= MLP_NOT_SERVED);
+        const int rows = mlp_adjoint_rows(a, B);   // the call's family writes them; lde_reserve asked with adaptive = false
+        if (rows > 0) assert(mlp_reserved_rows(mlp_adjoint_mapping(s, h, l, B, false), B) >= rows);
+      }
+    }
+  }
+  // 9. the MLP kernels' template argument: the two solvers validate() admits reach the kernels, nothing else
+  {
+    int seen[2] = {0, 0};
+    auto rec = [&](auto S) -> int { seen[decltype(S)::value]++; return 10 + decltype(S)::value; };
+    static_assert(LDE_SOLVER_TSIT5 == 0 && LDE_SOLVER_RK4 == 1, "solver codes");
+    assert(mlp_dispatch(LDE_SOLVER_TSIT5, rec) == 10 && mlp_dispatch(LDE_SOLVER_RK4, rec) == 11 && seen[0] == 1 && seen[1] == 1);
+    assert(mlp_dispatch(2, rec) == LDE_ERR_UNSUPPORTED && mlp_dispatch(-1, rec) == LDE_ERR_UNSUPPORTED && seen[0] == 1 && seen[1] == 1);
+    for (int it = 0; it < 20000; it++) {
+      const int solver = hostile_int();
+      int called = 0;
+      const int rc = mlp_dispatch(solver, [&](auto) -> int { called++; return LDE_OK; });
+      assert(called == (solver == LDE_SOLVER_TSIT5 || solver == LDE_SOLVER_RK4) && rc == (called ? LDE_OK : LDE_ERR_UNSUPPORTED));
+    }
+  }
   std::printf("host logic under ASan + UBSan: %d accepted, %d refused hostile descriptions; forward mappings as measured; "
-              "pullback mappings, ring shapes and kernel dispatch checked\n", n_ok, n_bad);
+              "pullback mappings, ring shapes and kernel dispatch checked; MLP family mappings as measured, reserve rows and solver dispatch checked\n", n_ok, n_bad);
   return 0;
 }

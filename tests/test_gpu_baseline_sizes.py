@@ -17,6 +17,12 @@ pytestmark = pytest.mark.gpu
 NT = max(1, min(64, (os.cpu_count() or 2) // 2))
 
 
+# The kernel family (option "adjoint_family": 0 tiles, 1 k_mlp64, 2 k_mlpb, 3 k_mlpc) the adjoint of each BASELINE shape runs — literal
+# expectations, recorded on the MI355X from the commit before the choice moved into lde_host::mlp_adjoint_mapping, not taken from the
+# mapping's output
+FAMILY = {"c2_256": 2, "c3_1024": 1, "c4_512": 3, "c4_4096": 0, "ref_64": 2}
+
+
 def _native(W, **kw):
     from tests.gpu_util import Native, make_desc, copy_desc_to_oracle
     d = make_desc(**kw)
@@ -47,6 +53,7 @@ def test_c3_full_batch_1024(o32, o64):
     z, ret, st = nat.forward(z0, L, ts)
     g0, gL, gW, sb = nat.adjoint(z, L, ts, dz)
     assert (ret == 0).all() and st["nfailed"] == 0 and sb["nfailed"] == 0
+    assert nat.adjoint_family() == FAMILY["c3_1024"]
     zr, retr, info = o32.forward(od, z0, L, ts, W=W, nthreads=NT)
     r0, rL, rW, infob = o32.adjoint(od, z, L, ts, dz, W=W, nthreads=NT)
     per_traj = np.abs(z - zr).max(axis=(0, 2))
@@ -88,6 +95,7 @@ def test_c2_adjoint_full_batch_256(o32, o64):
     dz = O.cotangent(T, B, 8)
     z, _, st = nat.forward(z0, None, ts)
     g0, _, gW, sb = nat.adjoint(z, None, ts, dz)
+    assert nat.adjoint_family() == FAMILY["c2_256"]
     zr, _, _ = o32.forward(od, z0, None, ts, W=W, nthreads=NT)
     r0, _, rW, info = o32.adjoint(od, z, None, ts, dz, W=W, nthreads=NT)
     assert sb["naccept"] == info["naccept"] == 49 and sb["nfailed"] == 0
@@ -120,6 +128,7 @@ def test_c4_coupled_full_batches(o32, B):
     z, ret, st = nat.forward(z0, None, ts)
     g0, _, gW, sb = nat.adjoint(z, None, ts, dz)
     assert (ret == 0).all() and st["nfailed"] == 0 and sb["nfailed"] == 0
+    assert nat.adjoint_family() == FAMILY[f"c4_{B}"]
     zr, _, info = o32.forward(od, z0, None, ts, W=W, nthreads=NT)
     r0, _, rW, infob = o32.adjoint(od, z, None, ts, dz, W=W, nthreads=NT)
     assert abs(st["naccept"] - info["naccept"]) <= 0.1 * info["naccept"] + 2
@@ -172,6 +181,7 @@ def test_reference_default_latentode_b64(o32, o64):
     z, ret, st = nat.forward(z0, None, ts)
     g0, _, gW, sb = nat.adjoint(z, None, ts, dz)
     assert (ret == 0).all() and st["nfailed"] == 0 and sb["nfailed"] == 0
+    assert nat.adjoint_family() == FAMILY["ref_64"]
     zr, _, info = o32.forward(od, z0, None, ts, W=W, nthreads=NT)
     r0, _, rW, infob = o32.adjoint(od, z, None, ts, dz, W=W, nthreads=NT)
     assert abs(st["naccept"] - info["naccept"]) <= 0.1 * info["naccept"] + 2

@@ -524,16 +524,37 @@ def test_one_mlp_handle_changing_shapes(o32, layers, batching, solver):
         assert e0 <= 2e-3 and eW <= 2e-3, (T, B, e0, eW)
 
 
+# test_kernel_families_agree: the family (option "adjoint_family") each leg's adjoint runs — literal expectations, recorded on the MI355X from
+# the commit before the choice moved into lde_host::mlp_adjoint_mapping (its predicates in lde_mlp.hip), not taken from the mapping's output
+FAMILIES_RAN = {
+    "c2_rk4_coupled": dict(new=2, mlpw=4, tiles=0, mlpv=5),
+    "c3_per_traj": dict(new=1, mlpw=1, tiles=6, mlpv=5),
+    "c4_coupled": dict(new=3, mlpw=4, tiles=0, mlpv=5),
+    "tanh_per_traj_4d": dict(new=1, mlpw=1, tiles=6, mlpv=5),
+    "rk4_per_traj_small": dict(new=1, mlpw=1, tiles=6, mlpv=5),
+    "deep_4_layers": dict(new=5, mlpw=5, tiles=6, mlpv=5),
+    "tsit5_d12_h150_coupled": dict(new=2, mlpw=4, tiles=0, mlpv=5),
+    "rk4_d20_h96_per_traj": dict(new=4, mlpw=4, tiles=0, mlpv=5),
+    "tanh_d8_h70_aug": dict(new=4, mlpw=4, tiles=0, mlpv=5),
+    "tanh_d8_h70_backsolve": dict(new=4, mlpw=4, tiles=0, mlpv=5),
+    "relu_d32_h128_long_grid": dict(new=4, mlpw=4, tiles=0, mlpv=5),
+}
+
+
 @pytest.mark.parametrize("case", ["c2_rk4_coupled", "c3_per_traj", "c4_coupled", "tanh_per_traj_4d", "rk4_per_traj_small", "deep_4_layers",
                                   "tsit5_d12_h150_coupled", "rk4_d20_h96_per_traj", "tanh_d8_h70_aug", "tanh_d8_h70_backsolve",
                                   "relu_d32_h128_long_grid"])
 def test_kernel_families_agree(case, o64):
-    """Four kernel families serve the MLP right-hand sides: 16-column MFMA tiles (large batches; options "mlpv" = "mlp64" = "mlpw" = 0
-    force them), one trajectory per workgroup with lanes = hidden units (k_mlpv; "mlp64" = "mlpw" = 0), one wave per trajectory
-    with everything in registers (k_mlp64: three layers ≤ 64 wide, D' ≤ 4, per-trajectory control) and W waves per trajectory with
-    weights and state in registers (k_mlpw: three layers ≤ 200 wide, D' ≤ 32). Same algorithm, same control arithmetic: they
-    agree like two correct f32 solves — round-off for fixed steps and smooth networks at tight tolerance, the solver's own error
-    where a relu network meets the adaptive controller — and every family is no farther from the float64 adjoint than that."""
+    """Seven kernel families serve the MLP right-hand sides (option "adjoint_family" says which one an lde_adjoint ran): the staged ones
+    behind options "mlpv" = "mlp64" = "mlpw" = 0 — the 16-column MFMA tiles (0), or, for networks at most 64 wide, four columns per wave
+    in front of them (6: k_mlp4_adjoint) —, one trajectory per workgroup with lanes = hidden units (5: k_mlpv; "mlp64" = "mlpw" = 0), one
+    wave per trajectory with everything in registers (1: k_mlp64: three layers ≤ 64 wide, D' ≤ 4, per-trajectory control), W waves per
+    trajectory with weights and state in registers (4: k_mlpw: three layers ≤ 200 wide, D' ≤ 32; the default where k_mlpb / k_mlpc do
+    not serve, and their parity reference behind "mlpb" = 0), W₂ as register blocks with the weight gradient folded on the CU (2: k_mlpb)
+    and two trajectories per workgroup (3: k_mlpc). Same algorithm, same control arithmetic: they agree like two correct f32 solves —
+    round-off for fixed steps and smooth networks at tight tolerance, the solver's own error where a relu network meets the adaptive
+    controller — and every family is no farther from the float64 adjoint than that. Each leg must have RUN the family it is named for
+    (FAMILIES_RAN: a leg whose option stopped working would otherwise compare a kernel with itself)."""
     cfg = {
         "c2_rk4_coupled": dict(layers=(8, 200, 200, 8), B=48, kw=dict(rhs_kind=O.RHS_MLP, state_dim=8, param_dim=0, solver=O.SOLVER_RK4, adaptive=0, dt=0.05, batching=O.BATCH_COUPLED), lim=5e-6),
         "c3_per_traj": dict(layers=(2, 64, 64, 2), B=80, kw=dict(rhs_kind=O.RHS_PENDULUM_PLUS_MLP), lim=1e-2),
@@ -567,7 +588,11 @@ def test_kernel_families_agree(case, o64):
         z, ret, st = nat.forward(z0, L, ts)
         g0, gL, gW, sb = nat.adjoint(z, L, ts, dz)
         assert (ret == 0).all() and sb["nfailed"] == 0
+        ran = nat.adjoint_family()
+        assert ran == FAMILIES_RAN[case][fam], (fam, ran)
+        assert {"mlpv": ran == 5, "mlpw": ran not in (2, 3), "tiles": ran in (0, 6), "new": 0 <= ran <= 6}[fam], (fam, ran)
         res[fam] = (z, g0, gL, gW)
+    assert {f_ for row in FAMILIES_RAN.values() for f_ in row.values()} == set(range(7))   # across the cases every family runs
     rel = lambda a, b: np.abs(a - b).max() / max(np.abs(b).max(), 1e-30)
     for fam in ("new", "mlpw", "mlpv"):
         z, g0, gL, gW = res[fam]

@@ -2,7 +2,7 @@
 not available on this pool): (1) the oracle — everything the parity tests trust — driven at small, ragged, degenerate and failing shapes
 through every family of its entry points (oracle/asan_driver.c, f32 and f64 builds); (2) the C ABI's host-side logic — validation of a
 problem description, the weight count, the step-record layout arithmetic, the option block, grid checks, the analytic path's kernel
-choices (csrc/lde_host.h, which lde_api.hip and the launch code are built from) — with 200 000 hostile descriptions (tests/host_logic_driver.cpp)."""
+choices and the MLP path's kernel families (csrc/lde_host.h, which lde_api.hip and the launch code are built from) — with 200 000 hostile descriptions (tests/host_logic_driver.cpp)."""
 import os
 import shutil
 import subprocess
@@ -37,6 +37,7 @@ def test_c_abi_host_logic_under_asan_ubsan(tmp_path):
     _clean(r)
     assert "accepted" in r.stdout and "forward mappings as measured" in r.stdout
     assert "pullback mappings, ring shapes and kernel dispatch checked" in r.stdout
+    assert "MLP family mappings as measured, reserve rows and solver dispatch checked" in r.stdout
 
 
 def test_lde_api_is_built_from_the_checked_logic():
@@ -50,5 +51,10 @@ def test_lde_api_is_built_from_the_checked_logic():
     assert "tn." not in pend and "24576" not in pend   # no PendTune field read and no pullback threshold outside lde_host.h
     for s in (pend, dual):   # the (rhs_kind, solver, adaptive) → template-argument chain lives in lde_host::pend_dispatch only
         assert "lde_host::pend_dispatch(" in s and "#define LDE_LAUNCH" not in s
+    # the MLP path likewise: the family choice and every threshold live in lde_host.h's two mappings, the launch code switches on their result
+    mlp = open(os.path.join(ROOT, "latentdiffeq.jl_amd", "csrc", "lde_mlp.hip")).read()
+    assert "lde_host::mlp_forward_mapping(" in mlp and "lde_host::mlp_adjoint_mapping(" in mlp
+    for gone in ("_applicable(", "attr_set", "65536", "tune.mlp64", "tune.mlpv", "tune.mlpw", "tune.mlpb", "tune.mlp4"):
+        assert gone not in mlp, gone
     for fn in ("static int validate(", "static size_t rec_bytes(", "static lde::StepRec rec_view(", "static lde::KOpts make_opts("):
         assert fn not in src, fn
