@@ -21,6 +21,8 @@
 //    adjoint — `k_mlp_dw` + `k_reduce_tiles` from lde_mfma.h, with every 16-column group as one slot of weight 1.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "lde_host.h"
 #include "lde_mfma.h"
 
 namespace lde {
@@ -117,7 +120,7 @@ __device__ __forceinline__ float cact_grad_out(int kind, float f) {
 // One wave: NT_ (1 or 2) 16-row tiles × NCG column groups, all K-groups, software-pipelined: A fragments (global/L2) run
 // PFA K-groups ahead in a register ring, B operands PFB ahead; pre() is called before the K loop (its loads overlap the
 // MFMAs), epi() after. Per K-group NT_ fragment loads + NCG operand loads feed 4·NT_·NCG MFMAs.
-template <int NT_, int NCG, bool BGLB, bool BF, class Pre, class Epi>
+template <int NT_, int NCG, bool BGLB, class Pre, class Epi>
 __device__ __forceinline__ void chain_mac(const f32x4* A0, const f32x4* A1, const float* bp, int cgstride, int KG, int row_a,
                                           int row_b, int cg0, int col, Pre pre, Epi epi) {
   constexpr int PFA = 4, PFB = BGLB ? 4 : 2;
@@ -159,22 +162,12 @@ __device__ __forceinline__ void chain_mac(const f32x4* A0, const f32x4* A1, cons
         if (NT_ == 2) ra1[i] = A1[ka * 64];
 #pragma unroll
         for (int cg = 0; cg < NCG; cg++) rb[i % PFB][cg] = *reinterpret_cast<const f32x4*>(bp + (cg0 + cg) * cgstride + kb * 16);
-        if (BF) {   // bf16 operands: one 16x16x16 MFMA per (row tile, column group) and K-group
-          const s16x4 a0 = cvt_bf16x4(c0), a1 = cvt_bf16x4(c1);
+#pragma unroll
+        for (int s4 = 0; s4 < 4; s4++) {   // K-step outer: 2·NCG independent accumulators between two uses of the same one
 #pragma unroll
           for (int cg = 0; cg < NCG; cg++) {
-            const s16x4 b4 = cvt_bf16x4(cb[cg]);
-            acc0[cg] = mfma16_bf(a0, b4, acc0[cg]);
-            if (NT_ == 2) acc1[cg] = mfma16_bf(a1, b4, acc1[cg]);
-          }
-        } else {
-#pragma unroll
-          for (int s4 = 0; s4 < 4; s4++) {   // K-step outer: 2·NCG independent accumulators between two uses of the same one
-#pragma unroll
-            for (int cg = 0; cg < NCG; cg++) {
-              acc0[cg] = mfma16(c0[s4], cb[cg][s4], acc0[cg]);
-              if (NT_ == 2) acc1[cg] = mfma16(c1[s4], cb[cg][s4], acc1[cg]);
-            }
+            acc0[cg] = mfma16(c0[s4], cb[cg][s4], acc0[cg]);
+            if (NT_ == 2) acc1[cg] = mfma16(c1[s4], cb[cg][s4], acc1[cg]);
           }
         }
       }
@@ -192,7 +185,7 @@ __device__ __forceinline__ void chain_mac(const f32x4* A0, const f32x4* A1, cons
 // Row tiles are dealt 16 at a time (a wave takes tiles rt and rt+8 together); 9–15 left-over tiles make one more such
 // pass, exactly 8 a single-tile pass, and fewer than 8 are dealt as (tile, column group) units so that the last pass
 // still uses every wave (49 tiles of the 784-row layer: 3 passes + 1/8 instead of 4).
-template <int CG, bool BGLB, bool BF, class Pre, class Epi>
+template <int CG, bool BGLB, class Pre, class Epi>
 __device__ __forceinline__ void chain_gemm(const float* __restrict__ gfrag, int R, int K, const float* Bp, int ldb,
                                            int cgstride, Pre pre, Epi epi) {
   constexpr int NW = 8;
@@ -205,25 +198,25 @@ __device__ __forceinline__ void chain_gemm(const float* __restrict__ gfrag, int 
   int base = 0;
   for (; base + 2 * NW <= RT; base += 2 * NW) {
     const int rt = base + wave, rt2 = rt + NW;
-    chain_mac<2, CG, BGLB, BF>(A + (size_t)rt * KG * 64, A + (size_t)rt2 * KG * 64, bp, cgstride, KG, rt * 16 + rsub,
-                           rt2 * 16 + rsub, 0, col, pre, epi);
+    chain_mac<2, CG, BGLB>(A + (size_t)rt * KG * 64, A + (size_t)rt2 * KG * 64, bp, cgstride, KG, rt * 16 + rsub,
+                       rt2 * 16 + rsub, 0, col, pre, epi);
   }
   if (RT - base > NW) {   // 9–15 tiles left: one more double pass; a wave without a second tile repeats its first
     const int rt = base + wave, rt2 = rt + NW;
     const bool two = rt2 < RT;
-    chain_mac<2, CG, BGLB, BF>(A + (size_t)rt * KG * 64, A + (size_t)(two ? rt2 : rt) * KG * 64, bp, cgstride, KG,
-                           rt * 16 + rsub, two ? rt2 * 16 + rsub : -1, 0, col, pre, epi);
+    chain_mac<2, CG, BGLB>(A + (size_t)rt * KG * 64, A + (size_t)(two ? rt2 : rt) * KG * 64, bp, cgstride, KG,
+                       rt * 16 + rsub, two ? rt2 * 16 + rsub : -1, 0, col, pre, epi);
     return;
   }
   if (RT - base == NW) {
     const int rt = base + wave;
-    chain_mac<1, CG, BGLB, BF>(A + (size_t)rt * KG * 64, nullptr, bp, cgstride, KG, rt * 16 + rsub, 0, 0, col, pre, epi);
+    chain_mac<1, CG, BGLB>(A + (size_t)rt * KG * 64, nullptr, bp, cgstride, KG, rt * 16 + rsub, 0, 0, col, pre, epi);
     return;
   }
   const int units = (RT - base) * CG;
   for (int u = wave; u < units; u += NW) {
     const int rt = base + u / CG, cg = u % CG;
-    chain_mac<1, 1, BGLB, BF>(A + (size_t)rt * KG * 64, nullptr, bp, cgstride, KG, rt * 16 + rsub, 0, cg, col, pre, epi);
+    chain_mac<1, 1, BGLB>(A + (size_t)rt * KG * 64, nullptr, bp, cgstride, KG, rt * 16 + rsub, 0, cg, col, pre, epi);
   }
 }
 
@@ -298,7 +291,7 @@ __device__ __forceinline__ long long chain_tile_start(const ChainDims& cd, int N
 // about one unit in 10⁷, which a test with 3·10⁵ columns caught as a 3 % error in one column's gradient.)
 struct SaveTo { float* base; long long n0, N; };   // base == nullptr: nothing is saved
 
-template <int CG, bool BF, bool BG = false>
+template <int CG, bool BG = false>
 __device__ __forceinline__ void chain_hidden_layer(const ChainDims& cd, int l, const float* frag, const float* biasc,
                                                    const float* Xin, int ldx, float* Y, float* fstage = nullptr,
                                                    SaveTo sv = SaveTo{nullptr, 0, 0}) {
@@ -306,7 +299,7 @@ __device__ __forceinline__ void chain_hidden_layer(const ChainDims& cd, int l, c
   const int in = dm.sizes[l], out = dm.sizes[l + 1], actk = cd.act[l], skip = BG ? 0 : cd.skip[l], ldh = cd.ldh;
   const float* bias = biasc + dm.bias_lin[l];
   const int out32 = pad32(out);
-  chain_gemm<CG, BG, BF>(frag + dm.frag_off[l], out, in, Xin, ldx, 16 * ldx, [](int, int, int) { return NoPre{}; },
+  chain_gemm<CG, BG>(frag + dm.frag_off[l], out, in, Xin, ldx, 16 * ldx, [](int, int, int) { return NoPre{}; },
                         [&](int row0, int cg, int col, f32x4 v, NoPre) {
                           const int c = cg * 16 + col;
                           f32x4 r = v;
@@ -336,7 +329,7 @@ __device__ __forceinline__ void chain_hidden_layer(const ChainDims& cd, int l, c
 }
 
 constexpr int F32_OCC = 1;   // waves per SIMD of the f32 chain kernels' launch bounds
-template <int CG, bool BF>
+template <int CG>
 __device__ __forceinline__ void chain_forward_body(const ChainDims& cd, const ChainFwdArgs& a, const unsigned bx) {
   extern __shared__ __attribute__((aligned(16))) float csm[];
   constexpr int NC = 16 * CG;
@@ -359,8 +352,8 @@ __device__ __forceinline__ void chain_forward_body(const ChainDims& cd, const Ch
     float* Y = (l & 1) ? H1 : H0;
     PROF_T(pl0);
     const SaveTo sv{a.saved, n0, a.N};
-    if (l == 0 && cd.gx) chain_hidden_layer<CG, BF, true>(cd, 0, a.frag, biasc, xg, dm.sizes[0], Y, nullptr, sv);
-    else chain_hidden_layer<CG, BF>(cd, l, a.frag, biasc, Xin, ldx, Y, nullptr, sv);
+    if (l == 0 && cd.gx) chain_hidden_layer<CG, true>(cd, 0, a.frag, biasc, xg, dm.sizes[0], Y, nullptr, sv);
+    else chain_hidden_layer<CG>(cd, l, a.frag, biasc, Xin, ldx, Y, nullptr, sv);
     PROF_T(pl1);
     __syncthreads();
     PROF_T(pl2);
@@ -409,8 +402,8 @@ __device__ __forceinline__ void chain_forward_body(const ChainDims& cd, const Ch
                             }
                           };
     auto nopre = [](int, int, int) { return NoPre{}; };
-    if (nL == 1 && cd.gx) chain_gemm<CG, true, BF>(a.frag + dm.frag_off[l], out, in, xg, in, 16 * in, nopre, epi_last);
-    else chain_gemm<CG, false, BF>(a.frag + dm.frag_off[l], out, in, Xin, ldx, 16 * ldx, nopre, epi_last);
+    if (nL == 1 && cd.gx) chain_gemm<CG, true>(a.frag + dm.frag_off[l], out, in, xg, in, 16 * in, nopre, epi_last);
+    else chain_gemm<CG, false>(a.frag + dm.frag_off[l], out, in, Xin, ldx, 16 * ldx, nopre, epi_last);
     if (a.mse_t) {
       const float t = chain_wg_sum(msum, csm);   // (the panels are free behind the barrier inside)
       if (threadIdx.x == 0) a.mse_part[bx] = t;
@@ -420,14 +413,14 @@ __device__ __forceinline__ void chain_forward_body(const ChainDims& cd, const Ch
   PROF_ADD(2 + 2 * (nL - 1), pz0, pz1);
   PROF_ADD(40, pc0, pz1);
 }
-template <int CG, bool BF>
+template <int CG>
 __global__ void __launch_bounds__(512, (CG <= 2 ? F32_OCC : 1)) k_chain_forward(ChainDims cd, ChainFwdArgs a) {
-  chain_forward_body<CG, BF>(cd, a, blockIdx.x);
+  chain_forward_body<CG>(cd, a, blockIdx.x);
 }
-template <int CG, bool BF>
+template <int CG>
 __global__ void __launch_bounds__(512, (CG <= 2 ? F32_OCC : 1)) k_chain_forward_group(GroupTable<ChainDims, ChainFwdArgs> g) {
   const int j = group_find(g.start, g.n, blockIdx.x);
-  chain_forward_body<CG, BF>(g.dims[j], g.args[j], blockIdx.x - g.start[j]);
+  chain_forward_body<CG>(g.dims[j], g.args[j], blockIdx.x - g.start[j]);
 }
 
 struct ChainBwdArgs {
@@ -451,7 +444,7 @@ struct ChainBwdArgs {
 
 struct PrePair { f32x4 h, a; };
 
-template <int CG, bool BF>
+template <int CG>
 __device__ __forceinline__ void chain_backward_body(const ChainDims& cd, const ChainBwdArgs& a, const unsigned bx) {
   extern __shared__ __attribute__((aligned(16))) float csm[];
   constexpr int NC = 16 * CG;
@@ -520,8 +513,8 @@ __device__ __forceinline__ void chain_backward_body(const ChainDims& cd, const C
     int ldx = cd.ld0;
     for (int l = 0; l + 1 < nL; l++) {
       float* Y = (l & 1) ? P1 : P0;
-      if (l == 0 && cd.gx) chain_hidden_layer<CG, BF, true>(cd, 0, a.frag, biasc, xg, dm.sizes[0], Y);
-      else chain_hidden_layer<CG, BF>(cd, l, a.frag, biasc, Xin, ldx, Y, cd.skip[l] ? blk0 + cd.f_off[l] : nullptr);
+      if (l == 0 && cd.gx) chain_hidden_layer<CG, true>(cd, 0, a.frag, biasc, xg, dm.sizes[0], Y);
+      else chain_hidden_layer<CG>(cd, l, a.frag, biasc, Xin, ldx, Y, cd.skip[l] ? blk0 + cd.f_off[l] : nullptr);
       __syncthreads();
 #pragma unroll
       for (int cg = 0; cg < CG; cg++)
@@ -609,8 +602,8 @@ __device__ __forceinline__ void chain_backward_body(const ChainDims& cd, const C
         for (int q = 0; q < 4; q++) d[q] = row0 + q < in ? g[q] * d[q] : 0.f;
         *reinterpret_cast<f32x4*>(Dn + c * ldh + row0) = d;
       };
-      if (l == L1) chain_gemm<CG, true, BF>(fragT, in, out, Bglb, pad32(out), dm.blk_floats, pre, epi);
-      else chain_gemm<CG, false, BF>(fragT, in, out, Dcur, ldh, 16 * ldh, pre, epi);
+      if (l == L1) chain_gemm<CG, true>(fragT, in, out, Bglb, pad32(out), dm.blk_floats, pre, epi);
+      else chain_gemm<CG, false>(fragT, in, out, Dcur, ldh, 16 * ldh, pre, epi);
       __syncthreads();
 #pragma unroll
       for (int cg = 0; cg < CG; cg++)
@@ -629,19 +622,19 @@ __device__ __forceinline__ void chain_backward_body(const ChainDims& cd, const C
             if (row0 + q < in) a.dx[(size_t)n * in + row0 + q] = g[q];
         }
       };
-      if (l == L1) chain_gemm<CG, true, BF>(fragT, in, out, Bglb, pad32(out), dm.blk_floats, pre, epi);
-      else chain_gemm<CG, false, BF>(fragT, in, out, Dcur, ldh, 16 * ldh, pre, epi);
+      if (l == L1) chain_gemm<CG, true>(fragT, in, out, Bglb, pad32(out), dm.blk_floats, pre, epi);
+      else chain_gemm<CG, false>(fragT, in, out, Dcur, ldh, 16 * ldh, pre, epi);
     }
   }
 }
-template <int CG, bool BF>
+template <int CG>
 __global__ void __launch_bounds__(512, (CG <= 2 ? F32_OCC : 1)) k_chain_backward(ChainDims cd, ChainBwdArgs a) {
-  chain_backward_body<CG, BF>(cd, a, blockIdx.x);
+  chain_backward_body<CG>(cd, a, blockIdx.x);
 }
-template <int CG, bool BF>
+template <int CG>
 __global__ void __launch_bounds__(512, (CG <= 2 ? F32_OCC : 1)) k_chain_backward_group(GroupTable<ChainDims, ChainBwdArgs> g) {
   const int j = group_find(g.start, g.n, blockIdx.x);
-  chain_backward_body<CG, BF>(g.dims[j], g.args[j], blockIdx.x - g.start[j]);
+  chain_backward_body<CG>(g.dims[j], g.args[j], blockIdx.x - g.start[j]);
 }
 
 #include "lde_chain_bf16.h"
@@ -672,18 +665,16 @@ struct lde_chain {
   float* fragT = nullptr;
   MlpDims* dm_dev = nullptr;   // device copy of cd.dm (lde_refresh_weights' job table points at it)
   bool have_W = false;
-  int cg_fwd = 0, cg_bwd = 0;
-  size_t lds_fwd = 0, lds_bwd = 0;
+  int cg_fwd = 0, cg_bwd = 0;  // column groups per tile (lde_host::chain_tile_pick; 0: the panels do not fit)
   ChainDims cdx;               // the panel-free layout for wide inputs (gx), when applicable
   int cgx_fwd = 0, cgx_bwd = 0;
   int opt_group = 1;        // lde_chain_set_option "group": this chain may take part in a merged (one launch per stage) grouped call
   int opt_async_dw = 1;     // lde_chain_set_option "async_dw": this chain's weight-gradient kernels go to the dw stream when one is set (lde_set_dw_stream)
-  size_t ldsx_fwd = 0, ldsx_bwd = 0;
   // backward workspace
   float* stage = nullptr; size_t stage_cap = 0;
   float* wts = nullptr; size_t wts_cap = 0;
   float* slab = nullptr; size_t slab_cap = 0;
-  int32_t* ints = nullptr; size_t ints_cap = 0;   // zero words for the slab reduction: [0] "no private slabs", [2..3] feedback sink
+  int32_t* ints = nullptr;     // zero words for the slab reduction: [0] "no private slabs", [2..3] feedback sink
   DwSync dws;                  // weight-gradient kernels on the dw stream (lde_set_dw_stream)
   std::string err;
 };
@@ -699,18 +690,13 @@ static int chain_desc_ok(const lde_chain_desc* d) {
   return 1;
 }
 
-static size_t chain_lds(const ChainDims& cd, int cg, int npanels) {
-  const int NC = 16 * cg;
-  return ((size_t)NC * cd.ld0 + (size_t)npanels * NC * cd.ldh + ((cd.dm.nbias + 3) & ~3)) * sizeof(float);
-}
-
-// native bf16 path: LDS bytes of the forward (two bf16 panels + input panel + biases) and pullback (two bf16 panels + the f32
-// skip-gradient panel) kernels
-static size_t chain_lds_b(const ChainDims& cd, const BfDims& bd, int cg, bool bwd) {
-  const size_t NC = 16 * cg;
-  if (bwd) return NC * bd.ldb * 2 * 2 + NC * bd.ldg * 4;
-  return (2 + (bd.fpanel ? 1 : 0)) * NC * bd.ldb * 2 + (size_t)((cd.dm.nbias + 3) & ~3) * 4   // the input panel shares the second panel's space
-         + (cd.gx ? chain_xs_bytes(cg) : 0);                                 // wide input: the first layer's chunk buffers
+// what lde_host's LDS formulas read of a layout (the wide input's chunk buffers grow linearly with the column groups)
+static ChainLdsDims chain_lds_dims(const ChainDims& cd, const BfDims& bd) {
+  ChainLdsDims q;
+  q.ld0 = cd.ld0; q.ldh = cd.ldh; q.nbias = cd.dm.nbias;
+  q.ldb = bd.ldb; q.ldg = bd.ldg; q.fpanel = bd.fpanel;
+  q.xs_per_cg = cd.gx ? chain_xs_bytes(1) : 0;
+  return q;
 }
 
 // lde_loss.hip: out[0] = (base ? base[0] : 0) + scale·Σ scratch[0..g) in index order (k_loss_final)
@@ -796,35 +782,6 @@ int lde_chain_create(const lde_chain_desc* d, lde_chain** out) {
       c->err = "chain layer widths up to 1024 are supported";
       return LDE_ERR_UNSUPPORTED;
     }
-  // Column groups per workgroup: the widest tile that still lets TWO workgroups share a CU (≤ 80 KB of LDS each) — one
-  // tile's barrier / prologue latencies are then covered by the other's MFMAs. Measured on the reconstructor
-  // (N = 12800): forward 64 columns 110 µs, 32 columns 107 µs; backward 32 columns 331 µs, 16 columns 313 µs.
-  // Falls back to the widest tile that fits at all.
-  auto pick = [&](const ChainDims& q, int* cgf, size_t* ldf, int* cgb, size_t* ldb) {
-    *cgf = *cgb = 0;
-    for (size_t lim : {LDS_MAX / 2, LDS_MAX}) {
-      for (int cg : {4, 2, 1}) {
-        if (!*cgf && chain_lds(q, cg, 2) <= lim) { *cgf = cg; *ldf = chain_lds(q, cg, 2); }
-        if (cg <= 2 && !*cgb && chain_lds(q, cg, 3) <= lim) { *cgb = cg; *ldb = chain_lds(q, cg, 3); }
-      }
-    }
-  };
-  pick(cd, &c->cg_fwd, &c->lds_fwd, &c->cg_bwd, &c->lds_bwd);
-  // wide inputs (an image encoder's first layer): x itself is the B operand of layer 0, no input panel
-  c->cdx = cd;
-  if (dm.sizes[0] % 16 == 0 && dm.sizes[0] >= 128 && !cd.skip[0]) {   // (lde_chain_set_option "gx" = 0 takes the layout away again: tests)
-    c->cdx.gx = 1;
-    c->cdx.ld0 = 0;
-    pick(c->cdx, &c->cgx_fwd, &c->ldsx_fwd, &c->cgx_bwd, &c->ldsx_bwd);
-  }
-  if (!c->cg_fwd || !c->cg_bwd) {
-    if (c->cgx_fwd && c->cgx_bwd) {   // only the panel-free layout fits: it needs N ≥ one tile (checked per call)
-      c->cg_fwd = c->cg_bwd = 0;
-    } else {
-      c->err = "chain: activation panels do not fit the 160 KiB LDS";
-      return LDE_ERR_UNSUPPORTED;
-    }
-  }
   {   // native bf16 layouts (lde_chain_bf16.h)
     BfDims& bd = c->bd;
     std::memset(&bd, 0, sizeof(bd));
@@ -842,19 +799,30 @@ int lde_chain_create(const lde_chain_desc* d, lde_chain** out) {
     c->bdx = bd;
     c->bdx.ldb = panel_stride_b(pad32(hmax));   // wide input read in place: the panels only hold hidden vectors
     c->bdx.ld0 = 0;
-    // 32-column tiles (CG = 2): ≤ 128 registers and ≤ 80 KB of LDS, so two workgroups share a CU (lde_chain_bf16.h: BF_PFA / BF_OCC);
-    // (a 64-column forward instantiation exists; it is only picked when nothing narrower fits)
-    auto pickb = [&](const ChainDims& q, const BfDims& b, int* cgf, int* cgb) {
-      *cgf = *cgb = 0;
-      for (size_t lim : {LDS_MAX / 2, LDS_MAX}) {
-        for (int cg : {2, 1}) {
-          if (!*cgf && chain_lds_b(q, b, cg, false) <= lim) *cgf = cg;
-          if (!*cgb && chain_lds_b(q, b, cg, true) <= lim) *cgb = cg;
-        }
-      }
-    };
-    pickb(cd, bd, &c->bcg_fwd, &c->bcg_bwd);
-    if (c->cdx.gx) pickb(c->cdx, c->bdx, &c->bcgx_fwd, &c->bcgx_bwd);
+  }
+  // column groups per workgroup of the four kernels (lde_host::chain_tile_pick), for the layout with an input panel …
+  auto pick = [](const ChainDims& q, const BfDims& b, int* cgf, int* cgb, int* bcgf, int* bcgb) {
+    const ChainLdsDims L = chain_lds_dims(q, b);
+    *cgf = lde_host::chain_tile_pick(L, false, false, LDS_MAX);
+    *cgb = lde_host::chain_tile_pick(L, false, true, LDS_MAX);
+    *bcgf = lde_host::chain_tile_pick(L, true, false, LDS_MAX);
+    *bcgb = lde_host::chain_tile_pick(L, true, true, LDS_MAX);
+  };
+  pick(cd, c->bd, &c->cg_fwd, &c->cg_bwd, &c->bcg_fwd, &c->bcg_bwd);
+  // … and for wide inputs (an image encoder's first layer): x itself is the B operand of layer 0, no input panel
+  c->cdx = cd;
+  if (dm.sizes[0] % 16 == 0 && dm.sizes[0] >= 128 && !cd.skip[0]) {   // (lde_chain_set_option "gx" = 0 takes the layout away again: tests)
+    c->cdx.gx = 1;
+    c->cdx.ld0 = 0;
+    pick(c->cdx, c->bdx, &c->cgx_fwd, &c->cgx_bwd, &c->bcgx_fwd, &c->bcgx_bwd);
+  }
+  if (!c->cg_fwd || !c->cg_bwd) {
+    if (c->cgx_fwd && c->cgx_bwd) {   // only the panel-free layout fits: it needs N ≥ one tile (checked per call)
+      c->cg_fwd = c->cg_bwd = 0;
+    } else {
+      c->err = "chain: activation panels do not fit the 160 KiB LDS";
+      return LDE_ERR_UNSUPPORTED;
+    }
   }
   size_t nfb = 0, nfTb = 0;
   for (int l = 0; l < d->n_layers; l++) { nfb += bf_frag_elems(dm, l, false); nfTb += bf_frag_elems(dm, l, true); }
@@ -971,85 +939,47 @@ int lde_refresh_weights(int n, const int* kinds, void* const* handles, const flo
   return LDE_OK;
 }
 
-// which layout a call uses: the panel-free one (gx) when the input is wide, x is 16-byte aligned and N fills a tile
-struct ChainPick { const ChainDims* cd; int cg; size_t lds; };
+// The layout and tile width of one call, in the handle's current dtype (lde_host::chain_call_choice), and the kernel's LDS bytes
+struct ChainPick { const ChainDims* cd; const BfDims* bd; int cg; size_t lds; };
 static bool chain_pick(const lde_chain* c, const float* x, int64_t N, bool bwd, ChainPick* p) {
-  const int cgx = bwd ? c->cgx_bwd : c->cgx_fwd, cg = bwd ? c->cg_bwd : c->cg_fwd;
-  // Mid-size batches (a training step's N = B·T ≈ 3 200 columns): the widest tile leaves most CUs without a workgroup —
-  // 50–100 tiles on 256 CUs — and a tile's time barely depends on its width (the weight fragments stream through the
-  // workgroup either way). Narrow the tile until the grid has ≈ 200 workgroups (measured, GOKU training step at B = 64:
-  // 1.70 → 1.32 ms and 2.17 → 1.84 ms in two back-to-back pairs; at B = 256 the grids are full and nothing changes).
-  auto narrow = [&](const ChainDims& q, int cg0, size_t lds0) {
-    int g = cg0;
-    while (g > 1 && (N + 16 * g - 1) / (16 * g) < 192) g /= 2;
-    return ChainPick{&q, g, g == cg0 ? lds0 : chain_lds(q, g, bwd ? 3 : 2)};
-  };
-  if (cgx && N >= 16 * cgx && (((uintptr_t)x) & 15) == 0) {
-    *p = narrow(c->cdx, cgx, bwd ? c->ldsx_bwd : c->ldsx_fwd);
-    return true;
-  }
-  if (!cg) return false;
-  *p = narrow(c->cd, cg, bwd ? c->lds_bwd : c->lds_fwd);
+  const int cgx = c->bf16 ? (bwd ? c->bcgx_bwd : c->bcgx_fwd) : (bwd ? c->cgx_bwd : c->cgx_fwd);
+  const int cg = c->bf16 ? (bwd ? c->bcg_bwd : c->bcg_fwd) : (bwd ? c->cg_bwd : c->cg_fwd);
+  const lde_host::ChainChoice ch = lde_host::chain_call_choice(cgx, cg, N, (((uintptr_t)x) & 15) == 0);
+  if (ch.layout == lde_host::CHAIN_NONE) return false;
+  const bool gx = ch.layout == lde_host::CHAIN_GX;
+  *p = ChainPick{gx ? &c->cdx : &c->cd, gx ? &c->bdx : &c->bd, ch.cg, 0};
+  p->lds = lde_host::chain_lds_bytes(chain_lds_dims(*p->cd, *p->bd), c->bf16, bwd, ch.cg);
   return true;
 }
 
-// virtual tiling of the slot range for k_mlp_dw: (virtual tiles × jobs) ≈ one workgroup per CU — the kernel's register
-// footprint allows one resident workgroup per CU, so 256 equal shares beat 384 (a second, half-empty round)
-static void chain_dw_split(const lde_chain* c, int cg_bwd, int64_t N, int* nvt, int* cap, int64_t* total) {
-  const int64_t tiles = (N + 16 * cg_bwd - 1) / (16 * cg_bwd);
-  *total = tiles * cg_bwd;
-  int v = 256 / dw_jobs(c->cd.dm, dw_pick_ndw(c->cd.dm));
-  if (v < 1) v = 1;
-  if (*total < v) v = (int)*total;
-  *nvt = v;
-  *cap = (int)((*total + v - 1) / v);
-  if (*cap < 1) *cap = 1;
-}
-
-int lde_chain_reserve(lde_chain* c, int64_t N) {
-  if (!c || !c->W_dev || N < 1) return LDE_ERR_INVALID_ARG;
-  int nvt, cap;
-  int64_t total;
-  chain_dw_split(c, 2, N, &nvt, &cap, &total);   // 2 column groups per tile rounds the slot count up the most
-  const MlpDims& dm = c->cd.dm;
-  if (!grow(&c->stage, &c->stage_cap, (size_t)total * dm.blk_floats) || !grow(&c->wts, &c->wts_cap, (size_t)total * NB) ||
-      !grow(&c->slab, &c->slab_cap, ((size_t)nvt + 1) * dm.slab_n)) {
+// two words the slab reduction reads as "no private slabs" / writes its feedback to: zero, once
+static int chain_zero_words(lde_chain* c) {
+  if (c->ints) return LDE_OK;
+  if (hipMalloc(&c->ints, 64) != hipSuccess || hipMemset(c->ints, 0, 64) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
     c->err = "chain: hipMalloc of the backward workspace failed";
     return LDE_ERR_ALLOC;
-  }
-  if (!c->ints) {   // two words the slab reduction reads as "no private slabs" / writes its feedback to: zero, once
-    if (hipMalloc(&c->ints, 64) != hipSuccess || hipMemset(c->ints, 0, 64) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
-      c->err = "chain: hipMalloc of the backward workspace failed";
-      return LDE_ERR_ALLOC;
-    }
-    c->ints_cap = 16;
   }
   return LDE_OK;
 }
 
-// ---- the native bf16 path (lde_chain_bf16.h) ------------------------------------------------------------------------------------
-struct ChainPickB { const ChainDims* cd; const BfDims* bd; int cg; size_t lds; };
-static bool chain_pick_b(const lde_chain* c, const float* x, int64_t N, bool bwd, ChainPickB* p) {
-  const int cgx = bwd ? c->bcgx_bwd : c->bcgx_fwd, cg = bwd ? c->bcg_bwd : c->bcg_fwd;
-  auto narrow = [&](const ChainDims& q, const BfDims& b, int cg0) {
-    int g = cg0;
-    while (g > 1 && (N + 16 * g - 1) / (16 * g) < 192) g /= 2;
-    return ChainPickB{&q, &b, g, chain_lds_b(q, b, g, bwd)};
-  };
-  if (c->cdx.gx && cgx && N >= 16 * cgx && (((uintptr_t)x) & 15) == 0) {
-    *p = narrow(c->cdx, c->bdx, cgx);
-    return true;
+int lde_chain_reserve(lde_chain* c, int64_t N) {
+  if (!c || !c->W_dev || N < 1) return LDE_ERR_INVALID_ARG;
+  const MlpDims& dm = c->cd.dm;
+  const lde_host::ChainDwSplit sp = lde_host::chain_dw_split(dw_jobs(dm, dw_pick_ndw(dm)), 2, N);   // 2 column groups per tile rounds the slot count up the most
+  if (!grow(&c->stage, &c->stage_cap, (size_t)sp.total * dm.blk_floats) || !grow(&c->wts, &c->wts_cap, (size_t)sp.total * NB) ||
+      !grow(&c->slab, &c->slab_cap, ((size_t)sp.nvt + 1) * dm.slab_n)) {
+    c->err = "chain: hipMalloc of the backward workspace failed";
+    return LDE_ERR_ALLOC;
   }
-  if (!cg) return false;
-  *p = narrow(c->cd, c->bd, cg);
-  return true;
+  return chain_zero_words(c);
 }
 
-// ---- grouped calls (lde_chain_group_*): while a recorder is installed the launch sites below RECORD what they would launch; the group
-// entry point then issues each stage once for all the modules (k_*_group, lde_mfma.h) when they ask for the same kernel instance, and
-// one by one otherwise. Same arguments, same code per module: the results are those of the separate calls, bit for bit.
+// ---- what a launch site hands over: a RECORD of the launch (kernel instance, grid, LDS bytes, arguments). A single call launches it
+// (launch_*_single); a grouped call (lde_chain_group_*) keeps the records of its modules and then issues each stage once for all of them
+// (k_*_group, lde_mfma.h) when they ask for the same kernel instance, and one by one otherwise. Same arguments, same code per module: the
+// results are those of the separate calls, bit for bit.
 struct RecMain {   // stage 0: the forward kernel, or the pullback's first kernel
-  int kind;        // 0 k_chain_forward<·,false>, 1 k_chain_forward_b, 2 k_chain_backward<·,false>, 3 k_chain_backward_b, 4: other (launched, not recorded)
+  int kind;        // 0 k_chain_forward, 1 k_chain_forward_b, 2 k_chain_backward, 3 k_chain_backward_b (MAIN_NAME)
   int cg;
   ChainDims cd;
   BfDims bd;
@@ -1061,7 +991,7 @@ struct RecMain {   // stage 0: the forward kernel, or the pullback's first kerne
   size_t lds;
 };
 struct RecDw {     // stage 1: the weight-gradient product
-  int kind;        // 0 k_mlp_dw<ndw,false>, 1 k_chain_dw_b<ndw>
+  int kind;        // 0 k_mlp_dw<ndw>, 1 k_chain_dw_b<ndw>
   int ndw;
   MlpDims dm;
   DwArgs d32;
@@ -1083,69 +1013,87 @@ struct GroupRec {
   RecDw dw[GROUP_MAX];
   RecRed red[GROUP_MAX];
 };
-struct FwdMse { const float* t; float* part; unsigned tiles; bool delta; float scale; };   // delta: also leave δ_L′ for the pullback (bf16 mode)
-static thread_local FwdMse t_fwd_mse = {nullptr, nullptr, 0, false, 0.f};                // lde_chain_forward_save_mse (tiles: the forward launch's grid, set by the launch site)
-struct MseSrc { const float* t; const float* g; float scale; };
-static thread_local MseSrc t_mse = {nullptr, nullptr, 0.f};
-static thread_local const float* t_delta_g = nullptr;   // lde_chain_backward_saved_delta: δ_L′ is staged; the cotangent g multiplies dx / dW at the end              // lde_chain_backward_saved_mse
-static thread_local const float* t_dy_more[2] = {nullptr, nullptr};   // lde_chain_backward_saved_sum: further sources of the output gradient
-static thread_local GroupRec* t_rec = nullptr;
 // (kernel arguments: 4 KB on this runtime)
 static_assert(sizeof(GroupTable<ChainBDims, ChainBwdArgsB>) <= 4096 && sizeof(GroupTable<ChainDims, ChainBwdArgs>) <= 4096 &&
               sizeof(GroupTable<ChainBDims, DwArgsB>) <= 4096 && sizeof(GroupTable<MlpDims, DwArgs, GROUP_MAX_DW>) <= 4096 &&
               sizeof(GroupTable<MlpDims, ReduceArgs, GROUP_MAX_DW>) <= 4096, "a group's argument table must fit the kernel-argument segment");
 
-static bool set_max_lds_(const void* fn, bool* done) {
-  if (*done) return true;
+// Everything one call carries beyond the arrays every entry point takes: the entry point fills it, chain_forward_impl / chain_backward_impl
+// and their bf16 halves read it — and nothing else does, so one call's extras cannot reach another's.
+struct ChainCall {
+  struct {                      // lde_chain_forward_save_mse[_delta]: Σ (y − target)² per tile into `part` from the last layer's epilogue
+    const float* target = nullptr;
+    float* part = nullptr;
+    bool delta = false;         // also leave δ_L′ = 2·scale·(y − target)·act′(y) for the pullback (bf16 mode)
+    float scale = 0.f;
+    unsigned tiles = 0;         // OUT: the forward launch's grid = the partial sums written
+  } fwd;
+  struct {
+    const float* dy_more[2] = {nullptr, nullptr};   // lde_chain_backward_saved_sum: further sources of the output gradient
+    const float* target = nullptr;                  // lde_chain_backward_saved_mse: the first source is 2·(g·scale)·(y − target)
+    const float* g = nullptr;
+    float scale = 0.f;
+    const float* delta_g = nullptr;                 // lde_chain_backward_saved_delta: δ_L′ is staged; the cotangent g multiplies dx / dW at the end
+  } bwd;
+  GroupRec* rec = nullptr;      // a grouped call: the launch sites record into slot rec->n instead of launching
+};
+
+// every kernel here may ask for the whole LDS: once per kernel
+static bool set_max_lds_(const void* fn) {
+  static std::mutex mu;
+  static std::vector<const void*> done;
+  std::lock_guard<std::mutex> lk(mu);
+  if (std::find(done.begin(), done.end(), fn) != done.end()) return true;
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) return false;
-  *done = true;
+  done.push_back(fn);
   return true;
 }
-static void launch_main_single(const RecMain& r, hipStream_t stream) {
-  ChainDims cdv = r.cd;
-  BfDims bdv = r.bd;
+static const char* const MAIN_NAME[4] = {"k_chain_forward", "k_chain_forward_b", "k_chain_backward", "k_chain_backward_b"};
+// (like the two below: false when the LDS attribute could not be set; a failed launch stays in hipGetLastError for the caller)
+static bool launch_main_single(const RecMain& r, hipStream_t stream) {
+  const void* fn;
+  void* argv[3] = {(void*)&r.cd, nullptr, nullptr};
   if (r.kind == 0) {
-    ChainFwdArgs a = r.f32;
-    void* argv[] = {(void*)&cdv, (void*)&a};
-    const void* fn = r.cg == 4 ? (const void*)k_chain_forward<4, false> : r.cg == 2 ? (const void*)k_chain_forward<2, false> : (const void*)k_chain_forward<1, false>;
-    (void)hipLaunchKernel(fn, dim3(r.grid), dim3(512), argv, r.lds, stream);
+    fn = r.cg == 4 ? (const void*)k_chain_forward<4> : r.cg == 2 ? (const void*)k_chain_forward<2> : (const void*)k_chain_forward<1>;
+    argv[1] = (void*)&r.f32;
   } else if (r.kind == 1) {
-    ChainFwdArgsB a = r.fb;
-    void* argv[] = {(void*)&cdv, (void*)&bdv, (void*)&a};
-    const void* fn = r.cg == 4 ? (const void*)k_chain_forward_b<4> : r.cg == 2 ? (const void*)k_chain_forward_b<2> : (const void*)k_chain_forward_b<1>;
-    (void)hipLaunchKernel(fn, dim3(r.grid), dim3(512), argv, r.lds, stream);
+    fn = r.cg == 4 ? (const void*)k_chain_forward_b<4> : r.cg == 2 ? (const void*)k_chain_forward_b<2> : (const void*)k_chain_forward_b<1>;
+    argv[1] = (void*)&r.bd; argv[2] = (void*)&r.fb;
   } else if (r.kind == 2) {
-    ChainBwdArgs a = r.b32;
-    void* argv[] = {(void*)&cdv, (void*)&a};
-    const void* fn = r.cg == 2 ? (const void*)k_chain_backward<2, false> : (const void*)k_chain_backward<1, false>;
-    (void)hipLaunchKernel(fn, dim3(r.grid), dim3(512), argv, r.lds, stream);
+    fn = r.cg == 2 ? (const void*)k_chain_backward<2> : (const void*)k_chain_backward<1>;
+    argv[1] = (void*)&r.b32;
   } else {
-    ChainBwdArgsB a = r.bb;
-    void* argv[] = {(void*)&cdv, (void*)&bdv, (void*)&a};
-    const void* fn = r.cg == 4 ? (const void*)k_chain_backward_b<4> : r.cg == 2 ? (const void*)k_chain_backward_b<2> : (const void*)k_chain_backward_b<1>;
-    (void)hipLaunchKernel(fn, dim3(r.grid), dim3(512), argv, r.lds, stream);
+    fn = r.cg == 4 ? (const void*)k_chain_backward_b<4> : r.cg == 2 ? (const void*)k_chain_backward_b<2> : (const void*)k_chain_backward_b<1>;
+    argv[1] = (void*)&r.bd; argv[2] = (void*)&r.bb;
   }
+  if (!set_max_lds_(fn)) return false;
+  (void)hipLaunchKernel(fn, dim3(r.grid), dim3(512), argv, r.lds, stream);
+  return true;
 }
-static void launch_dw_single(const RecDw& r, hipStream_t stream) {
+static bool launch_dw_single(const RecDw& r, hipStream_t stream) {   // false: the LDS attribute could not be set
+  const void* fn;
+  void* argv[3];
   if (r.kind == 0) {
-    static bool attr[3] = {false, false, false};
-    (void)set_max_lds_((const void*)k_mlp_dw<1, false>, &attr[0]);
-    (void)set_max_lds_((const void*)k_mlp_dw<2, false>, &attr[1]);
-    (void)set_max_lds_((const void*)k_mlp_dw<4, false>, &attr[2]);
-    const dim3 grid(r.gx, r.gy, r.gz);
-    if (r.ndw == 1) hipLaunchKernelGGL((k_mlp_dw<1, false>), grid, dim3(512), r.lds, stream, r.dm, r.d32);
-    else if (r.ndw == 2) hipLaunchKernelGGL((k_mlp_dw<2, false>), grid, dim3(512), r.lds, stream, r.dm, r.d32);
-    else hipLaunchKernelGGL((k_mlp_dw<4, false>), grid, dim3(512), r.lds, stream, r.dm, r.d32);
+    fn = r.ndw == 1 ? (const void*)k_mlp_dw<1> : r.ndw == 2 ? (const void*)k_mlp_dw<2> : (const void*)k_mlp_dw<4>;
+    argv[0] = (void*)&r.dm; argv[1] = (void*)&r.d32;
   } else {
-    const dim3 grid(r.gx, r.gy);
-    if (r.ndw == 1) hipLaunchKernelGGL(k_chain_dw_b<1>, grid, dim3(512), r.lds, stream, r.cd, r.bd, r.db);
-    else if (r.ndw == 2) hipLaunchKernelGGL(k_chain_dw_b<2>, grid, dim3(512), r.lds, stream, r.cd, r.bd, r.db);
-    else hipLaunchKernelGGL(k_chain_dw_b<4>, grid, dim3(512), r.lds, stream, r.cd, r.bd, r.db);
+    fn = r.ndw == 1 ? (const void*)k_chain_dw_b<1> : r.ndw == 2 ? (const void*)k_chain_dw_b<2> : (const void*)k_chain_dw_b<4>;
+    argv[0] = (void*)&r.cd; argv[1] = (void*)&r.bd; argv[2] = (void*)&r.db;
   }
+  if (!set_max_lds_(fn)) return false;
+  (void)hipLaunchKernel(fn, dim3(r.gx, r.gy, r.gz), dim3(512), argv, r.lds, stream);
+  return true;
 }
 static void launch_red_single(const RecRed& r, hipStream_t stream) {
   hipLaunchKernelGGL(k_reduce_tiles, dim3(r.grid), dim3(256), 0, stream, r.a.priv, r.a.nflush, r.a.nwg, r.a.slab, r.a.nslab, r.dm, r.a.dW, r.a.feedback,
                      r.a.assign);
+}
+// one launch of a merged stage: the modules' grids side by side, the widest LDS request
+static bool launch_group(const void* fn, void* table, int grid, int threads, size_t lds, hipStream_t stream) {
+  if (lds && !set_max_lds_(fn)) return false;
+  void* argv[] = {table};
+  (void)hipLaunchKernel(fn, dim3(grid), dim3(threads), argv, lds, stream);
+  return true;
 }
 // the three stages of a recorded group: ONE launch per stage when every module asks for the same small-tile kernel instance
 static int group_flush(GroupRec& g, hipStream_t stream) {
@@ -1157,41 +1105,32 @@ static int group_flush(GroupRec& g, hipStream_t stream) {
       size_t lds = 0;
       for (int j = 0; j < n; j++) lds = std::max(lds, g.main[j].lds);
       const int kind = g.main[0].kind;
-      static bool attr[4] = {false, false, false, false};
-      if (kind == 0 || kind == 2) {
-        if (kind == 0) {
-          GroupTable<ChainDims, ChainFwdArgs> t{};
-          t.n = n;
-          for (int j = 0; j < n; j++) { t.start[j + 1] = t.start[j] + (int)g.main[j].grid; t.dims[j] = g.main[j].cd; t.args[j] = g.main[j].f32; }
-          if (!set_max_lds_((const void*)k_chain_forward_group<1, false>, &attr[0])) return LDE_ERR_HIP;
-          void* argv[] = {(void*)&t};
-          (void)hipLaunchKernel((const void*)k_chain_forward_group<1, false>, dim3(t.start[n]), dim3(512), argv, lds, stream);
-        } else {
-          GroupTable<ChainDims, ChainBwdArgs> t{};
-          t.n = n;
-          for (int j = 0; j < n; j++) { t.start[j + 1] = t.start[j] + (int)g.main[j].grid; t.dims[j] = g.main[j].cd; t.args[j] = g.main[j].b32; }
-          if (!set_max_lds_((const void*)k_chain_backward_group<1, false>, &attr[2])) return LDE_ERR_HIP;
-          void* argv[] = {(void*)&t};
-          (void)hipLaunchKernel((const void*)k_chain_backward_group<1, false>, dim3(t.start[n]), dim3(512), argv, lds, stream);
-        }
+      bool ok;
+      if (kind == 0) {
+        GroupTable<ChainDims, ChainFwdArgs> t{};
+        t.n = n;
+        for (int j = 0; j < n; j++) { t.start[j + 1] = t.start[j] + (int)g.main[j].grid; t.dims[j] = g.main[j].cd; t.args[j] = g.main[j].f32; }
+        ok = launch_group((const void*)k_chain_forward_group<1>, &t, t.start[n], 512, lds, stream);
+      } else if (kind == 2) {
+        GroupTable<ChainDims, ChainBwdArgs> t{};
+        t.n = n;
+        for (int j = 0; j < n; j++) { t.start[j + 1] = t.start[j] + (int)g.main[j].grid; t.dims[j] = g.main[j].cd; t.args[j] = g.main[j].b32; }
+        ok = launch_group((const void*)k_chain_backward_group<1>, &t, t.start[n], 512, lds, stream);
       } else if (kind == 1) {
         GroupTable<ChainBDims, ChainFwdArgsB> t{};
         t.n = n;
         for (int j = 0; j < n; j++) { t.start[j + 1] = t.start[j] + (int)g.main[j].grid; t.dims[j].cd = g.main[j].cd; t.dims[j].bd = g.main[j].bd; t.args[j] = g.main[j].fb; }
-        if (!set_max_lds_((const void*)k_chain_forward_b_group<1>, &attr[1])) return LDE_ERR_HIP;
-        void* argv[] = {(void*)&t};
-        (void)hipLaunchKernel((const void*)k_chain_forward_b_group<1>, dim3(t.start[n]), dim3(512), argv, lds, stream);
+        ok = launch_group((const void*)k_chain_forward_b_group<1>, &t, t.start[n], 512, lds, stream);
       } else {
         GroupTable<ChainBDims, ChainBwdArgsB> t{};
         t.n = n;
         for (int j = 0; j < n; j++) { t.start[j + 1] = t.start[j] + (int)g.main[j].grid; t.dims[j].cd = g.main[j].cd; t.dims[j].bd = g.main[j].bd; t.args[j] = g.main[j].bb; }
-        if (!set_max_lds_((const void*)k_chain_backward_b_group<1>, &attr[3])) return LDE_ERR_HIP;
-        void* argv[] = {(void*)&t};
-        (void)hipLaunchKernel((const void*)k_chain_backward_b_group<1>, dim3(t.start[n]), dim3(512), argv, lds, stream);
+        ok = launch_group((const void*)k_chain_backward_b_group<1>, &t, t.start[n], 512, lds, stream);
       }
+      if (!ok) return LDE_ERR_HIP;
     } else {
       for (int j = 0; j < n; j++)
-        if (g.main_set[j]) launch_main_single(g.main[j], stream);
+        if (g.main_set[j] && !launch_main_single(g.main[j], stream)) return LDE_ERR_HIP;
     }
   }
   {   // stage 1
@@ -1200,7 +1139,7 @@ static int group_flush(GroupRec& g, hipStream_t stream) {
     if (any && same) {
       size_t lds = 0;
       for (int j = 0; j < n; j++) lds = std::max(lds, g.dw[j].lds);
-      static bool attr[2] = {false, false};
+      bool ok;
       if (g.dw[0].kind == 0) {
         GroupTable<MlpDims, DwArgs, GROUP_MAX_DW> t{};
         t.n = n;
@@ -1208,9 +1147,7 @@ static int group_flush(GroupRec& g, hipStream_t stream) {
           t.start[j + 1] = t.start[j] + g.dw[j].gx * g.dw[j].gy * g.dw[j].gz;
           t.gx[j] = g.dw[j].gx; t.gy[j] = g.dw[j].gy; t.dims[j] = g.dw[j].dm; t.args[j] = g.dw[j].d32;
         }
-        if (!set_max_lds_((const void*)k_mlp_dw_group<1, false>, &attr[0])) return LDE_ERR_HIP;
-        void* argv[] = {(void*)&t};
-        (void)hipLaunchKernel((const void*)k_mlp_dw_group<1, false>, dim3(t.start[n]), dim3(512), argv, lds, stream);
+        ok = launch_group((const void*)k_mlp_dw_group<1>, &t, t.start[n], 512, lds, stream);
       } else {
         GroupTable<ChainBDims, DwArgsB> t{};
         t.n = n;
@@ -1218,13 +1155,12 @@ static int group_flush(GroupRec& g, hipStream_t stream) {
           t.start[j + 1] = t.start[j] + g.dw[j].gx * g.dw[j].gy;
           t.gx[j] = g.dw[j].gx; t.gy[j] = g.dw[j].gy; t.dims[j].cd = g.dw[j].cd; t.dims[j].bd = g.dw[j].bd; t.args[j] = g.dw[j].db;
         }
-        if (!set_max_lds_((const void*)k_chain_dw_b_group<1>, &attr[1])) return LDE_ERR_HIP;
-        void* argv[] = {(void*)&t};
-        (void)hipLaunchKernel((const void*)k_chain_dw_b_group<1>, dim3(t.start[n]), dim3(512), argv, lds, stream);
+        ok = launch_group((const void*)k_chain_dw_b_group<1>, &t, t.start[n], 512, lds, stream);
       }
+      if (!ok) return LDE_ERR_HIP;
     } else if (any) {
       for (int j = 0; j < n; j++)
-        if (g.dw_set[j]) launch_dw_single(g.dw[j], stream);
+        if (g.dw_set[j] && !launch_dw_single(g.dw[j], stream)) return LDE_ERR_HIP;
     }
   }
   {   // stage 2
@@ -1234,8 +1170,7 @@ static int group_flush(GroupRec& g, hipStream_t stream) {
       GroupTable<MlpDims, ReduceArgs, GROUP_MAX_DW> t{};
       t.n = n;
       for (int j = 0; j < n; j++) { t.start[j + 1] = t.start[j] + (int)g.red[j].grid; t.dims[j] = g.red[j].dm; t.args[j] = g.red[j].a; }
-      void* argv[] = {(void*)&t};
-      (void)hipLaunchKernel((const void*)k_reduce_tiles_group, dim3(t.start[n]), dim3(256), argv, 0, stream);
+      (void)launch_group((const void*)k_reduce_tiles_group, &t, t.start[n], 256, 0, stream);
     } else if (any) {
       for (int j = 0; j < n; j++)
         if (g.red_set[j]) launch_red_single(g.red[j], stream);
@@ -1244,204 +1179,160 @@ static int group_flush(GroupRec& g, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
 }
 
-static int chain_forward_b(lde_chain* c, const float* x, int64_t N, float* y, __bf16* saved, hipStream_t stream) {
-  ChainPickB pk;
-  if (!chain_pick_b(c, x, N, false, &pk)) {
+// stage 0 of a call: into the group's record, or launched
+static int submit_main(lde_chain* c, ChainCall& call, const RecMain& r, hipStream_t stream) {
+  if (call.rec) {
+    call.rec->main[call.rec->n] = r;
+    call.rec->main_set[call.rec->n] = true;
+    return LDE_OK;
+  }
+  if (!launch_main_single(r, stream)) {
+    c->err = std::string("hipFuncSetAttribute(") + MAIN_NAME[r.kind] + ") failed";
+    return LDE_ERR_HIP;
+  }
+  if (hipGetLastError() != hipSuccess) {
+    c->err = std::string(MAIN_NAME[r.kind]) + " launch failed";
+    return LDE_ERR_HIP;
+  }
+  return LDE_OK;
+}
+// stages 1 and 2: into the group's record (a group's jobs stay on the caller's stream), or launched on `wst`
+static int submit_dw(lde_chain* c, ChainCall& call, const RecDw& r, const RecRed& q, hipStream_t wst) {
+  if (call.rec) {
+    call.rec->dw[call.rec->n] = r;
+    call.rec->red[call.rec->n] = q;
+    call.rec->dw_set[call.rec->n] = call.rec->red_set[call.rec->n] = true;
+    return LDE_OK;
+  }
+  if (!launch_dw_single(r, wst)) {
+    c->err = r.kind == 0 ? "hipFuncSetAttribute(k_mlp_dw) failed" : "hipFuncSetAttribute(k_chain_dw_b) failed";
+    return LDE_ERR_HIP;
+  }
+  launch_red_single(q, wst);
+  if (hipGetLastError() != hipSuccess) {
+    c->err = r.kind == 0 ? "weight-gradient kernels failed to launch" : "bf16 weight-gradient kernels failed to launch";
+    return LDE_ERR_HIP;
+  }
+  return LDE_OK;
+}
+
+// LDE_PROF builds: zero the kernels' cycle counters before a launch (`after`: first wait for this stream's work, which still adds to
+// them), and print them behind one — every 20th call of a site with more than 1000 columns
+#if LDE_PROF
+static void prof_reset(bool wait, hipStream_t after) {
+  if (wait) (void)hipStreamSynchronize(after);
+  long long z[64] = {0};
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof(z));
+}
+static void prof_report(hipStream_t stream, int64_t N, int site, const char* tag, ...) {
+  static int calls[4] = {0, 0, 0, 0};
+  (void)hipStreamSynchronize(stream);
+  long long v[64];
+  (void)hipMemcpyFromSymbol(v, HIP_SYMBOL(g_prof), sizeof(v));
+  if (N > 1000 && ++calls[site] % 20 == 0) {
+    va_list ap;
+    va_start(ap, tag);
+    vfprintf(stderr, tag, ap);
+    fprintf(stderr, " cycles:");
+    va_end(ap);
+    for (int i = 0; i < 64; i++)
+      if (v[i]) fprintf(stderr, " %d:%lld", i, v[i]);
+    fprintf(stderr, "\n");
+  }
+}
+#else
+static void prof_reset(bool, hipStream_t) {}
+static void prof_report(hipStream_t, int64_t, int, const char*, ...) {}
+#endif
+
+static int chain_forward_b(lde_chain* c, const float* x, int64_t N, float* y, __bf16* saved, hipStream_t stream, ChainCall& call) {
+  ChainPick pk;
+  if (!chain_pick(c, x, N, false, &pk)) {
     c->err = "lde_chain_forward (bf16): no tile layout fits LDS for this input";
     return LDE_ERR_UNSUPPORTED;
   }
-  ChainFwdArgsB a{x, y, c->fragb, c->W_dev, (long long)N, saved, t_fwd_mse.t, t_fwd_mse.part, nullptr, 0.f, 0};
-  if (t_fwd_mse.delta) {   // δ_L′ into the last layer's δ matrix of the pullback's workspace (the allocation the pullback would make: it finds it there)
+  RecMain r{};
+  r.kind = 1; r.cg = pk.cg; r.cd = *pk.cd; r.bd = *pk.bd; r.lds = pk.lds;
+  r.fb = ChainFwdArgsB{x, y, c->fragb, c->W_dev, (long long)N, saved, call.fwd.target, call.fwd.part, nullptr, 0.f, 0};
+  if (call.fwd.delta) {   // δ_L′ into the last layer's δ matrix of the pullback's workspace (the allocation the pullback would make: it finds it there)
     const MlpDims& dmf = c->cd.dm;
     if (!grow(&c->dstage, &c->dstage_cap, (size_t)N * c->bd.dl_total + (size_t)64 * c->bd.dl_w[dmf.nL - 1] + 64)) {
       c->err = "chain: hipMalloc of the bf16 backward workspace failed";
       return LDE_ERR_ALLOC;
     }
-    ChainPickB pkb;   // (the δ matrices' layout is the pullback's choice)
-    if (!chain_pick_b(c, x, N, true, &pkb)) {
+    ChainPick pkb;   // (the δ matrices' layout is the pullback's choice)
+    if (!chain_pick(c, x, N, true, &pkb)) {
       c->err = "lde_chain_forward_save_mse_delta: no pullback tile layout fits LDS for this input";
       return LDE_ERR_UNSUPPORTED;
     }
-    a.dL = c->dstage + (size_t)N * pkb.bd->dl_off[dmf.nL - 1];
-    a.dk2 = 2.0f * t_fwd_mse.scale;
-    a.dlw = pkb.bd->dl_w[dmf.nL - 1];
+    r.fb.dL = c->dstage + (size_t)N * pkb.bd->dl_off[dmf.nL - 1];
+    r.fb.dk2 = 2.0f * call.fwd.scale;
+    r.fb.dlw = pkb.bd->dl_w[dmf.nL - 1];
   }
-  const int NC = 16 * pk.cg;
-  const dim3 grid((unsigned)((N + NC - 1) / NC));
-  t_fwd_mse.tiles = grid.x;
-  static bool attr[5] = {false, false, false, false, false};
-  const void* fn = pk.cg == 4 ? (const void*)k_chain_forward_b<4> : pk.cg == 2 ? (const void*)k_chain_forward_b<2> : (const void*)k_chain_forward_b<1>;
-  if (!attr[pk.cg]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) {
-      c->err = "hipFuncSetAttribute(k_chain_forward_b) failed";
-      return LDE_ERR_HIP;
-    }
-    attr[pk.cg] = true;
-  }
-  ChainDims cdv = *pk.cd;
-  BfDims bdv = *pk.bd;
-  void* argv[] = {(void*)&cdv, (void*)&bdv, (void*)&a};
-#if LDE_PROF
-  { long long z[64] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof(z)); }
-#endif
-  if (t_rec) {
-    RecMain& r = t_rec->main[t_rec->n];
-    r.kind = 1; r.cg = pk.cg; r.cd = cdv; r.bd = bdv; r.fb = a; r.grid = grid.x; r.lds = pk.lds;
-    t_rec->main_set[t_rec->n] = true;
-    (void)argv;
-    return LDE_OK;
-  }
-  (void)hipLaunchKernel(fn, grid, dim3(512), argv, pk.lds, stream);
-  if (hipGetLastError() != hipSuccess) {
-    c->err = "k_chain_forward_b launch failed";
-    return LDE_ERR_HIP;
-  }
-#if LDE_PROF
-  {
-    static int calls = 0;
-    (void)hipStreamSynchronize(stream);
-    long long v[64];
-    (void)hipMemcpyFromSymbol(v, HIP_SYMBOL(g_prof), sizeof(v));
-    if (N > 1000 && ++calls % 20 == 0) {
-      fprintf(stderr, "[prof chain fwd bf16 cg=%d] cycles:", pk.cg);
-      for (int i = 0; i < 64; i++)
-        if (v[i]) fprintf(stderr, " %d:%lld", i, v[i]);
-      fprintf(stderr, "\n");
-    }
-  }
-#endif
-  return LDE_OK;
+  r.grid = (unsigned)lde_host::chain_tiles(N, pk.cg);
+  call.fwd.tiles = r.grid;
+  prof_reset(false, nullptr);
+  const int rc = submit_main(c, call, r, stream);
+  if (rc == LDE_OK && !call.rec) prof_report(stream, N, 0, "[prof chain fwd bf16 cg=%d]", pk.cg);
+  return rc;
 }
 
 static int chain_backward_b(lde_chain* c, const float* x, const float* y, const float* dy, const __bf16* saved, int64_t N, float* dx,
-                            float* dW, hipStream_t stream) {
+                            float* dW, hipStream_t stream, ChainCall& call) {
   const MlpDims& dm = c->cd.dm;
   const int ndw = dw_pick_ndw(dm), jobs = dw_jobs(dm, ndw);
-  const int64_t nchunks = (N + DWB_NK - 1) / DWB_NK;
-  int parts = 256 / jobs;
-  parts = parts < 1 ? 1 : parts;
-  if (parts > nchunks) parts = (int)nchunks;
+  const int parts = lde_host::chain_dw_parts_bf16(jobs, N, DWB_NK);
   // (+ one tile of rows of the last layer's matrix: its read-back as a B operand covers the ragged tile's columns beyond N — their
   //  results are dropped, but the loads must stay inside the allocation)
   if (!grow(&c->dstage, &c->dstage_cap, (size_t)N * c->bd.dl_total + (size_t)64 * c->bd.dl_w[dm.nL - 1] + 64) || !grow(&c->slab, &c->slab_cap, ((size_t)parts + 1) * dm.slab_n)) {
     c->err = "chain: hipMalloc of the bf16 backward workspace failed";
     return LDE_ERR_ALLOC;
   }
-  if (!c->ints) {
-    if (hipMalloc(&c->ints, 64) != hipSuccess || hipMemset(c->ints, 0, 64) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
-      c->err = "chain: hipMalloc of the backward workspace failed";
-      return LDE_ERR_ALLOC;
-    }
-    c->ints_cap = 16;
-  }
+  int rc = chain_zero_words(c);
+  if (rc) return rc;
   if (!saved) {   // the caller kept nothing: the pullback's own forward pass fills a scratch copy of the saved matrices
     const size_t need = (size_t)c->cd.sv_total * N + 8;
     if (!grow(&c->svscratch, &c->svscratch_cap, need)) {
       c->err = "chain: hipMalloc of the saved-activation scratch failed";
       return LDE_ERR_ALLOC;
     }
-    const int rcf = chain_forward_b(c, x, N, nullptr, c->svscratch, stream);
-    if (rcf) return rcf;
+    ChainCall plain;   // a forward pass without extras, launched (never recorded: a grouped pullback always brings its saved buffers)
+    rc = chain_forward_b(c, x, N, nullptr, c->svscratch, stream, plain);
+    if (rc) return rc;
     saved = c->svscratch;
   }
-  ChainPickB pk;
-  if (!chain_pick_b(c, x, N, true, &pk)) {
+  ChainPick pk;
+  if (!chain_pick(c, x, N, true, &pk)) {
     c->err = "lde_chain_backward (bf16): no tile layout fits LDS for this input";
     return LDE_ERR_UNSUPPORTED;
   }
-  ChainBwdArgsB a{x, y, dy, dx, c->fragTb, c->W_dev, c->dstage, (long long)N, saved, t_dy_more[0], t_dy_more[1], t_mse.t, t_mse.g, t_mse.scale,
-                  t_delta_g ? 1 : 0, t_delta_g};
-  if (!t_delta_g) { c->delta_N = -1; c->delta_saved = nullptr; }   // (this pullback writes its own δ_L over whatever the forward pass staged)
-  const int NC = 16 * pk.cg;
-  {
-    const dim3 grid((unsigned)((N + NC - 1) / NC));
-    static bool attr[5] = {false, false, false, false, false};
-    const void* fn = pk.cg == 4 ? (const void*)k_chain_backward_b<4> : pk.cg == 2 ? (const void*)k_chain_backward_b<2> : (const void*)k_chain_backward_b<1>;
-    if (!attr[pk.cg]) {
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) {
-        c->err = "hipFuncSetAttribute(k_chain_backward_b) failed";
-        return LDE_ERR_HIP;
-      }
-      attr[pk.cg] = true;
-    }
-    ChainDims cdv = *pk.cd;
-    BfDims bdv = *pk.bd;
-    void* argv[] = {(void*)&cdv, (void*)&bdv, (void*)&a};
-    if (t_rec) {
-      RecMain& r = t_rec->main[t_rec->n];
-      r.kind = 3; r.cg = pk.cg; r.cd = cdv; r.bd = bdv; r.bb = a; r.grid = grid.x; r.lds = pk.lds;
-      t_rec->main_set[t_rec->n] = true;
-    } else {
-      (void)hipLaunchKernel(fn, grid, dim3(512), argv, pk.lds, stream);
-      if (hipGetLastError() != hipSuccess) {
-        c->err = "k_chain_backward_b launch failed";
-        return LDE_ERR_HIP;
-      }
-    }
-  }
+  const float* delta_g = call.bwd.delta_g;
+  if (!delta_g) { c->delta_N = -1; c->delta_saved = nullptr; }   // (this pullback writes its own δ_L over whatever the forward pass staged)
+  RecMain r{};
+  r.kind = 3; r.cg = pk.cg; r.cd = *pk.cd; r.bd = *pk.bd; r.lds = pk.lds; r.grid = (unsigned)lde_host::chain_tiles(N, pk.cg);
+  r.bb = ChainBwdArgsB{x, y, dy, dx, c->fragTb, c->W_dev, c->dstage, (long long)N, saved, call.bwd.dy_more[0], call.bwd.dy_more[1], call.bwd.target, call.bwd.g,
+                       call.bwd.scale, delta_g ? 1 : 0, delta_g};
+  rc = submit_main(c, call, r, stream);
+  if (rc) return rc;
   // weight gradient: [n][feature] matrices through the transposing LDS reads, then the fixed-order slab reduction
   bool sw_ok = true;
-  hipStream_t wst = (t_rec || !c->opt_async_dw) ? stream : dw_sync_switch(c->dws, stream, &sw_ok);   // (recorded for a grouped launch: on the caller's stream)
+  hipStream_t wst = (call.rec || !c->opt_async_dw) ? stream : dw_sync_switch(c->dws, stream, &sw_ok);   // (recorded for a grouped launch: on the caller's stream)
   if (!sw_ok) {
     c->err = "lde_chain_backward: switching to the weight-gradient stream failed";
     return LDE_ERR_HIP;
   }
-  {
-    const size_t dlds = dw_b_lds_bytes(dm, ndw);
-    if (dlds > LDS_MAX) {
-      c->err = "layer too wide for the bf16 weight-gradient kernel's LDS images";
-      return LDE_ERR_UNSUPPORTED;
-    }
-    static bool attr_set = false;
-    if (!attr_set) {
-      if (hipFuncSetAttribute((const void*)k_chain_dw_b<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_chain_dw_b<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_chain_dw_b<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) {
-        c->err = "hipFuncSetAttribute(k_chain_dw_b) failed";
-        return LDE_ERR_HIP;
-      }
-      attr_set = true;
-    }
-    DwArgsB da{x, saved, c->dstage, c->slab, (long long)N, t_delta_g};
-    const dim3 grid(parts, jobs);
-#if LDE_PROF
-    { (void)hipStreamSynchronize(wst); long long z[64] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof(z)); }
-#endif
-    ChainDims cdv = c->cd;
-    BfDims bdv = c->bd;
-    if (t_rec) {
-      RecDw& r = t_rec->dw[t_rec->n];
-      r.kind = 1; r.ndw = ndw; r.cd = cdv; r.bd = bdv; r.db = da; r.gx = parts; r.gy = jobs; r.gz = 1; r.lds = dlds;
-      t_rec->dw_set[t_rec->n] = true;
-      RecRed& q = t_rec->red[t_rec->n];
-      q.dm = dm; q.a = ReduceArgs{nullptr, c->ints, 0, c->slab, parts, dW, c->ints + 2, c->accumulate ? 0 : 1}; q.grid = (unsigned)cdiv(dm.slab_n, 1024);
-      t_rec->red_set[t_rec->n] = true;
-      return LDE_OK;
-    }
-    if (ndw == 1) hipLaunchKernelGGL(k_chain_dw_b<1>, grid, dim3(512), dlds, wst, cdv, bdv, da);
-    else if (ndw == 2) hipLaunchKernelGGL(k_chain_dw_b<2>, grid, dim3(512), dlds, wst, cdv, bdv, da);
-    else hipLaunchKernelGGL(k_chain_dw_b<4>, grid, dim3(512), dlds, wst, cdv, bdv, da);
-    hipLaunchKernelGGL(k_reduce_tiles, dim3(cdiv(dm.slab_n, 1024)), dim3(256), 0, wst, (const float*)nullptr, c->ints, 0, c->slab, parts, dm, dW,
-                       c->ints + 2, c->accumulate ? 0 : 1);
-    if (hipGetLastError() != hipSuccess) {
-      c->err = "bf16 weight-gradient kernels failed to launch";
-      return LDE_ERR_HIP;
-    }
-#if LDE_PROF
-    {
-      static int calls = 0;
-      (void)hipStreamSynchronize(wst);
-      long long v[64];
-      (void)hipMemcpyFromSymbol(v, HIP_SYMBOL(g_prof), sizeof(v));
-      if (N > 1000 && ++calls % 20 == 0) {
-        fprintf(stderr, "[prof chain dw bf16 parts=%d jobs=%d ndw=%d] cycles:", parts, jobs, ndw);
-        for (int i = 0; i < 64; i++)
-          if (v[i]) fprintf(stderr, " %d:%lld", i, v[i]);
-        fprintf(stderr, "\n");
-      }
-    }
-#endif
+  RecDw w{};
+  w.kind = 1; w.ndw = ndw; w.cd = c->cd; w.bd = c->bd; w.db = DwArgsB{x, saved, c->dstage, c->slab, (long long)N, delta_g};
+  w.gx = parts; w.gy = jobs; w.gz = 1; w.lds = dw_b_lds_bytes(dm, ndw);
+  if (w.lds > LDS_MAX) {
+    c->err = "layer too wide for the bf16 weight-gradient kernel's LDS images";
+    return LDE_ERR_UNSUPPORTED;
   }
+  const RecRed q{dm, ReduceArgs{nullptr, c->ints, 0, c->slab, parts, dW, c->ints + 2, c->accumulate ? 0 : 1}, (unsigned)cdiv(dm.slab_n, 1024)};
+  prof_reset(true, wst);
+  rc = submit_dw(c, call, w, q, wst);
+  if (rc || call.rec) return rc;
+  prof_report(wst, N, 1, "[prof chain dw bf16 parts=%d jobs=%d ndw=%d]", parts, jobs, ndw);
   if (!dw_sync_end(c->dws, wst, stream)) {
     c->err = "lde_chain_backward: hipEventRecord failed";
     return LDE_ERR_HIP;
@@ -1449,9 +1340,9 @@ static int chain_backward_b(lde_chain* c, const float* x, const float* y, const 
   return LDE_OK;
 }
 
-static int chain_forward_impl(lde_chain* c, const float* x, int64_t N, float* y, float* saved, void* stream_) {
+static int chain_forward_impl(lde_chain* c, const float* x, int64_t N, float* y, float* saved, void* stream_, ChainCall& call) {
   if (!c || !c->W_dev) return LDE_ERR_INVALID_ARG;
-  if (!x || (!y && !t_fwd_mse.delta) || N < 1) {   // (y may be NULL only where the forward pass leaves δ_L′ instead: lde_chain_forward_save_mse_delta)
+  if (!x || (!y && !call.fwd.delta) || N < 1) {   // (y may be NULL only where the forward pass leaves δ_L′ instead: lde_chain_forward_save_mse_delta)
     c->err = "lde_chain_forward: NULL pointer or empty batch";
     return LDE_ERR_INVALID_ARG;
   }
@@ -1464,64 +1355,24 @@ static int chain_forward_impl(lde_chain* c, const float* x, int64_t N, float* y,
     return LDE_ERR_INVALID_ARG;
   }
   hipStream_t stream = (hipStream_t)stream_;
-  if (c->bf16) return chain_forward_b(c, x, N, y, reinterpret_cast<__bf16*>(saved), stream);
-  ChainFwdArgs a{x, y, c->frag, c->W_dev, (long long)N, saved, t_fwd_mse.t, t_fwd_mse.part};
+  if (c->bf16) return chain_forward_b(c, x, N, y, reinterpret_cast<__bf16*>(saved), stream, call);
   ChainPick pk;
   if (!chain_pick(c, x, N, false, &pk)) {
     c->err = "lde_chain_forward: the only layout whose panels fit LDS reads x in place and needs N ≥ one tile and a 16-byte aligned x";
     return LDE_ERR_UNSUPPORTED;
   }
-  const int NC = 16 * pk.cg;
-  const dim3 grid((unsigned)((N + NC - 1) / NC));
-  t_fwd_mse.tiles = grid.x;
-  static bool attr[2][5] = {{false, false, false, false, false}, {false, false, false, false, false}};
-  const int bf = c->bf16 ? 1 : 0;
-  const void* fn = bf ? (pk.cg == 4 ? (const void*)k_chain_forward<4, true> : pk.cg == 2 ? (const void*)k_chain_forward<2, true> : (const void*)k_chain_forward<1, true>)
-                      : (pk.cg == 4 ? (const void*)k_chain_forward<4, false> : pk.cg == 2 ? (const void*)k_chain_forward<2, false> : (const void*)k_chain_forward<1, false>);
-  if (!attr[bf][pk.cg]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) {
-      c->err = "hipFuncSetAttribute(k_chain_forward) failed";
-      return LDE_ERR_HIP;
-    }
-    attr[bf][pk.cg] = true;
-  }
-#if LDE_PROF
-  { long long z[64] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof(z)); }
-#endif
-  if (t_rec && !bf) {
-    RecMain& r = t_rec->main[t_rec->n];
-    r.kind = 0; r.cg = pk.cg; r.cd = *pk.cd; r.f32 = a; r.grid = grid.x; r.lds = pk.lds;
-    t_rec->main_set[t_rec->n] = true;
-    return LDE_OK;
-  }
-  {
-    ChainDims cdv = *pk.cd;
-    void* argv[] = {(void*)&cdv, (void*)&a};
-    (void)hipLaunchKernel(fn, grid, dim3(512), argv, pk.lds, stream);
-  }
-  if (hipGetLastError() != hipSuccess) {
-    c->err = "k_chain_forward launch failed";
-    return LDE_ERR_HIP;
-  }
-#if LDE_PROF
-  {
-    static int calls = 0;
-    (void)hipStreamSynchronize(stream);
-    long long v[64];
-    (void)hipMemcpyFromSymbol(v, HIP_SYMBOL(g_prof), sizeof(v));
-    if (N > 1000 && ++calls % 20 == 0) {
-      fprintf(stderr, "[prof chain fwd] cycles:");
-      for (int i = 0; i < 64; i++)
-        if (v[i]) fprintf(stderr, " %d:%lld", i, v[i]);
-      fprintf(stderr, "\n");
-    }
-  }
-#endif
-  return LDE_OK;
+  RecMain r{};
+  r.kind = 0; r.cg = pk.cg; r.cd = *pk.cd; r.lds = pk.lds; r.grid = (unsigned)lde_host::chain_tiles(N, pk.cg);
+  r.f32 = ChainFwdArgs{x, y, c->frag, c->W_dev, (long long)N, saved, call.fwd.target, call.fwd.part};
+  call.fwd.tiles = r.grid;
+  prof_reset(false, nullptr);
+  const int rc = submit_main(c, call, r, stream);
+  if (rc == LDE_OK && !call.rec) prof_report(stream, N, 2, "[prof chain fwd]");
+  return rc;
 }
 
 static int chain_backward_impl(lde_chain* c, const float* x, const float* y, const float* dy, const float* saved, int64_t N,
-                               float* dx, float* dW, void* stream_) {
+                               float* dx, float* dW, void* stream_, ChainCall& call) {
   if (!c || !c->W_dev) return LDE_ERR_INVALID_ARG;
   if (!x || !y || !dy || !dW || N < 1) {
     c->err = "lde_chain_backward: NULL pointer or empty batch";
@@ -1535,95 +1386,64 @@ static int chain_backward_impl(lde_chain* c, const float* x, const float* y, con
     c->err = "lde_chain_backward: y and dy must be 16-byte aligned";
     return LDE_ERR_INVALID_ARG;
   }
-  if (!dw_sync_begin(c->dws, (hipStream_t)stream_)) {   // the workspace is about to be rewritten
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!dw_sync_begin(c->dws, stream)) {   // the workspace is about to be rewritten
     c->err = "lde_chain_backward: waiting for the previous weight gradient failed";
     return LDE_ERR_HIP;
   }
-  if (c->bf16) return chain_backward_b(c, x, y, dy, reinterpret_cast<const __bf16*>(saved), N, dx, dW, (hipStream_t)stream_);
+  if (c->bf16) return chain_backward_b(c, x, y, dy, reinterpret_cast<const __bf16*>(saved), N, dx, dW, stream, call);
   int rc = lde_chain_reserve(c, N);
   if (rc) return rc;
-  hipStream_t stream = (hipStream_t)stream_;
   const MlpDims& dm = c->cd.dm;
   ChainPick pk;
   if (!chain_pick(c, x, N, true, &pk)) {
     c->err = "lde_chain_backward: the only layout whose panels fit LDS reads x in place and needs N ≥ one tile and a 16-byte aligned x";
     return LDE_ERR_UNSUPPORTED;
   }
-  int nvt, cap;
-  int64_t total;
-  chain_dw_split(c, pk.cg, N, &nvt, &cap, &total);
-  ChainBwdArgs a{x, y, dy, dx, c->frag, c->fragT, c->W_dev, c->stage, c->wts, (long long)N, saved, t_dy_more[0], t_dy_more[1], t_mse.t, t_mse.g, t_mse.scale};
-  const int NC = 16 * pk.cg;
-  const dim3 grid((unsigned)((N + NC - 1) / NC));
-  static bool attr[2][3] = {{false, false, false}, {false, false, false}};
-  const int bf = c->bf16 ? 1 : 0;
-  const void* fn = bf ? (pk.cg == 2 ? (const void*)k_chain_backward<2, true> : (const void*)k_chain_backward<1, true>)
-                      : (pk.cg == 2 ? (const void*)k_chain_backward<2, false> : (const void*)k_chain_backward<1, false>);
-  if (!attr[bf][pk.cg]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) {
-      c->err = "hipFuncSetAttribute(k_chain_backward) failed";
-      return LDE_ERR_HIP;
-    }
-    attr[bf][pk.cg] = true;
-  }
-  const bool rec32 = t_rec && !bf;
-  if (rec32) {
-    RecMain& r = t_rec->main[t_rec->n];
-    r.kind = 2; r.cg = pk.cg; r.cd = *pk.cd; r.b32 = a; r.grid = grid.x; r.lds = pk.lds;
-    t_rec->main_set[t_rec->n] = true;
-  } else {
-    ChainDims cdv = *pk.cd;
-    void* argv[] = {(void*)&cdv, (void*)&a};
-    (void)hipLaunchKernel(fn, grid, dim3(512), argv, pk.lds, stream);
-  }
-  if (hipGetLastError() != hipSuccess) {
-    c->err = "k_chain_backward launch failed";
-    return LDE_ERR_HIP;
-  }
-  // weight gradient: large-K product over the staged panels (lde_mfma.h)
-  DwArgs da;
-  da.stage = c->stage; da.wts = c->wts; da.nslots = nullptr; da.slab = c->slab; da.cap = cap; da.total = total;   // tiles filled in order
-#if LDE_PROF
-  { (void)hipStreamSynchronize(stream); long long z[64] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof(z)); }
-#endif
+  const int ndw = dw_pick_ndw(dm), jobs = dw_jobs(dm, ndw);
+  const lde_host::ChainDwSplit sp = lde_host::chain_dw_split(jobs, pk.cg, N);
+  RecMain r{};
+  r.kind = 2; r.cg = pk.cg; r.cd = *pk.cd; r.lds = pk.lds; r.grid = (unsigned)lde_host::chain_tiles(N, pk.cg);
+  r.b32 = ChainBwdArgs{x, y, dy, dx, c->frag, c->fragT, c->W_dev, c->stage, c->wts, (long long)N, saved, call.bwd.dy_more[0], call.bwd.dy_more[1], call.bwd.target,
+                       call.bwd.g, call.bwd.scale};
+  rc = submit_main(c, call, r, stream);
+  if (rc) return rc;
+  // weight gradient: large-K product over the staged panels (lde_mfma.h), then the fixed-order slab reduction
+  prof_reset(true, stream);
   bool sw_ok = true;
-  hipStream_t wst = (t_rec || !c->opt_async_dw) ? stream : dw_sync_switch(c->dws, stream, &sw_ok);   // (recorded for a grouped launch: on the caller's stream)
+  hipStream_t wst = (call.rec || !c->opt_async_dw) ? stream : dw_sync_switch(c->dws, stream, &sw_ok);   // (recorded for a grouped launch: on the caller's stream)
   if (!sw_ok) {
     c->err = "lde_chain_backward: switching to the weight-gradient stream failed";
     return LDE_ERR_HIP;
   }
-  if (rec32) {
-    const int ndw = dw_pick_ndw(dm);
-    RecDw& r = t_rec->dw[t_rec->n];
-    r.kind = 0; r.ndw = ndw; r.dm = dm; r.d32 = da; r.gx = nvt; r.gy = 1; r.gz = dw_jobs(dm, ndw); r.lds = dw_lds_floats(dm, ndw) * sizeof(float);
-    t_rec->dw_set[t_rec->n] = true;
-    RecRed& q = t_rec->red[t_rec->n];
-    q.dm = dm; q.a = ReduceArgs{nullptr, c->ints, 0, da.slab, nvt, dW, c->ints + 2, c->accumulate ? 0 : 1}; q.grid = (unsigned)cdiv(dm.slab_n, 1024);
-    t_rec->red_set[t_rec->n] = true;
-    return LDE_OK;
+  RecDw w{};
+  w.kind = 0; w.ndw = ndw; w.dm = dm; w.gx = sp.nvt; w.gy = 1; w.gz = jobs; w.lds = dw_lds_floats(dm, ndw) * sizeof(float);
+  w.d32.stage = c->stage; w.d32.wts = c->wts; w.d32.nslots = nullptr; w.d32.slab = c->slab; w.d32.cap = sp.cap; w.d32.total = sp.total;   // tiles filled in order
+  if (w.lds > LDS_MAX) {
+    c->err = "layer too wide for the weight-gradient kernel's LDS panels";
+    return LDE_ERR_UNSUPPORTED;
   }
-  rc = launch_weight_gradient(dm, da, nvt, 1, nullptr, c->ints, 0, dW, c->ints + 2, wst, c->err, !c->accumulate, c->bf16);
-  if (rc == LDE_OK && !dw_sync_end(c->dws, wst, stream)) {
+  const RecRed q{dm, ReduceArgs{nullptr, c->ints, 0, c->slab, sp.nvt, dW, c->ints + 2, c->accumulate ? 0 : 1}, (unsigned)cdiv(dm.slab_n, 1024)};
+  rc = submit_dw(c, call, w, q, wst);
+  if (rc || call.rec) return rc;
+  if (!dw_sync_end(c->dws, wst, stream)) {
     c->err = "lde_chain_backward: hipEventRecord failed";
     return LDE_ERR_HIP;
   }
-  if (rc) return rc;
-#if LDE_PROF
-  {
-    static int calls = 0;
-    (void)hipStreamSynchronize(stream);
-    long long v[64];
-    (void)hipMemcpyFromSymbol(v, HIP_SYMBOL(g_prof), sizeof(v));
-    if (N > 1000 && ++calls % 20 == 0) {
-      fprintf(stderr, "[prof chain dw] nvt=%d cap=%d jobs=%d ndw=%d cycles:", nvt, cap, dw_jobs(dm, dw_pick_ndw(dm)), dw_pick_ndw(dm));
-      for (int i = 0; i < 64; i++)
-        if (v[i]) fprintf(stderr, " %d:%lld", i, v[i]);
-      fprintf(stderr, "\n");
-    }
-  }
-#endif
+  prof_report(stream, N, 3, "[prof chain dw] nvt=%d cap=%d jobs=%d ndw=%d", sp.nvt, sp.cap, jobs, ndw);
   return LDE_OK;
 }
+
+// the saved-activation buffer of the *_save / *_saved entry points (`what`: the entry point's sentence about it)
+static int chain_saved_ok(lde_chain* c, const float* saved, const char* what) {
+  if (c && (!saved || (((uintptr_t)saved) & 15) != 0)) {
+    c->err = what;
+    return LDE_ERR_INVALID_ARG;
+  }
+  return LDE_OK;
+}
+static const char* const FWD_SAVED = "lde_chain_forward_save: saved must be a 16-byte aligned device buffer of lde_chain_saved_floats(c, N) floats";
+static const char* const BWD_SAVED = "lde_chain_backward_saved: saved must be the buffer lde_chain_forward_save filled";
 
 int lde_chain_set_dtype(lde_chain* c, int dtype) {
   if (!c || (dtype != LDE_DTYPE_F32 && dtype != LDE_DTYPE_BF16)) return LDE_ERR_INVALID_ARG;
@@ -1636,10 +1456,12 @@ int lde_chain_set_dtype(lde_chain* c, int dtype) {
   return LDE_OK;
 }
 int lde_chain_forward(lde_chain* c, const float* x, int64_t N, float* y, void* stream) {
-  return chain_forward_impl(c, x, N, y, nullptr, stream);
+  ChainCall call;
+  return chain_forward_impl(c, x, N, y, nullptr, stream, call);
 }
 int lde_chain_backward(lde_chain* c, const float* x, const float* y, const float* dy, int64_t N, float* dx, float* dW, void* stream) {
-  return chain_backward_impl(c, x, y, dy, nullptr, N, dx, dW, stream);
+  ChainCall call;
+  return chain_backward_impl(c, x, y, dy, nullptr, N, dx, dW, stream, call);
 }
 int64_t lde_chain_saved_floats(const lde_chain* c, int64_t N) {
   if (!c || N < 1) return -1;
@@ -1647,19 +1469,15 @@ int64_t lde_chain_saved_floats(const lde_chain* c, int64_t N) {
   return n > 0 ? n : 4;   // a chain without hidden layers saves nothing; keep the buffer non-empty
 }
 int lde_chain_forward_save(lde_chain* c, const float* x, int64_t N, float* y, float* saved, void* stream) {
-  if (c && (!saved || (((uintptr_t)saved) & 15) != 0)) {
-    c->err = "lde_chain_forward_save: saved must be a 16-byte aligned device buffer of lde_chain_saved_floats(c, N) floats";
-    return LDE_ERR_INVALID_ARG;
-  }
-  return chain_forward_impl(c, x, N, y, saved, stream);
+  if (const int rc = chain_saved_ok(c, saved, FWD_SAVED)) return rc;
+  ChainCall call;
+  return chain_forward_impl(c, x, N, y, saved, stream, call);
 }
 int lde_chain_backward_saved(lde_chain* c, const float* x, const float* y, const float* dy, const float* saved, int64_t N,
                              float* dx, float* dW, void* stream) {
-  if (c && (!saved || (((uintptr_t)saved) & 15) != 0)) {
-    c->err = "lde_chain_backward_saved: saved must be the buffer lde_chain_forward_save filled";
-    return LDE_ERR_INVALID_ARG;
-  }
-  return chain_backward_impl(c, x, y, dy, saved, N, dx, dW, stream);
+  if (const int rc = chain_saved_ok(c, saved, BWD_SAVED)) return rc;
+  ChainCall call;
+  return chain_backward_impl(c, x, y, dy, saved, N, dx, dW, stream, call);
 }
 
 int64_t lde_chain_mse_scratch_floats(const lde_chain* c, int64_t N) { return (!c || N < 1) ? -1 : (N + 15) / 16 + 1; }
@@ -1670,16 +1488,14 @@ int lde_chain_forward_save_mse(lde_chain* c, const float* x, int64_t N, float* y
     c->err = "lde_chain_forward_save_mse: NULL pointer or unaligned target";
     return LDE_ERR_INVALID_ARG;
   }
-  if (t_rec) {
-    c->err = "lde_chain_forward_save_mse: not inside a grouped call";
-    return LDE_ERR_UNSUPPORTED;
-  }
-  t_fwd_mse = FwdMse{target, scratch, 0};
-  const int rc = saved ? lde_chain_forward_save(c, x, N, y, saved, stream) : lde_chain_forward(c, x, N, y, stream);
-  const unsigned tiles = t_fwd_mse.tiles;
-  t_fwd_mse = FwdMse{nullptr, nullptr, 0};
+  int rc = saved ? chain_saved_ok(c, saved, FWD_SAVED) : LDE_OK;   // (saved may be NULL: nothing is kept)
   if (rc) return rc;
-  return loss_finalize(scratch, (int)tiles, scale, base, out, (hipStream_t)stream);   // out = base + scale·Σ partials, in tile order
+  ChainCall call;
+  call.fwd.target = target;
+  call.fwd.part = scratch;
+  rc = chain_forward_impl(c, x, N, y, saved, stream, call);
+  if (rc) return rc;
+  return loss_finalize(scratch, (int)call.fwd.tiles, scale, base, out, (hipStream_t)stream);   // out = base + scale·Σ partials, in tile order
 }
 int lde_chain_backward_saved_sum(lde_chain* c, const float* x, const float* y, int n_dy, const float* const* dys, const float* saved, int64_t N,
                                  float* dx, float* dW, void* stream) {
@@ -1693,11 +1509,11 @@ int lde_chain_backward_saved_sum(lde_chain* c, const float* x, const float* y, i
       c->err = "lde_chain_backward_saved_sum: NULL or unaligned output-gradient array";
       return LDE_ERR_INVALID_ARG;
     }
-  t_dy_more[0] = n_dy > 1 ? dys[1] : nullptr;
-  t_dy_more[1] = n_dy > 2 ? dys[2] : nullptr;
-  const int rc = saved ? lde_chain_backward_saved(c, x, y, dys[0], saved, N, dx, dW, stream) : lde_chain_backward(c, x, y, dys[0], N, dx, dW, stream);
-  t_dy_more[0] = t_dy_more[1] = nullptr;
-  return rc;
+  if (const int rc = saved ? chain_saved_ok(c, saved, BWD_SAVED) : LDE_OK) return rc;
+  ChainCall call;
+  call.bwd.dy_more[0] = n_dy > 1 ? dys[1] : nullptr;
+  call.bwd.dy_more[1] = n_dy > 2 ? dys[2] : nullptr;
+  return chain_backward_impl(c, x, y, dys[0], saved, N, dx, dW, stream, call);
 }
 
 int lde_chain_backward_saved_mse(lde_chain* c, const float* x, const float* y, const float* target, const float* g_dev, float scale,
@@ -1707,12 +1523,13 @@ int lde_chain_backward_saved_mse(lde_chain* c, const float* x, const float* y, c
     c->err = "lde_chain_backward_saved_mse: NULL or unaligned target / cotangent";
     return LDE_ERR_INVALID_ARG;
   }
-  t_mse = MseSrc{target, g_dev, scale};
-  t_dy_more[0] = dy_more;
-  const int rc = saved ? lde_chain_backward_saved(c, x, y, target, saved, N, dx, dW, stream) : lde_chain_backward(c, x, y, target, N, dx, dW, stream);
-  t_mse = MseSrc{nullptr, nullptr, 0.f};
-  t_dy_more[0] = nullptr;
-  return rc;
+  if (const int rc = saved ? chain_saved_ok(c, saved, BWD_SAVED) : LDE_OK) return rc;
+  ChainCall call;
+  call.bwd.target = target;
+  call.bwd.g = g_dev;
+  call.bwd.scale = scale;
+  call.bwd.dy_more[0] = dy_more;
+  return chain_backward_impl(c, x, y, target, saved, N, dx, dW, stream, call);   // (dy is not read: the target stands in for the checks)
 }
 
 // The reconstructor under the loss, bf16 mode, without the x̂ round trip: the forward launch's last epilogue — where x̂ and the target are in
@@ -1727,18 +1544,22 @@ int lde_chain_forward_save_mse_delta(lde_chain* c, const float* x, int64_t N, fl
     c->err = "lde_chain_forward_save_mse_delta: NULL pointer or unaligned target";
     return LDE_ERR_INVALID_ARG;
   }
-  if (!c->bf16 || (c->cd.dm.sizes[c->cd.dm.nL] & 7) != 0 || t_rec) {
+  if (!c->bf16 || (c->cd.dm.sizes[c->cd.dm.nL] & 7) != 0) {
     c->err = "lde_chain_forward_save_mse_delta: bf16 mode, an output width that is a multiple of 8, not inside a grouped call";
     return LDE_ERR_UNSUPPORTED;
   }
-  t_fwd_mse = FwdMse{target, scratch, 0, true, scale};
-  const int rc = lde_chain_forward_save(c, x, N, y, saved, stream);
-  const unsigned tiles = t_fwd_mse.tiles;
-  t_fwd_mse = FwdMse{nullptr, nullptr, 0, false, 0.f};
+  int rc = chain_saved_ok(c, saved, FWD_SAVED);
+  if (rc) return rc;
+  ChainCall call;
+  call.fwd.target = target;
+  call.fwd.part = scratch;
+  call.fwd.delta = true;
+  call.fwd.scale = scale;
+  rc = chain_forward_impl(c, x, N, y, saved, stream, call);
   if (rc) return rc;
   c->delta_N = N;
   c->delta_saved = saved;
-  return loss_finalize(scratch, (int)tiles, scale, base, out, (hipStream_t)stream);
+  return loss_finalize(scratch, (int)call.fwd.tiles, scale, base, out, (hipStream_t)stream);
 }
 int lde_chain_delta_is_staged(const lde_chain* c, const float* saved, int64_t N) {
   return c && c->bf16 && c->dstage && c->delta_N == N && N >= 0 && c->delta_saved == saved && saved != nullptr;
@@ -1756,9 +1577,9 @@ int lde_chain_backward_saved_delta(lde_chain* c, const float* x, const float* g_
              "(lde_chain_forward_save_mse_delta must be the chain's last such call; lde_chain_delta_is_staged tells)";
     return LDE_ERR_INVALID_ARG;
   }
-  t_delta_g = g_dev;
-  const int rc = lde_chain_backward_saved(c, x, x, x, saved, N, dx, dW, stream);   // (y and dy are not read: δ_L′ is staged)
-  t_delta_g = nullptr;
+  ChainCall call;   // (saved is aligned: it is the pointer lde_chain_forward_save_mse_delta checked)
+  call.bwd.delta_g = g_dev;
+  const int rc = chain_backward_impl(c, x, x, x, saved, N, dx, dW, stream, call);   // (y and dy are not read: δ_L′ is staged)
   c->delta_N = -1;          // consumed: a second pullback from the same staging must not pass silently either
   c->delta_saved = nullptr;
   return rc;
@@ -1785,22 +1606,16 @@ int lde_chain_group_forward_save(int n, lde_chain* const* cs, const float* const
   if (n < 1 || !cs || !xs || !Ns || !ys) return LDE_ERR_INVALID_ARG;
   for (int i = 0; i < n; i++)
     if (!cs[i]) return LDE_ERR_INVALID_ARG;
-  if (!group_ok(n, cs) || !group_distinct(n, cs)) {
-    for (int i = 0; i < n; i++) {
-      const int rc = chain_forward_impl(cs[i], xs[i], Ns[i], ys[i], saveds ? saveds[i] : nullptr, stream);
-      if (rc) return rc;
-    }
-    return LDE_OK;
-  }
   GroupRec g;
-  t_rec = &g;
+  ChainCall call;
+  if (group_ok(n, cs) && group_distinct(n, cs)) call.rec = &g;   // else: one after the other, launched as they come
   for (int i = 0; i < n; i++) {
     g.n = i;
-    const int rc = chain_forward_impl(cs[i], xs[i], Ns[i], ys[i], saveds ? saveds[i] : nullptr, stream);
-    if (rc) { t_rec = nullptr; return rc; }
+    const int rc = chain_forward_impl(cs[i], xs[i], Ns[i], ys[i], saveds ? saveds[i] : nullptr, stream, call);
+    if (rc) return rc;
   }
+  if (!call.rec) return LDE_OK;
   g.n = n;
-  t_rec = nullptr;
   const int rc = group_flush(g, (hipStream_t)stream);
   if (rc) cs[0]->err = "lde_chain_group_forward_save: launch failed";
   return rc;
@@ -1813,23 +1628,16 @@ int lde_chain_group_backward_saved(int n, lde_chain* const* cs, const float* con
     if (!cs[i]) return LDE_ERR_INVALID_ARG;
     if (cs[i]->bf16 && !(saveds && saveds[i])) grp = false;   // (a bf16 pullback without saved activations starts with a forward launch of its own)
   }
-  grp = grp && group_distinct(n, cs);
-  if (!grp) {
-    for (int i = 0; i < n; i++) {
-      const int rc = chain_backward_impl(cs[i], xs[i], ys[i], dys[i], saveds ? saveds[i] : nullptr, Ns[i], dxs ? dxs[i] : nullptr, dWs[i], stream);
-      if (rc) return rc;
-    }
-    return LDE_OK;
-  }
   GroupRec g;
-  t_rec = &g;
+  ChainCall call;
+  if (grp && group_distinct(n, cs)) call.rec = &g;
   for (int i = 0; i < n; i++) {
     g.n = i;
-    const int rc = chain_backward_impl(cs[i], xs[i], ys[i], dys[i], saveds ? saveds[i] : nullptr, Ns[i], dxs ? dxs[i] : nullptr, dWs[i], stream);
-    if (rc) { t_rec = nullptr; return rc; }
+    const int rc = chain_backward_impl(cs[i], xs[i], ys[i], dys[i], saveds ? saveds[i] : nullptr, Ns[i], dxs ? dxs[i] : nullptr, dWs[i], stream, call);
+    if (rc) return rc;
   }
+  if (!call.rec) return LDE_OK;
   g.n = n;
-  t_rec = nullptr;
   const int rc = group_flush(g, (hipStream_t)stream);
   if (rc) cs[0]->err = "lde_chain_group_backward_saved: launch failed";
   return rc;

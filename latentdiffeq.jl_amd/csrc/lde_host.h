@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <limits>
 #include <string>
 #include <type_traits>
 
@@ -397,6 +398,80 @@ static int mlp_dispatch(int solver, F&& f) {
   if (solver == LDE_SOLVER_TSIT5) return f(std::integral_constant<int, LDE_SOLVER_TSIT5>{});
   if (solver == LDE_SOLVER_RK4) return f(std::integral_constant<int, LDE_SOLVER_RK4>{});
   return LDE_ERR_UNSUPPORTED;
+}
+
+// ---- the dense chains (csrc/lde_chain.hip's launch code asks these): tile widths, the layout of a call, the split of the
+// weight-gradient product. A tile is 16·cg columns (cg column groups); the thresholds are measurements on the MI355X.
+using lde::ChainLdsDims;
+
+// LDS bytes of a tile kernel: f32 — the input panel, 2 (forward) / 3 (pullback) hidden panels and the biases; bf16 forward — two bf16
+// panels (the input panel shares the second one's space), a third with skip layers, the biases, the chunk buffers of a wide input read
+// in place; bf16 pullback — two bf16 panels and the f32 skip-gradient panel.
+static size_t chain_lds_bytes(const ChainLdsDims& q, bool bf16, bool bwd, int cg) {
+  const size_t NC = 16 * (size_t)cg, bias = ((size_t)q.nbias + 3) & ~size_t(3);
+  if (!bf16) return (NC * q.ld0 + (bwd ? 3 : 2) * NC * q.ldh + bias) * sizeof(float);
+  if (bwd) return NC * q.ldb * 2 * 2 + NC * q.ldg * 4;
+  return (2 + (q.fpanel ? 1 : 0)) * NC * q.ldb * 2 + bias * 4 + (size_t)cg * q.xs_per_cg;
+}
+
+// Column groups per workgroup, chosen once per handle: the widest tile that still lets TWO workgroups share a CU (half the LDS each) —
+// one tile's barrier / prologue latencies are then covered by the other's MFMAs. Measured on the reconstructor (N = 12800): f32 forward
+// 64 columns 110 µs, 32 columns 107 µs; pullback 32 columns 331 µs, 16 columns 313 µs. Falls back to the widest tile that fits at all;
+// 0: none does. Candidates: 4, 2, 1 for the f32 forward; 2, 1 for the f32 pullback and for bf16 (≤ 128 registers: csrc/lde_chain_bf16.h —
+// a 64-column bf16 forward instantiation exists and is never picked here).
+static int chain_tile_pick(const ChainLdsDims& q, bool bf16, bool bwd, size_t lds_max) {
+  for (size_t lim : {lds_max / 2, lds_max})
+    for (int cg = (bf16 || bwd) ? 2 : 4; cg >= 1; cg /= 2)
+      if (chain_lds_bytes(q, bf16, bwd, cg) <= lim) return cg;
+  return 0;
+}
+
+// workgroups of a tile kernel = its grid (0 only for N < 1, which every entry point refuses)
+static int64_t chain_tiles(int64_t N, int cg) { return N < 1 ? 0 : (N - 1) / (16 * (int64_t)std::max(cg, 1)) + 1; }
+
+// Mid-size batches (a training step's N = B·T ≈ 3 200 columns): the widest tile leaves most CUs without a workgroup — 50–100 tiles on
+// 256 CUs — and a tile's time barely depends on its width (the weight fragments stream through the workgroup either way). Narrow the tile
+// until the grid has ≈ 200 workgroups (measured, GOKU training step at B = 64: 1.70 → 1.32 ms and 2.17 → 1.84 ms in two back-to-back
+// pairs; at B = 256 the grids are full and nothing changes).
+static int chain_narrow(int64_t N, int cg0) {
+  int g = std::max(cg0, 1);
+  while (g > 1 && chain_tiles(N, g) < 192) g /= 2;
+  return g;
+}
+
+// Which layout a call uses: the panel-free one (x[in×N] itself is the first layer's B operand; `cgx` column groups, 0: the chain has
+// none) when N fills one of its tiles and x is 16-byte aligned, else the one with an input panel (`cg`, 0: its panels do not fit) — and
+// the call's tile width.
+enum ChainLayout { CHAIN_NONE = 0, CHAIN_PANEL, CHAIN_GX };
+struct ChainChoice {
+  ChainLayout layout;
+  int cg;
+};
+static ChainChoice chain_call_choice(int cgx, int cg, int64_t N, bool x_aligned) {
+  if (cgx > 0 && N >= 16 * (int64_t)cgx && x_aligned) return {CHAIN_GX, chain_narrow(N, cgx)};
+  if (cg > 0) return {CHAIN_PANEL, chain_narrow(N, cg)};
+  return {CHAIN_NONE, 0};
+}
+
+// The f32 weight gradient: k_mlp_dw sees the pullback's staged 16-column slots (`total`: every tile brings cg of them) as `nvt` virtual
+// tiles of `cap` slots; (virtual tiles × jobs) ≈ one workgroup per CU — the kernel's register footprint allows one resident workgroup per
+// CU, so 256 equal shares beat 384 (a second, half-empty round).
+struct ChainDwSplit {
+  int nvt, cap;
+  int64_t total;
+};
+static ChainDwSplit chain_dw_split(int jobs, int cg, int64_t N) {
+  ChainDwSplit s;
+  s.total = chain_tiles(N, cg) * std::max(cg, 1);
+  const int64_t v = std::max<int64_t>(1, std::min<int64_t>(std::max(256 / std::max(jobs, 1), 1), s.total));
+  s.nvt = (int)v;
+  s.cap = (int)std::min<int64_t>(std::max<int64_t>((s.total + v - 1) / v, 1), std::numeric_limits<int>::max());
+  return s;
+}
+// … and the bf16 one: k_chain_dw_b splits the N rows of its operands into `parts` K-ranges of whole `chunk`-row chunks, by the same rule
+static int chain_dw_parts_bf16(int jobs, int64_t N, int chunk) {
+  const int64_t nchunks = N < 1 ? 1 : (N - 1) / std::max(chunk, 1) + 1;
+  return (int)std::min<int64_t>(std::max(256 / std::max(jobs, 1), 1), nchunks);
 }
 
 static KOpts make_opts(const lde_problem_desc& d, const double* ts, int T, int B) {

@@ -1378,11 +1378,11 @@ static int rnn_group_flush(RnnGroupRec& g, hipStream_t stream) {
         u.start[j + 1] = u.start[j] + (int)q.rgrid; u.dims[j] = q.rdm; u.args[j] = q.ra;
       }
       if (!attr[0]) {
-        if (hipFuncSetAttribute((const void*)k_mlp_dw_group<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) return LDE_ERR_HIP;
+        if (hipFuncSetAttribute((const void*)k_mlp_dw_group<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) return LDE_ERR_HIP;
         attr[0] = true;
       }
       void* argv[] = {(void*)&t};
-      (void)hipLaunchKernel((const void*)k_mlp_dw_group<1, false>, dim3(t.start[g.ndw]), dim3(512), argv, lds, stream);
+      (void)hipLaunchKernel((const void*)k_mlp_dw_group<1>, dim3(t.start[g.ndw]), dim3(512), argv, lds, stream);
       if (g.ns0 >= 2) {   // … and the initial-state sums ride on the slab sums' launch
         ReduceState0Tables rs{};
         rs.u = u;

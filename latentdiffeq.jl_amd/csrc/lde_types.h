@@ -76,6 +76,16 @@ struct MlpLds {
   int mlp4_blocks = 0;        // … and its workgroups
 };
 
+// What the LDS carve-up of a dense chain's tile kernels depends on (csrc/lde_host.h: chain_lds_bytes / chain_tile_pick); filled from
+// ChainDims / BfDims, whose layouts the kernels of csrc/lde_chain.hip and csrc/lde_chain_bf16.h walk.
+struct ChainLdsDims {
+  int ld0 = 0, ldh = 0;       // f32: stride (floats) of the input panel (0: x is read in place) and of the hidden / gradient panels
+  int nbias = 0;              // biases of all layers (floats), kept in LDS by the forward kernels
+  int ldb = 0, ldg = 0;       // bf16: stride (elements) of the bf16 panels, stride (floats) of the f32 skip-gradient panel
+  int fpanel = 0;             // bf16 forward: a third panel (chains with skip layers)
+  size_t xs_per_cg = 0;       // bf16 forward reading x in place: bytes of the first layer's chunk buffers per column group (else 0)
+};
+
 // Options handed to every kernel by value (mirrors the `kwargs...` splat into solve()).
 struct KOpts {
   float abstol, reltol;

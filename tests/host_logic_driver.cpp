@@ -103,6 +103,24 @@ int main() {
         default: d.beta2 = hostile_double(); break;
       }
     }
+    {   // the dense chains' choices with hostile numbers: no division by zero, no signed overflow, never an empty grid for N ≥ 1
+      const int64_t N = (rnd() & 1) ? (int64_t)hostile_int() : (rnd() & 1) ? std::numeric_limits<int64_t>::max() - (int64_t)(rnd() % 64) : (int64_t)(rnd() % 100000);
+      const int cg = hostile_int(), jobs = hostile_int();
+      const int g = chain_narrow(N, cg);
+      assert(g >= 1 && (cg < 1 || g <= cg) && (N < 1) == (chain_tiles(N, cg) == 0) && chain_tiles(N, g) >= chain_tiles(N, cg));
+      const ChainChoice ch = chain_call_choice(hostile_int(), cg, N, rnd() & 1);
+      assert(ch.layout == CHAIN_NONE ? ch.cg == 0 : ch.cg >= 1);
+      if (ch.layout != CHAIN_NONE && N >= 1) assert(chain_tiles(N, ch.cg) >= 1);
+      const ChainDwSplit sp = chain_dw_split(jobs, cg, N);
+      assert(sp.nvt >= 1 && sp.nvt <= 256 && sp.cap >= 1 && (N >= 1 ? sp.total >= 1 : sp.total == 0));
+      if (sp.total < (int64_t)1 << 40) assert((int64_t)sp.nvt * sp.cap >= sp.total && sp.nvt <= std::max<int64_t>(sp.total, 1));   // every slot in a virtual tile
+      const int parts = chain_dw_parts_bf16(jobs, N, (rnd() & 1) ? 64 : hostile_int());
+      assert(parts >= 1 && parts <= 256);
+      lde::ChainLdsDims q;
+      q.ld0 = hostile_int(); q.ldh = hostile_int(); q.nbias = hostile_int(); q.ldb = hostile_int(); q.ldg = hostile_int(); q.fpanel = (int)(rnd() & 1); q.xs_per_cg = (size_t)rnd();
+      const int t = chain_tile_pick(q, rnd() & 1, rnd() & 1, (rnd() & 1) ? (size_t)160 * 1024 : (size_t)rnd());
+      assert(t == 0 || t == 1 || t == 2 || t == 4);
+    }
     const int rc = validate(&d, &why);
     (void)num_weights(&d);                                       // (defined for ANY description: n_layers is clamped to the struct's capacity)
     if (rc == LDE_OK) {
@@ -477,7 +495,48 @@ int main() {
       assert(called == (solver == LDE_SOLVER_TSIT5 || solver == LDE_SOLVER_RK4) && rc == (called ? LDE_OK : LDE_ERR_UNSUPPORTED));
     }
   }
+  // 10. the dense chains (csrc/lde_chain.hip's launch code asks these): LDS bytes, tile widths, the layout of a call, the weight-gradient split
+  {
+    const size_t CAP = 160 * 1024;
+    // the reconstructor 2-200-200-200-784: input panel stride 40, hidden panels 232, 3·200 + 784 biases
+    lde::ChainLdsDims rec;
+    rec.ld0 = 40; rec.ldh = 232; rec.nbias = 1384;
+    assert(chain_lds_bytes(rec, false, false, 4) == 134560 && chain_lds_bytes(rec, false, false, 2) == 70048 && chain_lds_bytes(rec, false, false, 1) == 37792);
+    assert(chain_lds_bytes(rec, false, true, 2) == 99744 && chain_lds_bytes(rec, false, true, 1) == 52640);
+    assert(chain_tile_pick(rec, false, false, CAP) == 2 && chain_tile_pick(rec, false, true, CAP) == 1);   // two workgroups per CU: the instances the profiles show
+    // its bf16 form: panels of stride 272 elements (skip layers: a third forward panel), the f32 gradient panel 232 floats
+    rec.ldb = 272; rec.ldg = 232; rec.fpanel = 1;
+    assert(chain_lds_bytes(rec, true, false, 2) == 3 * 32 * 272 * 2 + 1384 * 4 && chain_lds_bytes(rec, true, true, 2) == 32 * 272 * 4 + 32 * 232 * 4);
+    assert(chain_tile_pick(rec, true, false, CAP) == 2 && chain_tile_pick(rec, true, true, CAP) == 2);
+    rec.xs_per_cg = 9216;   // a wide input read in place: the chunk buffers grow with the column groups
+    assert(chain_lds_bytes(rec, true, false, 2) == 3 * 32 * 272 * 2 + 1384 * 4 + 2 * 9216 && chain_lds_bytes(rec, true, true, 2) == 32 * 272 * 4 + 32 * 232 * 4);
+    // half the LDS first, then all of it, then nothing: 512-wide hidden panels (stride 520) with a 32-wide input (stride 40)
+    lde::ChainLdsDims wide;
+    wide.ld0 = 40; wide.ldh = 520; wide.nbias = 1064;
+    assert(chain_lds_bytes(wide, false, false, 1) == 73376 && chain_lds_bytes(wide, false, false, 2) == 142496 && chain_lds_bytes(wide, false, true, 1) == 106656);
+    assert(chain_tile_pick(wide, false, false, CAP) == 1 && chain_tile_pick(wide, false, true, CAP) == 1);   // 16 columns fit half; the pullback only the whole
+    assert(chain_tile_pick(wide, false, false, 2 * 73376 - 1) == 2 && chain_tile_pick(wide, false, true, 106655) == 0);
+    wide.nbias = 5; wide.ld0 = 0;
+    assert(chain_lds_bytes(wide, false, false, 1) == (2 * 16 * 520 + 8) * 4);                                // biases rounded up to 4 floats
+    // the narrowing rule: halve the tile until the grid has 192 workgroups
+    assert(chain_narrow(3200, 4) == 1 && chain_narrow(12800, 2) == 2 && chain_narrow(12288, 4) == 4 && chain_narrow(12224, 4) == 2);
+    assert(chain_narrow(6144, 2) == 2 && chain_narrow(6112, 2) == 1 && chain_narrow(1, 4) == 1 && chain_narrow(3072, 1) == 1 && chain_narrow(1 << 20, 4) == 4);
+    assert(chain_tiles(1, 4) == 1 && chain_tiles(64, 4) == 1 && chain_tiles(65, 4) == 2 && chain_tiles(37, 1) == 3 && chain_tiles(0, 1) == 0);
+    // the layout of a call: x in place when the chain has that layout, N fills a tile of it and x is 16-byte aligned; else the input panel; else none
+    auto is = [](ChainChoice c, ChainLayout l, int cg) { return c.layout == l && c.cg == cg; };
+    assert(is(chain_call_choice(2, 2, 12800, true), CHAIN_GX, 2) && is(chain_call_choice(2, 1, 12800, false), CHAIN_PANEL, 1));
+    assert(is(chain_call_choice(4, 2, 64, true), CHAIN_GX, 1) && is(chain_call_choice(4, 2, 63, true), CHAIN_PANEL, 1) && is(chain_call_choice(0, 4, 12288, true), CHAIN_PANEL, 4));
+    assert(is(chain_call_choice(2, 0, 31, true), CHAIN_NONE, 0) && is(chain_call_choice(2, 0, 32, false), CHAIN_NONE, 0) && is(chain_call_choice(2, 0, 32, true), CHAIN_GX, 1));
+    assert(is(chain_call_choice(0, 0, 1000, true), CHAIN_NONE, 0) && is(chain_call_choice(2, 2, 6144, true), CHAIN_GX, 2) && is(chain_call_choice(2, 2, 6112, true), CHAIN_GX, 1));
+    // the weight-gradient split: (virtual tiles × jobs) ≈ 256 workgroups, never more virtual tiles than slots
+    auto split = [](int jobs, int cg, int64_t N, int nvt, int cap, int64_t total) { const ChainDwSplit s = chain_dw_split(jobs, cg, N); return s.nvt == nvt && s.cap == cap && s.total == total; };
+    assert(split(8, 2, 12800, 32, 25, 800) && split(300, 1, 37, 1, 3, 3) && split(4, 1, 16, 1, 1, 1) && split(8, 2, 37, 4, 1, 4) && split(8, 1, 3200, 32, 7, 200));
+    assert(split(8, 2, 300000, 32, 586, 18750) && split(1, 1, 1 << 20, 256, 256, 65536));
+    assert(chain_dw_parts_bf16(8, 12800, 64) == 32 && chain_dw_parts_bf16(8, 100, 64) == 2 && chain_dw_parts_bf16(300, 12800, 64) == 1);
+    assert(chain_dw_parts_bf16(8, 64, 64) == 1 && chain_dw_parts_bf16(8, 65, 64) == 2 && chain_dw_parts_bf16(1, 1 << 20, 64) == 256);
+  }
   std::printf("host logic under ASan + UBSan: %d accepted, %d refused hostile descriptions; forward mappings as measured; "
               "pullback mappings, ring shapes and kernel dispatch checked; MLP family mappings as measured, reserve rows and solver dispatch checked\n", n_ok, n_bad);
+  std::printf("dense chains: LDS bytes, tile picks, call layouts, tile narrowing and weight-gradient splits as measured; hostile sizes checked\n");
   return 0;
 }

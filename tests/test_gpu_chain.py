@@ -454,3 +454,110 @@ def test_group_entry_points_validate():
     assert lib.lde_chain_group_forward_save(2, hs, hs, (C.c_int64 * 2)(1, 1), hs, None, None) == -1        # NULL chain handle
     assert lib.lde_chain_group_backward_saved(2, hs, hs, hs, hs, None, (C.c_int64 * 2)(1, 1), None, hs, None) == -1
 
+
+
+@pytest.mark.parametrize("dtype,out", [("f32", 1), ("bf16", 1), ("bf16", 8)], ids=["f32", "bf16", "bf16_out8"])
+def test_extras_of_one_entry_point_do_not_reach_the_next(dtype, out):
+    """What a call carries beyond its arrays — further output gradients, the loss target and cotangent, the staged-δ cotangent, the loss
+    target of the forward pass — belongs to THAT call: on one handle, after each of lde_chain_backward_saved_sum (three arrays),
+    lde_chain_backward_saved_mse (with a further cotangent), two refused lde_chain_backward_saved_sum calls, the staged-δ pair (bf16) and
+    lde_chain_forward_save_mse, a plain lde_chain_forward_save + lde_chain_backward_saved gives the bits a fresh handle gave. C ABI through
+    ctypes; 16 → 200 → out (relu, softplus), N = 37: three 16-column tiles, the last ragged; overwrite mode. out = 1: the latent_out head
+    (lde_chain_forward_save_mse_delta needs an output width that is a multiple of 8 and is refused there); out = 8: the pair runs.
+    The three-array sum is formed as (dy₁ + dy₂) + dy₃ in f32 where the output gradient is read: against the plain call on the array
+    summed beforehand it may differ by the rounding of a three-term sum, 3·2⁻²⁴ of the largest entry."""
+    import ctypes as C
+    import torch
+    from latentdiffeq_amd import _lib as L
+    from tests.gpu_util import NativeChain
+    sizes, acts, N = (16, 200, out), (O.CACT_RELU, O.CACT_SOFTPLUS), 37
+    W = O.mlp_weights(sizes, seed=11)
+    g = torch.Generator().manual_seed(3)
+    dev = "cuda"
+    x = torch.randn(N, 16, generator=g).to(dev)
+    dys = [(torch.randn(N, out, generator=g) / N).to(dev) for _ in range(3)]
+    target = torch.rand(N, out, generator=g).to(dev)
+    gdev = torch.tensor([1.3], device=dev)
+    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
+
+    def handle():
+        nat = NativeChain(sizes, acts)
+        nat.set_weights(W)
+        nat.set_dtype(dtype)
+        assert nat.lib.lde_chain_set_accumulate(nat.h, 0) == 0
+        return nat
+
+    def plain(nat, dy):
+        lib, s = nat.lib, C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        y, dx, dW = torch.full((N, out), 7.0, device=dev), torch.full((N, 16), 7.0, device=dev), torch.full((nat.nW,), 7.0, device=dev)
+        saved = torch.full((int(lib.lde_chain_saved_floats(nat.h, N)),), 7.0, device=dev)
+        assert lib.lde_chain_forward_save(nat.h, vp(x), N, vp(y), vp(saved), s) == 0
+        assert lib.lde_chain_backward_saved(nat.h, vp(x), vp(y), vp(dy), vp(saved), N, vp(dx), vp(dW), s) == 0
+        torch.cuda.synchronize()
+        return y.cpu().numpy(), dx.cpu().numpy(), dW.cpu().numpy(), saved, y
+
+    fresh = handle()
+    ref = plain(fresh, dys[0])[:3]
+    presum = plain(fresh, (dys[0] + dys[1]) + dys[2])[:3]
+    nat = handle()
+    lib, s = nat.lib, C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    y0, dx0, dW0, saved, yd = plain(nat, dys[0])
+    assert np.array_equal(y0, ref[0]) and np.array_equal(dx0, ref[1]) and np.array_equal(dW0, ref[2])
+
+    def still_plain(after):
+        got = plain(nat, dys[0])
+        for a, b, what in zip(got[:3], ref, ("y", "dx", "dW")):
+            assert np.array_equal(a, b), (after, what, float(np.abs(a - b).max()))
+
+    dx, dW = torch.full((N, 16), 7.0, device=dev), torch.full((nat.nW,), 7.0, device=dev)
+    scratch = torch.zeros((int(lib.lde_chain_mse_scratch_floats(nat.h, N)),), device=dev)
+    loss = torch.zeros((1,), device=dev)
+    # (i) three output gradients, summed where they are read
+    arr = (C.c_void_p * 4)(*[t.data_ptr() for t in dys], dys[0].data_ptr())
+    assert lib.lde_chain_backward_saved_sum(nat.h, vp(x), vp(yd), 3, arr, vp(saved), N, vp(dx), vp(dW), s) == 0
+    torch.cuda.synchronize()
+    for a, b, what in ((dx.cpu().numpy(), presum[1], "dx"), (dW.cpu().numpy(), presum[2], "dW")):
+        err, bound = float(np.abs(a - b).max()), 3 * 2.0 ** -24 * float(np.abs(b).max())
+        print(f"saved_sum vs pre-summed {dtype} out={out} {what}: {err:.3e} (bound {bound:.3e})")
+        assert err <= bound, (what, err, bound)
+    still_plain("saved_sum")
+    # (ii) the loss's cotangent formed in the kernel, plus a further one
+    assert lib.lde_chain_backward_saved_mse(nat.h, vp(x), vp(yd), vp(target), vp(gdev), 0.25, vp(dys[1]), vp(saved), N, vp(dx), vp(dW), s) == 0
+    torch.cuda.synchronize()
+    # (the kernel forms 2·(g·scale)·(y − target) + dy_more in f32, each product and sum rounded on its own — the same four operations as
+    #  the torch expression below: against the plain call on that array at most their four roundings, 4·2⁻²⁴ of the largest entry)
+    dy_mse = (2.0 * (gdev * 0.25)) * (yd - target) + dys[1]
+    want_mse = plain(fresh, dy_mse)[:3]
+    for a, b, what in ((dx.cpu().numpy(), want_mse[1], "dx"), (dW.cpu().numpy(), want_mse[2], "dW")):
+        err, bound = float(np.abs(a - b).max()), 4 * 2.0 ** -24 * float(np.abs(b).max())
+        print(f"saved_mse vs the cotangent formed beforehand {dtype} out={out} {what}: {err:.3e} (bound {bound:.3e})")
+        assert err <= bound, (what, err, bound)
+    still_plain("saved_mse")
+    # (iii) refused calls: four arrays; a misaligned second array
+    assert lib.lde_chain_backward_saved_sum(nat.h, vp(x), vp(yd), 4, arr, vp(saved), N, vp(dx), vp(dW), s) == -1      # LDE_ERR_INVALID_ARG
+    assert len(lib.lde_chain_last_error(nat.h)) > 0
+    odd = torch.zeros((N * out + 1,), device=dev)
+    arr2 = (C.c_void_p * 2)(dys[0].data_ptr(), odd.data_ptr() + 4)
+    assert lib.lde_chain_backward_saved_sum(nat.h, vp(x), vp(yd), 2, arr2, vp(saved), N, vp(dx), vp(dW), s) == -1
+    assert b"unaligned" in lib.lde_chain_last_error(nat.h)
+    still_plain("refused saved_sum")
+    # (iv) bf16: the forward pass leaves δ_L′, the pullback starts from it
+    if dtype == "bf16":
+        rc = lib.lde_chain_forward_save_mse_delta(nat.h, vp(x), N, vp(yd), vp(saved), vp(target), 0.25, None, vp(loss), vp(scratch), s)
+        if out % 8 == 0:
+            assert rc == 0 and lib.lde_chain_delta_is_staged(nat.h, vp(saved), N) == 1
+            assert lib.lde_chain_backward_saved_delta(nat.h, vp(x), vp(gdev), vp(saved), N, vp(dx), vp(dW), s) == 0
+            torch.cuda.synchronize()
+            assert torch.isfinite(dx).all() and torch.isfinite(dW).all() and lib.lde_chain_delta_is_staged(nat.h, vp(saved), N) == 0
+        else:
+            assert rc == -2 and len(lib.lde_chain_last_error(nat.h)) > 0                                               # LDE_ERR_UNSUPPORTED
+            assert lib.lde_chain_backward_saved_delta(nat.h, vp(x), vp(gdev), vp(saved), N, vp(dx), vp(dW), s) == -1   # nothing staged
+        still_plain("staged delta")
+    # (v) the loss from the forward pass's last epilogue
+    ym = torch.full((N, out), 7.0, device=dev)
+    assert lib.lde_chain_forward_save_mse(nat.h, vp(x), N, vp(ym), vp(saved), vp(target), 0.25, None, vp(loss), vp(scratch), s) == 0
+    torch.cuda.synchronize()
+    assert np.array_equal(ym.cpu().numpy(), ref[0])
+    want = 0.25 * float(((ym.double() - target.double()) ** 2).sum())
+    assert abs(float(loss) - want) <= 1e-5 * want
+    still_plain("forward_save_mse")

@@ -2,7 +2,7 @@
 not available on this pool): (1) the oracle — everything the parity tests trust — driven at small, ragged, degenerate and failing shapes
 through every family of its entry points (oracle/asan_driver.c, f32 and f64 builds); (2) the C ABI's host-side logic — validation of a
 problem description, the weight count, the step-record layout arithmetic, the option block, grid checks, the analytic path's kernel
-choices and the MLP path's kernel families (csrc/lde_host.h, which lde_api.hip and the launch code are built from) — with 200 000 hostile descriptions (tests/host_logic_driver.cpp)."""
+choices, the MLP path's kernel families and the dense chains' tile / layout / split choices (csrc/lde_host.h, which lde_api.hip and the launch code are built from) — with 200 000 hostile descriptions (tests/host_logic_driver.cpp)."""
 import os
 import shutil
 import subprocess
@@ -38,6 +38,7 @@ def test_c_abi_host_logic_under_asan_ubsan(tmp_path):
     assert "accepted" in r.stdout and "forward mappings as measured" in r.stdout
     assert "pullback mappings, ring shapes and kernel dispatch checked" in r.stdout
     assert "MLP family mappings as measured, reserve rows and solver dispatch checked" in r.stdout
+    assert "dense chains: LDS bytes, tile picks, call layouts, tile narrowing and weight-gradient splits as measured; hostile sizes checked" in r.stdout
 
 
 def test_lde_api_is_built_from_the_checked_logic():
@@ -56,5 +57,12 @@ def test_lde_api_is_built_from_the_checked_logic():
     assert "lde_host::mlp_forward_mapping(" in mlp and "lde_host::mlp_adjoint_mapping(" in mlp
     for gone in ("_applicable(", "attr_set", "65536", "tune.mlp64", "tune.mlpv", "tune.mlpw", "tune.mlpb", "tune.mlp4"):
         assert gone not in mlp, gone
+    # the dense chains: the tile widths, the layout of a call and the weight-gradient split come from lde_host.h; the launch code keeps no
+    # threshold, no per-call state outside its arguments and no per-function attribute table
+    chain = open(os.path.join(ROOT, "latentdiffeq.jl_amd", "csrc", "lde_chain.hip")).read()
+    for used in ("lde_host::chain_call_choice(", "lde_host::chain_dw_split(", "lde_host::chain_dw_parts_bf16(", "lde_host::chain_tile_pick(", "lde_host::chain_lds_bytes("):
+        assert used in chain, used
+    for gone in ("thread_local", "attr[", "< 192", "256 /"):
+        assert gone not in chain, gone
     for fn in ("static int validate(", "static size_t rec_bytes(", "static lde::StepRec rec_view(", "static lde::KOpts make_opts("):
         assert fn not in src, fn
