@@ -52,12 +52,18 @@ enum lde_rhs_kind {
   LDE_RHS_PENDULUM          = 0,  /* du = [y, -G/L sin x], G=10, L=p[1]    [REF examples/pendulum_friction-less/pendulum.jl:19-26] */
   LDE_RHS_PENDULUM_FRICTION = 1,  /* ... - (b/m) y, b=0.7, m=1             [REF pendulum.jl:65-74] */
   LDE_RHS_MLP               = 2,  /* Chain(Dense(relu)...Dense)            [REF examples/pendulum_friction-less/nODE.jl:12-14] */
-  LDE_RHS_PENDULUM_PLUS_MLP = 3   /* pendulum(z,L) + MLP(z): BASELINE.json configs[2] */
+  LDE_RHS_PENDULUM_PLUS_MLP = 3,  /* pendulum(z,L) + MLP(z): BASELINE.json configs[2] */
+  LDE_RHS_SPENDULUM         = 4   /* the stochastic pendulum: dx = v dt + σ dW₁, dv = −(G/L) sin x dt + σ dW₂, G=10, L=p[1], σ=0.01 (diagonal,
+                                     additive, constant: Itô = Stratonovich)   [REF examples/pendulum_friction-less/pendulum.jl:93-140].
+                                     Solvers LDE_SOLVER_EM / LDE_SOLVER_EULER_HEUN, LDE_SENSE_FORWARD_DUAL; see "the stochastic pendulum" below */
 };
 
 enum lde_solver {
   LDE_SOLVER_TSIT5 = 0,           /* Tsit5()  [REF pendulum.jl:11], [REF nODE.jl:15] */
-  LDE_SOLVER_RK4   = 1            /* RK4(), fixed step only (adaptive=0, dt=h) — BASELINE.json configs[1] */
+  LDE_SOLVER_RK4   = 1,           /* RK4(), fixed step only (adaptive=0, dt=h) — BASELINE.json configs[1] */
+  LDE_SOLVER_EM    = 2,           /* StochasticDiffEq's EM() (Euler–Maruyama), fixed step: y' = y + h·f(y) + ΔW. LDE_RHS_SPENDULUM only */
+  LDE_SOLVER_EULER_HEUN = 3       /* StochasticDiffEq's EulerHeun(), fixed step: ȳ = y + h·f(y) + ΔW, y' = y + (h/2)·(f(y) + f(ȳ)) + ΔW
+                                     (the same ΔW in both lines). LDE_RHS_SPENDULUM only */
 };
 
 enum lde_batching {
@@ -103,7 +109,8 @@ enum lde_sensealg {
                                            the dual record (below); lde_adjoint forms dz0 = Σ_j J_j[:, 0:2]ᵀ dz_out_j, dθ = Σ_j J_j[:, 2]ᵀ dz_out_j
                                            from it and nothing else (dW must be NULL). A failed trajectory: NaN ẑ block, retcode != 0, zero
                                            gradients. Analytic right-hand sides (LDE_RHS_PENDULUM, LDE_RHS_PENDULUM_FRICTION) with
-                                           LDE_BATCH_PER_TRAJECTORY, Tsit5 adaptive or fixed-step and RK4 fixed-step; any other description gives
+                                           LDE_BATCH_PER_TRAJECTORY, Tsit5 adaptive or fixed-step and RK4 fixed-step — and LDE_RHS_SPENDULUM with
+                                           its two fixed-step schemes, whose only sensealg this is; any other description gives
                                            LDE_ERR_UNSUPPORTED (lde_desc_error names the missing piece). Opt-in: lde_problem_desc_default keeps
                                            LDE_SENSE_DISCRETE. */
 };
@@ -199,6 +206,42 @@ void lde_destroy(lde_handle* h);
 int lde_set_weights(lde_handle* h, const float* flat_host, int64_t n);
 /* Same from a DEVICE pointer (async copy on `stream`). */
 int lde_set_weights_device(lde_handle* h, const float* flat_dev, int64_t n, void* stream);
+
+/* ---- the stochastic pendulum (LDE_RHS_SPENDULUM): the reference's `SPendulum` plug-in [REF examples/pendulum_friction-less/pendulum.jl:93-140] ----
+ * Description: state_dim = 2, param_dim = 1, no layers, augment_dim = 0, LDE_BATCH_PER_TRAJECTORY, adaptive = 0 with a finite dt > 0, solver
+ * LDE_SOLVER_EM or LDE_SOLVER_EULER_HEUN, sensealg LDE_SENSE_FORWARD_DUAL; anything else is LDE_ERR_UNSUPPORTED and lde_desc_error names the
+ * missing piece (another sensealg: "use LDE_SENSE_FORWARD_DUAL"). Arithmetic is f32, as in the other pendulum kernels.
+ *
+ * Deviation from the reference, stated: its default solver SOSRI() is NOT reproduced — it is adaptive with rejection sampling with memory,
+ * and its random stream could not be matched in any case. The two fixed-step schemes of StochasticDiffEq above are served instead. With
+ * σ = 0.01 their strong order 1 in the (additive) noise is not what limits accuracy; the order of the drift is (EM: 1, EulerHeun: 2) —
+ * hence EulerHeun is the Python mirror's default.
+ *
+ * The substep rule. Save times are hit exactly; nothing is interpolated across noise. For j = 1 … T−1: D_j = ts[j] − ts[j−1] (f64),
+ * n_j = max(1, ceil(D_j/dt − 1e-9)) equal substeps of h_j = D_j/n_j; the state advances by h = (float)h_j and ΔW = (0.01f·sqrtf(h))·ξ.
+ * ẑ(ts[0]) = ẑ₀. The substep index s runs 0 … N−1 over the whole solve, N = Σ_j n_j — the same for every trajectory (the grid is shared).
+ * N > maxiters: LDE_RET_MAXITERS for every trajectory; a non-finite state: LDE_RET_NONFINITE; a failed trajectory gets a NaN block, zero
+ * Jacobians and zero gradients. Statistics: naccept = N per trajectory, nreject = 0, nfe = 1 (EM) or 2 (EulerHeun) per substep.
+ *
+ * The noise is a pure function of (seed, trajectory, substep) — nothing depends on the launch geometry, so forward, pullback, shards of a
+ * batch and replays of a captured graph see the same path. Generator: Philox4x32-10, lde_randn's device code. For trajectory b (0-based
+ * within the call) and substep s: key = seed (low word, high word), counter = (first_trajectory + b, s, low word of off, high word of off)
+ * with off = offset + (epoch_dev ? *epoch_dev : 0); (ξ_x, ξ_v) = the Box–Muller pair of output words 0 and 1 by lde_randn's map,
+ * u = ((w >> 8) + ½)/2²⁴, (√(−2 ln u₁)·cos 2πu₂, √(−2 ln u₁)·sin 2πu₂); words 2 and 3 are unused. In lde_randn's terms: outputs 4b and
+ * 4b + 1 of a call with call = s (first_trajectory = 0).
+ *
+ * The gradient [REF pendulum.jl:103: sensalg = ForwardDiffSensitivity()]: with a fixed step there is no error norm, so it is the exact derivative
+ * of the scheme along the drawn path. The forward solve carries values and partials ∂/∂(x₀, v₀, L) (seeds e₀, e₁, 0; the noise has zero
+ * partials) and writes J_j into the dual record (layout below, under "step records"); lde_adjoint contracts it (dW must be NULL).
+ * lde_step_record_bytes / lde_set_step_record / lde_step_record_status (never an overflow) and option "step_trace" (start time and size
+ * of every substep) keep their dual-record meaning.
+ *
+ * lde_set_noise: seed, offset, first_trajectory and the device word of the NEXT lde_forward calls on this handle (defaults: 0, 0, 0,
+ * NULL). May be called between solves; `epoch_dev` (device int64, or NULL) is read by the kernel at run time, as lde_randn reads its
+ * own: inside a captured step it is the optimiser's step count, and every replay draws fresh noise. A batch sharded by trajectory passes
+ * each shard's first global trajectory index as `first_trajectory`: sharded and unsharded solves then draw the same path.
+ * LDE_ERR_UNSUPPORTED on a handle of another right-hand side. */
+int lde_set_noise(lde_handle* h, uint64_t seed, uint64_t offset, uint64_t first_trajectory, const int64_t* epoch_dev);
 
 /* Pre-size the handle's workspace for batches up to B and T save points (so that later
  * lde_forward/lde_adjoint calls allocate nothing and can be captured in a hipGraph). */

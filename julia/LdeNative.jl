@@ -16,6 +16,7 @@ module LdeNative
 
 using AMDGPU, ChainRulesCore, Flux
 using OrdinaryDiffEq: Tsit5, RK4                       # the solver tags the `diffeq` structs carry [REF src/LatentDiffEq.jl:3]
+using StochasticDiffEq: EM, EulerHeun                  # the two fixed-step schemes served for `SPendulum` (its default SOSRI() is not: include/lde.h)
 using SciMLSensitivity: ForwardDiffSensitivity, InterpolatingAdjoint, BacksolveAdjoint   # … and the sensealg tags [REF src/LatentDiffEq.jl:5]
 import ..LatentDiffEq: diffeq_layer, transform_after_diffeq, Decoder, GOKU, LatentODE
 
@@ -74,19 +75,37 @@ sensealg_code(s::BacksolveAdjoint)      = s.checkpointing ? LDE_SENSE_BACKSOLVE_
 sensealg_code(::Any)                    = LDE_SENSE_DISCRETE            # (any other discrete-exact tag, e.g. ReverseDiffAdjoint)
 solver_code(::Tsit5) = Int32(0)
 solver_code(::RK4)   = Int32(1)                                         # fixed step only: adaptive = false, dt = h through kwargs
+solver_code(::EM)        = Int32(2)                                     # LDE_SOLVER_EM          } `SPendulum` (rhs_kind 4) only, fixed step:
+solver_code(::EulerHeun) = Int32(3)                                     # LDE_SOLVER_EULER_HEUN  } dt = h through kwargs
+const LDE_RHS_SPENDULUM = Int32(4)
 
 # one handle per `diffeq` struct, built lazily from its fields (solver, sensealg, kwargs...)  [REF GOKU.jl:105-108]. The analytic right-hand
 # sides are a closed menu (include/lde.h: lde_rhs_kind) and the example structs live outside the package
 # [REF examples/pendulum_friction-less/pendulum.jl], so the example names its kind with one line next to its struct:
-#     LatentDiffEq.LdeNative.rhs_kind(::Pendulum) = 0            # LDE_RHS_PENDULUM;  Pendulum_friction: 1
+#     LatentDiffEq.LdeNative.rhs_kind(::Pendulum) = 0            # LDE_RHS_PENDULUM;  Pendulum_friction: 1;  SPendulum: 4
+# `SPendulum` [REF examples/pendulum_friction-less/pendulum.jl:93-140] → kind 4 with `solver = EM()` or `EulerHeun()` and `dt` in its kwargs
+# (its default SOSRI() is refused: LDE_ERR_UNSUPPORTED, the stated deviation of include/lde.h). Its ForwardDiffSensitivity() is
+# LDE_SENSE_FORWARD_DUAL whatever DUAL_NORM says (the only sensealg of that kind), the step is fixed, and every forward call draws fresh
+# noise: `lde_set_noise(seed = NOISE_SEED[], offset = calls so far)` — the pullback contracts the Jacobians its own forward left in the
+# dual record, so it needs no noise of its own.
 rhs_kind(diffeq) = error("LdeNative: no native right-hand side for $(typeof(diffeq)); define LdeNative.rhs_kind(::$(nameof(typeof(diffeq))))")
 const _handles = IdDict{Any,LdeHandle}()
 desc_kwargs(kw) = (k => (k === :adaptive ? Int32(v) : v) for (k, v) in pairs(kw) if k !== :saveat)
 function native(diffeq)                                                   # GOKU path: an analytic right-hand side
     get!(_handles, diffeq) do
-        LdeHandle(LdeDesc(; rhs_kind = rhs_kind(diffeq), solver = solver_code(diffeq.solver), sensealg = sensealg_code(diffeq.sensealg),
+        kind = Int32(rhs_kind(diffeq)); sde = kind == LDE_RHS_SPENDULUM
+        sa = sde && diffeq.sensealg isa ForwardDiffSensitivity ? LDE_SENSE_FORWARD_DUAL : sensealg_code(diffeq.sensealg)
+        LdeHandle(LdeDesc(; rhs_kind = kind, solver = solver_code(diffeq.solver), sensealg = sa, (sde ? (; adaptive = Int32(0)) : (;))...,
                           desc_kwargs(diffeq.kwargs)...))
     end
+end
+const NOISE_SEED = Ref(UInt64(0))
+const _noise_calls = IdDict{Any,UInt64}()
+function next_noise!(diffeq, h::LdeHandle)                                # SPendulum: a fresh offset per forward call; no-op for the other kinds
+    Int32(rhs_kind(diffeq)) == LDE_RHS_SPENDULUM || return
+    off = get(_noise_calls, diffeq, UInt64(0)); _noise_calls[diffeq] = off + 1
+    rc = ccall((:lde_set_noise, liblde), Cint, (Ptr{Cvoid}, UInt64, UInt64, UInt64, Ptr{Int64}), h.ptr, NOISE_SEED[], off, UInt64(0), C_NULL)
+    rc == 0 || error(unsafe_string(ccall((:lde_last_error, liblde), Cstring, (Ptr{Cvoid},), h.ptr)))
 end
 function native_node(diffeq)                                              # LatentODE path: `NODE` [REF examples/pendulum_friction-less/nODE.jl:3-32]
     get!(_handles, diffeq) do
@@ -115,6 +134,7 @@ end
 # --- the two methods that replace the bodies of [REF GOKU.jl:98-130] and [REF LatentODE.jl:61-78] ---------------
 function diffeq_layer(decoder::Decoder{T}, l̂, t) where {T<:GOKU}
     ẑ₀, θ̂ = l̂
+    next_noise!(decoder.diffeq, native(decoder.diffeq))
     ẑ, _ = lde_forward!(native(decoder.diffeq), ẑ₀, θ̂, t, size(ẑ₀, 1))
     ẑ = transform_after_diffeq(permutedims(ẑ, [1, 3, 2]), decoder.diffeq)   # hook sees [D×T×B] as today [REF GOKU.jl:124]
     return permutedims(ẑ, [1, 3, 2])
@@ -135,6 +155,7 @@ function ChainRulesCore.rrule(::typeof(diffeq_layer), decoder::Decoder{T}, l̂, 
     # LDE_SENSE_DISCRETE (the default, as in the reference): this solve's accepted steps travel with THIS pullback (Zygote may hold several
     # forwards of one `diffeq` before their pullbacks): a record per rrule, handed over before lde_forward and before lde_adjoint
     rec = new_step_record(h, h.sensealg, B, Tn)
+    next_noise!(decoder.diffeq, h)
     ẑ, ts = with_step_record(h, rec) do
         lde_forward!(h, ẑ₀, θ̂, t, size(ẑ₀, 1))
     end

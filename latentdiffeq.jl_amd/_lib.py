@@ -15,8 +15,8 @@ LIB_PATH = os.environ.get("LDE_LIB_PATH") or os.path.join(HERE, "liblde.so")
 LDE_ABI_VERSION = 1
 LDE_MAX_LAYERS = 6
 
-RHS_PENDULUM, RHS_PENDULUM_FRICTION, RHS_MLP, RHS_PENDULUM_PLUS_MLP = 0, 1, 2, 3
-SOLVER_TSIT5, SOLVER_RK4 = 0, 1
+RHS_PENDULUM, RHS_PENDULUM_FRICTION, RHS_MLP, RHS_PENDULUM_PLUS_MLP, RHS_SPENDULUM = 0, 1, 2, 3, 4
+SOLVER_TSIT5, SOLVER_RK4, SOLVER_EM, SOLVER_EULER_HEUN = 0, 1, 2, 3
 BATCH_PER_TRAJECTORY, BATCH_COUPLED, BATCH_COUPLED_GLOBAL = 0, 1, 2
 SENSE_BACKSOLVE_CHECKPOINTED, SENSE_BACKSOLVE, SENSE_PARALLEL_CHECKPOINTED, SENSE_DISCRETE, SENSE_FORWARD_DUAL = 0, 1, 2, 3, 4
 ACT_RELU, ACT_TANH = 0, 1
@@ -27,7 +27,7 @@ STATUS = {0: "LDE_OK", -1: "LDE_ERR_INVALID_ARG", -2: "LDE_ERR_UNSUPPORTED", -3:
 # every symbol include/lde.h declares
 EXPORTS = ["lde_abi_version", "lde_problem_desc_default", "lde_desc_error", "lde_num_weights", "lde_create", "lde_destroy",
            "lde_build_info", "lde_global_sum_mailbox_bytes", "lde_set_global_sum_peers", "lde_set_weights", "lde_set_weights_device", "lde_reserve", "lde_forward", "lde_adjoint",
-           "lde_get_stats", "lde_last_error", "lde_last_kernel", "lde_set_global_sum_hook", "lde_set_phase_timing", "lde_get_phase_ms",
+           "lde_get_stats", "lde_set_noise", "lde_last_error", "lde_last_kernel", "lde_set_global_sum_hook", "lde_set_phase_timing", "lde_get_phase_ms",
            "lde_step_record_bytes", "lde_set_step_record", "lde_get_step_record", "lde_step_record_capacity", "lde_step_record_status", "lde_set_option", "lde_get_option",
            "lde_chain_num_weights", "lde_chain_create", "lde_chain_destroy", "lde_chain_set_weights",
            "lde_chain_set_weights_device", "lde_chain_reserve", "lde_chain_forward", "lde_chain_backward",
@@ -123,6 +123,7 @@ def load():
     lib.lde_forward.argtypes = [vp, vp, vp, C.POINTER(C.c_double), i32, i32, vp, vp, vp]
     lib.lde_adjoint.argtypes = [vp, vp, vp, C.POINTER(C.c_double), i32, i32, vp, vp, vp, vp, vp]
     lib.lde_get_stats.argtypes = [vp, i32, C.POINTER(Stats), vp]
+    lib.lde_set_noise.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp]
     lib.lde_set_phase_timing.argtypes = [vp, C.c_int]
     lib.lde_get_phase_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.lde_set_global_sum_hook.argtypes = [vp, SUM_HOOK, vp, C.c_int64]

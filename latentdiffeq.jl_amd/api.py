@@ -8,6 +8,7 @@ include/lde.h. PyTorch is used only for device memory, streams and autograd plum
     ---------------------------------------------------------------  -----------------------------------
     Pendulum(; solver, sensalg, kwargs...)    [REF pendulum.jl:4-46]   Pendulum(solver=, sensalg=, **kwargs)
     Pendulum_friction(...)                    [REF pendulum.jl:50-91]  Pendulum_friction(...)
+    SPendulum(; solver, sensalg, kwargs...)   [REF pendulum.jl:93-140] SPendulum(solver=EulerHeun(), sensalg=, dt=, seed=, **kwargs)
     NODE(latent_dim_in; hidden_dim, augment_dim, kwargs...) [REF nODE.jl:3-32]   NODE(latent_dim_in, hidden_dim=, augment_dim=, **kwargs)
     GOKU_basic(), LatentODE()                 [REF GOKU.jl:6-7], [REF LatentODE.jl:6]   same
     Decoder(model_type, (latent_out, diffeq, reconstructor)) [REF LatentDiffEqModel.jl:79-99]   same
@@ -40,6 +41,17 @@ class Tsit5:
 class RK4:
     """RK4() — fixed step only: pass adaptive=False, dt=h through the diffeq kwargs."""
     code = L.SOLVER_RK4
+
+
+class EM:
+    """StochasticDiffEq's EM() (Euler–Maruyama), fixed step: y' = y + h·f(y) + ΔW. SPendulum only."""
+    code = L.SOLVER_EM
+
+
+class EulerHeun:
+    """StochasticDiffEq's EulerHeun(), fixed step: ȳ = y + h·f(y) + ΔW, y' = y + (h/2)·(f(y) + f(ȳ)) + ΔW. SPendulum only (its default:
+    with σ = 0.01 the drift's order limits accuracy, not the noise's — include/lde.h)."""
+    code = L.SOLVER_EULER_HEUN
 
 
 class BacksolveAdjoint:
@@ -221,6 +233,51 @@ class Pendulum_friction(_PhysicsDiffEq):
     _rhs_kind = L.RHS_PENDULUM_FRICTION
 
 
+class _DualTag:
+    code = L.SENSE_FORWARD_DUAL
+
+
+class SPendulum(_PhysicsDiffEq):
+    """Stochastic pendulum, dx = v dt + σ dW₁, dv = −(G/L) sin x dt + σ dW₂, σ = 0.01  [REF pendulum.jl:93-140] — LDE_RHS_SPENDULUM.
+
+    Stated deviation: the reference's default `SOSRI()` (adaptive, rejection sampling with memory) is not reproduced; `EulerHeun()`
+    (default) and `EM()` at the fixed step `dt` are served (include/lde.h: "the stochastic pendulum"). Any `ForwardDiffSensitivity` — the
+    reference's default here too — is LDE_SENSE_FORWARD_DUAL: the exact derivative of the scheme along the drawn path.
+
+    The noise is a pure function of (seed, offset, trajectory, substep). Every forward call advances `offset` by one, so an eager loop
+    draws fresh noise; `reseed(seed)` starts the sequence again. `epoch` (optional): a device int64 tensor the kernel adds to the offset
+    at run time — the optimiser's step count of a captured training step, whose replays then draw fresh noise too. `first_trajectory`:
+    the global index of this call's first trajectory (dist.diffeq_layer_sharded sets it: shards draw the unsharded solve's path)."""
+    _rhs_kind = L.RHS_SPENDULUM
+
+    def __init__(self, solver=None, sensalg=None, sensealg=None, dt: float = 0.05, seed: int = 0, epoch=None, **kwargs):
+        kwargs.setdefault("adaptive", False)
+        kwargs["dt"] = dt
+        super().__init__(solver=solver if solver is not None else EulerHeun(), sensalg=sensalg, sensealg=sensealg, **kwargs)
+        self.seed, self.offset, self.first_trajectory, self.epoch = int(seed), 0, 0, epoch
+
+    def reseed(self, seed: int):
+        self.seed, self.offset = int(seed), 0
+
+    def _native(self) -> _Handle:
+        if self._handle is None:
+            sa = _DualTag if isinstance(self.sensealg, ForwardDiffSensitivity) else self.sensealg
+            d = _make_desc(self._rhs_kind, 2, 1, 0, (), self.solver, sa, L.BATCH_PER_TRAJECTORY, self.kwargs)
+            self._handle = _Handle(d)
+        return self._handle
+
+    def _next_noise(self):
+        """(seed, offset, first_trajectory, epoch tensor) of the forward call being made; the offset then moves on."""
+        nz = (self.seed, self.offset, int(self.first_trajectory), self.epoch)
+        self.offset += 1
+        return nz
+
+
+def _set_noise(handle: _Handle, nz):
+    seed, offset, first, epoch = nz
+    L.check(handle.lib.lde_set_noise(handle.ptr, seed & (2**64 - 1), offset & (2**64 - 1), first, _ptr(epoch)), handle.ptr, "lde_set_noise")
+
+
 class NeuralODE:
     """Tag for NODE.neural_model  [REF nODE.jl:16]."""
 
@@ -386,7 +443,7 @@ class _SolveFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, handle: _Handle, ts: np.ndarray, z0: torch.Tensor, theta: Optional[torch.Tensor],
-                W: Optional[torch.Tensor]):
+                W: Optional[torch.Tensor], noise=None):
         if not z0.is_cuda:
             raise L.LdeError("diffeq_layer needs CUDA/HIP tensors: the solve runs on the GPU only (no CPU fallback)")
         lib = handle.lib
@@ -402,6 +459,9 @@ class _SolveFn(torch.autograd.Function):
         retcode = torch.empty((B,), device=z0.device, dtype=torch.int32)
         tsp = ts.ctypes.data_as(C.POINTER(C.c_double))
         ctx.rec = None
+        ctx.noise = noise                 # SPendulum: the pullback sees the (seed, offset) its forward drew with, whatever ran in between
+        if noise is not None:
+            _set_noise(handle, noise)
         if handle.desc.sensealg in (L.SENSE_DISCRETE, L.SENSE_FORWARD_DUAL):
             # the step record (the dual record: the Jacobians) travels with THIS graph node (several forwards of one diffeq may be in flight
             # before their pullbacks)
@@ -443,6 +503,8 @@ class _SolveFn(torch.autograd.Function):
         if (rec is not None and handle.check_record and handle.desc.sensealg == L.SENSE_DISCRETE
                 and not torch.cuda.is_current_stream_capturing()):
             rec = _SolveFn._record_that_holds(handle, rec, z_out, theta, ts, stream)
+        if ctx.noise is not None:
+            _set_noise(handle, ctx.noise)
         if rec is not None:
             L.check(lib.lde_set_step_record(handle.ptr, _ptr(rec), rec.numel()), handle.ptr, "lde_set_step_record")
         try:
@@ -451,7 +513,7 @@ class _SolveFn(torch.autograd.Function):
         finally:
             if rec is not None:
                 lib.lde_set_step_record(handle.ptr, C.c_void_p(), 0)
-        return None, None, dz0, dth, dW
+        return None, None, dz0, dth, dW, None
 
     @staticmethod
     def _record_that_holds(handle: _Handle, rec: torch.Tensor, z_out: torch.Tensor, theta, ts: np.ndarray, stream) -> torch.Tensor:
@@ -496,8 +558,9 @@ def solve_batch(diffeq, z0_BD: torch.Tensor, theta_BP: Optional[torch.Tensor], t
     handle = diffeq._native()
     handle.check_record = bool(getattr(diffeq, "check_record", True))     # (see _SolveFn._record_that_holds)
     W = diffeq.flat_weights()
+    noise = diffeq._next_noise() if hasattr(diffeq, "_next_noise") else None
     return _SolveFn.apply(handle, _ts_array(t), z0_BD.contiguous().float(),
-                          None if theta_BP is None else theta_BP.contiguous().float(), W)
+                          None if theta_BP is None else theta_BP.contiguous().float(), W, noise)
 
 
 def diffeq_layer(decoder: Decoder, l_hat: Any, t) -> torch.Tensor:

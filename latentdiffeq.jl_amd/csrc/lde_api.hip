@@ -33,6 +33,9 @@ int launch_pend_forward_dual(int kind, int solver, const float* z0, const float*
                              int32_t* ret, hipStream_t stream);
 int launch_pend_adjoint_dual(const DualRec& rec, const float* dz_out, int T, int B, float* dz0, float* dtheta, int32_t* nfe,
                              int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
+int launch_pend_forward_sde(int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o, const DualRec& rec,
+                            const SdeNoise& nz, bool over, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej,
+                            int32_t* ret, hipStream_t stream);
 struct MlpPlan;
 int mlp_plan_create(const lde_problem_desc& d, MlpPlan** out, std::string& err);
 void mlp_plan_destroy(MlpPlan* p);
@@ -87,12 +90,13 @@ struct lde_handle {
   int opt_record_capacity = 0;       // 0: automatic
   int opt_step_trace = 0;
   int opt_adjoint_overwrite = 0;
+  lde::SdeNoise noise;               // LDE_RHS_SPENDULUM: what lde_set_noise left for the next lde_forward calls
   lde::PendTune pend_tune;           // kernel-choice knobs of the analytic right-hand sides (MLP ones live in the plan)
   const char* last_kernel[2] = {"", ""};   // lde_last_kernel: the solve kernel the last lde_forward / lde_adjoint launched
   std::string err = "";
 };
 
-using namespace lde_host;   // validate, has_mlp, has_pend, rec_nseq, rec_capacity, rec_bytes, rec_view, align256, make_opts, num_weights, grid_ok, fixed_step_count
+using namespace lde_host;   // validate, has_mlp, has_pend, is_sde, sde_plan, rec_nseq, rec_capacity, rec_bytes, rec_view, align256, make_opts, num_weights, grid_ok, fixed_step_count
 static int rec_capacity(const lde_handle* h, int T, int which);
 
 #define HIP_TRY(h, expr)                                                                   \
@@ -409,9 +413,15 @@ int lde_forward(lde_handle* h, const float* z0, const float* theta, const double
     if (r.t) h->rec_last[0] = lde::StepRec{r.n, r.t, r.dt, nullptr, r.cap, B};   // (lde_get_step_record's view of the trace)
     h->last_B[0] = B;
     int32_t** st = h->st[0];
-    rc = lde::launch_pend_forward_dual(h->d.rhs_kind, h->d.solver, z0, theta, h->ts_dev, o, r, z_out, retcode, st[0], st[1], st[2], st[3],
-                                       stream);
-    h->last_kernel[0] = "k_pend_forward_dual";
+    if (is_sde(h->d)) {   // the stochastic pendulum: its own stepper writes the same dual record (csrc/lde_pend_sde.hip)
+      rc = lde::launch_pend_forward_sde(h->d.solver, z0, theta, h->ts_dev, o, r, h->noise, sde_plan(h->d, ts, T).over, z_out, retcode, st[0],
+                                        st[1], st[2], st[3], stream);
+      h->last_kernel[0] = "k_pend_forward_sde";
+    } else {
+      rc = lde::launch_pend_forward_dual(h->d.rhs_kind, h->d.solver, z0, theta, h->ts_dev, o, r, z_out, retcode, st[0], st[1], st[2], st[3],
+                                         stream);
+      h->last_kernel[0] = "k_pend_forward_dual";
+    }
     if (rc) h->err = "lde_forward: kernel launch failed";
     return rc;
   }
@@ -506,6 +516,19 @@ int lde_adjoint(lde_handle* h, const float* z_out, const float* theta, const dou
   h->last_kernel[1] = lde::pend_last_kernel(1);
   if (rc) h->err = "lde_adjoint: kernel launch failed";
   return rc;
+}
+
+int lde_set_noise(lde_handle* h, uint64_t seed, uint64_t offset, uint64_t first_trajectory, const int64_t* epoch_dev) {
+  if (!h) return LDE_ERR_INVALID_ARG;
+  if (!is_sde(h->d)) {
+    h->err = "lde_set_noise: the handle's right-hand side is deterministic (LDE_RHS_SPENDULUM only)";
+    return LDE_ERR_UNSUPPORTED;
+  }
+  h->noise.seed = seed;
+  h->noise.offset = offset;
+  h->noise.first_trajectory = first_trajectory;
+  h->noise.epoch_dev = (const long long*)epoch_dev;
+  return LDE_OK;
 }
 
 int lde_get_stats(lde_handle* h, int which, lde_stats* out, void* stream_) {

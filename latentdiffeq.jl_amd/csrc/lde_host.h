@@ -23,6 +23,8 @@ static bool has_mlp(const lde_problem_desc& d) {
   return d.rhs_kind == LDE_RHS_MLP || d.rhs_kind == LDE_RHS_PENDULUM_PLUS_MLP;
 }
 static bool has_pend(const lde_problem_desc& d) { return d.rhs_kind != LDE_RHS_MLP; }
+static bool is_sde(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_SPENDULUM; }
+static bool sde_solver(int solver) { return solver == LDE_SOLVER_EM || solver == LDE_SOLVER_EULER_HEUN; }
 
 static int validate(const lde_problem_desc* d, std::string* why) {
   auto bad = [&](const char* m) {
@@ -31,7 +33,7 @@ static int validate(const lde_problem_desc* d, std::string* why) {
   };
   if (!d) return bad("desc is NULL");
   if (d->abi_version != LDE_ABI_VERSION) return bad("abi_version mismatch");
-  if (d->rhs_kind < 0 || d->rhs_kind > LDE_RHS_PENDULUM_PLUS_MLP) return bad("unknown rhs_kind");
+  if (d->rhs_kind < 0 || d->rhs_kind > LDE_RHS_SPENDULUM) return bad("unknown rhs_kind");
   if (d->state_dim < 1 || d->param_dim < 0 || d->augment_dim < 0) return bad("bad dims");
   if (has_pend(*d) && (d->state_dim != 2 || d->param_dim != 1 || d->augment_dim != 0))
     return bad("pendulum RHS needs state_dim=2, param_dim=1, augment_dim=0");
@@ -44,7 +46,8 @@ static int validate(const lde_problem_desc* d, std::string* why) {
       if (d->layer_sizes[l] < 1) return bad("layer size < 1");
     if (d->activation != LDE_ACT_RELU && d->activation != LDE_ACT_TANH) return bad("unknown activation");
   }
-  if (d->solver != LDE_SOLVER_TSIT5 && d->solver != LDE_SOLVER_RK4) return bad("unknown solver");
+  if (is_sde(*d) && d->n_layers != 0) return bad("LDE_RHS_SPENDULUM is analytic: n_layers must be 0");
+  if (d->solver != LDE_SOLVER_TSIT5 && d->solver != LDE_SOLVER_RK4 && !sde_solver(d->solver)) return bad("unknown solver");
   if (d->batching != LDE_BATCH_PER_TRAJECTORY && d->batching != LDE_BATCH_COUPLED && d->batching != LDE_BATCH_COUPLED_GLOBAL)
     return bad("unknown batching");
   if (d->batching == LDE_BATCH_COUPLED_GLOBAL && !has_mlp(*d)) return bad("LDE_BATCH_COUPLED_GLOBAL needs an MLP right-hand side");
@@ -52,6 +55,21 @@ static int validate(const lde_problem_desc* d, std::string* why) {
   // (LDE_SENSE_DISCRETE with LDE_BATCH_COUPLED_GLOBAL: every rank records the common step sequence and ITS columns' states; the sweep
   //  has no step control, hence no sum to exchange)
 
+  auto unsupported = [&](const char* m) {
+    if (why) *why = m;
+    return (int)LDE_ERR_UNSUPPORTED;
+  };
+  // the stochastic pendulum is served by its own two fixed-step schemes on the dual-number path, and they serve nothing else (include/lde.h)
+  if (sde_solver(d->solver) && !is_sde(*d))
+    return unsupported("LDE_SOLVER_EM / LDE_SOLVER_EULER_HEUN are stochastic steppers: LDE_RHS_SPENDULUM only");
+  if (is_sde(*d)) {
+    if (!sde_solver(d->solver)) return unsupported("LDE_RHS_SPENDULUM: no deterministic solver; use LDE_SOLVER_EM or LDE_SOLVER_EULER_HEUN");
+    if (d->batching != LDE_BATCH_PER_TRAJECTORY) return unsupported("LDE_RHS_SPENDULUM: no coupled solve; LDE_BATCH_PER_TRAJECTORY only");
+    if (d->adaptive) return unsupported("LDE_RHS_SPENDULUM: no adaptive stepping (the reference's SOSRI is not reproduced); pass adaptive=0, dt=h");
+    if (!(d->dt > 0) || !std::isfinite(d->dt)) return unsupported("LDE_RHS_SPENDULUM: fixed step only; pass a finite dt > 0");
+    if (d->sensealg != LDE_SENSE_FORWARD_DUAL)
+      return unsupported("LDE_RHS_SPENDULUM: the gradient is the scheme's exact derivative along the drawn path; use LDE_SENSE_FORWARD_DUAL");
+  }
   if (d->solver == LDE_SOLVER_RK4 && d->adaptive) {
     if (why) *why = "RK4 is fixed-step only here: pass adaptive=0, dt=h";
     return LDE_ERR_UNSUPPORTED;
@@ -142,6 +160,23 @@ static int64_t fixed_step_count(const lde_problem_desc& d, const double* ts, int
     if (steps > d.maxiters) return d.maxiters;
   }
   return steps > d.maxiters ? d.maxiters : steps;
+}
+
+// The substep plan of the stochastic pendulum's solve over a save grid (include/lde.h: "the substep rule"): N = Σ_j n_j with n_j =
+// lde::sde_substeps(ts[j] − ts[j−1], dt) — the function the kernel's loop calls — capped at maxiters. `over`: the plan is longer than
+// maxiters, every trajectory ends with LDE_RET_MAXITERS (the grid is shared). No sum can overflow: n_j ≤ 1e9 and the loop ends at the cap.
+struct SdePlan {
+  int64_t N;
+  bool over;
+};
+static SdePlan sde_plan(const lde_problem_desc& d, const double* ts, int T) {
+  const int64_t cap = std::max<int64_t>(d.maxiters, 0);
+  int64_t N = 0;
+  for (int j = 1; j < T; j++) {
+    N += lde::sde_substeps(ts[j] - ts[j - 1], d.dt);
+    if (N > cap) return {cap, true};
+  }
+  return {N, false};
 }
 
 // Which forward mapping of the analytic right-hand sides serves a solve (csrc/lde_pendulum.hip's launch code switches on this; DESIGN.md §4.1;

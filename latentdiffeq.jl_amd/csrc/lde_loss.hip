@@ -15,6 +15,7 @@
 #include <cstdint>
 
 #include "../../include/lde.h"
+#include "lde_philox.h"
 
 namespace lde {
 
@@ -246,18 +247,8 @@ static int loss_map(const float* a, const float* b, const float* c, const float*
 // 1, 2, 3", SC'11] — the counter-based generator torch and Julia's Random123 use — keyed by the caller's 64-bit seed; block i of four
 // outputs has the counter (i, call, offset + *epoch): `epoch` is a DEVICE counter (the optimiser's step count), so a captured training
 // step draws fresh noise at every replay without the generator bookkeeping a framework puts in front of a replay (three launches and
-// a host-to-device copy per step for two torch.randn calls). The four words of a block make two Box–Muller pairs.
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&o)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
+// a host-to-device copy per step for two torch.randn calls). The four words of a block make two Box–Muller pairs. The generator and the
+// map are csrc/lde_philox.h's (the stochastic pendulum's stepper draws from the same device code).
 __device__ __forceinline__ void randn_block(float* __restrict__ out, long long n, unsigned long long seed, unsigned long long offset,
                                             unsigned call, const long long* __restrict__ epoch, unsigned* __restrict__ raw, const long long blk) {
   if (4 * blk >= n) return;
@@ -266,15 +257,7 @@ __device__ __forceinline__ void randn_block(float* __restrict__ out, long long n
   philox4x32_10((unsigned)blk, call, (unsigned)off, (unsigned)(off >> 32), (unsigned)seed, (unsigned)(seed >> 32), w);
   float z[4];
 #pragma unroll
-  for (int pr = 0; pr < 2; pr++) {
-    const float u1 = ((float)(w[2 * pr] >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0, 1): 24 bits, never 0
-    const float u2 = ((float)(w[2 * pr + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float rad = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincospif(2.0f * u2, &sn, &cs);
-    z[2 * pr] = rad * cs;
-    z[2 * pr + 1] = rad * sn;
-  }
+  for (int pr = 0; pr < 2; pr++) box_muller_pair(w[2 * pr], w[2 * pr + 1], z[2 * pr], z[2 * pr + 1]);
 #pragma unroll
   for (int q = 0; q < 4; q++)
     if (4 * blk + q < n) {

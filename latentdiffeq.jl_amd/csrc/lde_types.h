@@ -31,6 +31,26 @@ struct DualRec {
   int cap;       // 0 without the trace
 };
 
+// The stochastic pendulum's noise (include/lde.h: lde_set_noise), handed to k_pend_forward_sde by value: the Philox key, the two counter
+// words a caller steers and the device word the kernel adds to `offset` at run time.
+struct SdeNoise {
+  unsigned long long seed = 0, offset = 0, first_trajectory = 0;
+  const long long* epoch_dev = nullptr;
+};
+
+// Substeps of one save interval of length D under the nominal step dt (include/lde.h: "the substep rule"): max(1, ceil(D/dt − 1e-9)), at
+// most 1e9. ONE definition for the host's plan (csrc/lde_host.h: sde_plan) and the kernel's loop: f64 division and ceil round the same way
+// on both sides.
+#ifdef __HIPCC__
+#define LDE_HD __host__ __device__
+#else
+#define LDE_HD
+#endif
+LDE_HD inline int sde_substeps(double D, double dt) {
+  const double n = __builtin_ceil(D / dt - 1e-9);
+  return !(n >= 1.0) ? 1 : n > 1e9 ? 1000000000 : (int)n;
+}
+
 // Kernel-choice knobs of a handle (lde_set_option; tests force a family / a threshold through them — formerly LDE_* environment variables,
 // which a library behind a `ccall` host must not read). Defaults = the measured choices.
 struct PendTune {
