@@ -502,20 +502,28 @@ const char* lde_chain_last_error(const lde_chain* c);
  *   RNNCell : h' = act.(Wi*x .+ Wh*h .+ b)
  *   LSTMCell: g = Wi*x .+ Wh*h .+ b;  input, forget, cell, output = σ(g[1:o]), σ(g[o+1:2o]), tanh(g[2o+1:3o]), σ(g[3o+1:4o]);
  *             c' = forget.*c .+ input.*cell;  h' = output.*tanh.(c')
+ *   GRUCell : gx = Wi*x; gh = Wh*h, both [3h], three blocks of h rows in the order (r, z, n);
+ *             r = σ(gx₁ + gh₁ + b₁);  z = σ(gx₂ + gh₂ + b₂);  n = tanh(gx₃ + r.*gh₃ + b₃);  h' = (1 − z).*n .+ z.*h
+ *             ("GRU v1": the reset gate multiplies Wh₃*h only, ONE bias vector. GRUv3Cell is out of scope.)
  * Flat weights = Flux.destructure order per cell: vec(Wi) [G·h × in], vec(Wh) [G·h × h] (column-major), b [G·h],
- * state0 (h0 [h]; LSTM: then c0 [h]) — the initial state is a trainable parameter in this Flux version.
+ * state0 (h0 [h]; LSTM: then c0 [h]) — the initial state is a trainable parameter in this Flux version. G = 1 (RNN), 4 (LSTM),
+ * 3 (GRU): lde_rnn_num_weights = Σ_l (G·h·in + G·h·h + G·h + S·h), S = 2 for the LSTM, else 1.
+ * GRU pullback, per unit from dh': dn = dh'·(1−z)·(1−n²), dz = dh'·(h−n)·z·(1−z), dr = dn·gh₃·r·(1−r); Wi and b see the row deltas
+ * (dr, dz, dn), Wh sees (dr, dz, dn·r); d_in = Wiᵀ(dr, dz, dn), dh_prev = dh'·z + Whᵀ(dr, dz, dn·r); what is left at step 0 is state0's.
  *  - x [in×B×T], y [h_last×B], dy, dx are DEVICE pointers in the reference's column-major layout.
  *  - lde_rnn_backward recomputes the forward sweep (nothing is kept from lde_rnn_forward).
  */
 #define LDE_RNN_MAX_LAYERS 4
 
-enum lde_cell_kind { LDE_CELL_RNN_RELU = 0, LDE_CELL_RNN_TANH = 1, LDE_CELL_LSTM = 2 };
+enum lde_cell_kind { LDE_CELL_RNN_RELU = 0, LDE_CELL_RNN_TANH = 1, LDE_CELL_LSTM = 2, LDE_CELL_GRU = 3 /* Flux GRUCell ("GRU v1"), not GRUv3 */ };
 
 typedef struct lde_rnn_desc {
   int32_t abi_version;                       /* = LDE_ABI_VERSION */
   int32_t cell;                              /* lde_cell_kind */
   int32_t n_layers;                          /* stacked cells, 1..LDE_RNN_MAX_LAYERS */
   int32_t sizes[LDE_RNN_MAX_LAYERS + 1];     /* [in, h1, ..., hL]; gate rows G·h ≤ 64 (LSTM: h ≤ 16, RNN: h ≤ 64), in ≤ 256 */
+                                             /* LDE_CELL_GRU: h ≤ 64, in ≤ 256, and the stack's weights must fit the 160 KiB LDS — */
+                                             /* else LDE_ERR_UNSUPPORTED ("weights do not fit the 160 KiB LDS"), like every kind.   */
   int32_t reverse;                           /* 1: feed the frames T, T-1, ..., 1 (reverse(fe_out)) */
 } lde_rnn_desc;
 
@@ -544,7 +552,8 @@ int  lde_rnn_forward_train(lde_rnn* r, const float* x, int T, int B, float* y, v
 /* Several stacks on the same frames in one call (the GOKU encoder's three pattern extractors [REF src/models/GOKU.jl:32-51]): with
  * n ≤ 3 stacks of the default shape every stage — the sweep, the weight-gradient products of all (stack, cell) pairs, their fixed-order
  * sums, the initial-state sums — is ONE launch; anything else runs the stacks one after the other. Per stack the same kernels on the
- * same arguments as lde_rnn_forward / lde_rnn_backward: results equal bit for bit. dxs may be NULL or hold NULL entries. */
+ * same arguments as lde_rnn_forward / lde_rnn_backward: results equal bit for bit. dxs may be NULL or hold NULL entries. A group that
+ * contains an LDE_CELL_GRU stack runs its stacks one after the other. */
 int  lde_rnn_group_forward(int n, lde_rnn* const* stacks, const float* const* xs, int T, int B, float* const* ys, void* stream);
 int  lde_rnn_group_forward_train(int n, lde_rnn* const* stacks, const float* const* xs, int T, int B, float* const* ys, void* stream);
 int  lde_rnn_group_backward(int n, lde_rnn* const* stacks, const float* const* xs, const float* const* dys, int T, int B,

@@ -216,7 +216,7 @@ Base.@kwdef mutable struct LdeChainDesc       # mirror of lde_chain_desc (includ
 end
 
 Base.@kwdef mutable struct LdeRnnDesc          # mirror of lde_rnn_desc (include/lde.h)
-    abi_version::Int32 = 1;  cell::Int32 = 0   # 0 RNN relu, 1 RNN tanh, 2 LSTM
+    abi_version::Int32 = 1;  cell::Int32 = 0   # 0 RNN relu, 1 RNN tanh, 2 LSTM, 3 GRU (Flux GRUCell, "v1")
     n_layers::Int32 = 0;     sizes::NTuple{5,Int32} = ntuple(_ -> Int32(0), 5);  reverse::Int32 = 0
 end
 

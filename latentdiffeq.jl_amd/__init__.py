@@ -7,7 +7,7 @@ Layout:
   api.py     host-side mirror of the reference interface: Pendulum / Pendulum_friction / SPendulum / NODE,
              GOKU_basic / LatentODE, Decoder, diffeq_layer, transform_after_diffeq
   chain.py   Dense / SkipConnection / Chain, apply_latent_out, apply_reconstructor (the dense chains either side of the solve)
-  recurrent.py  RNN / LSTM / Recurrent, Encoder, apply_feature_extractor / _pattern_extractor / _latent_in, sample
+  recurrent.py  RNN / LSTM / GRU / Recurrent, Encoder, apply_feature_extractor / _pattern_extractor / _latent_in, sample
   loss.py    sample, vector_kl, reconstruction_loss (lde_sample_* / lde_kl_* / lde_mse_*)
   train.py   LatentDiffEqModel, default_layers, loss_batch, frange_cycle_linear, time_loader, train (host only)
   data.py    generate_dataset, create_frames: synthetic pendulum videos (approximation of the Luxor drawing)

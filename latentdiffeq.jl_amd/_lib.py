@@ -44,7 +44,7 @@ COMM_ID_BYTES = 128
 LOSS_SCRATCH_FLOATS = 1024
 
 LDE_RNN_MAX_LAYERS = 4
-CELL_RNN_RELU, CELL_RNN_TANH, CELL_LSTM = 0, 1, 2
+CELL_RNN_RELU, CELL_RNN_TANH, CELL_LSTM, CELL_GRU = 0, 1, 2, 3
 
 
 class RnnDesc(C.Structure):

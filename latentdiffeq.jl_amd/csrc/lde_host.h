@@ -509,6 +509,57 @@ static int chain_dw_parts_bf16(int jobs, int64_t N, int chunk) {
   return (int)std::min<int64_t>(std::max(256 / std::max(jobs, 1), 1), nchunks);
 }
 
+// ---- the GRU cell of the recurrent pattern extractor (LDE_CELL_GRU; csrc/lde_rnn_gru.h): the pure part of its plan.
+// The kernels run a cell of h units as P = 4h PSEUDO-ROWS of [Wi | Wh] over K = in + h columns — (r, z, n_x, n_h), h rows each: n_x is
+// [Wi₃ | 0] with the bias, n_h is [0 | Wh₃] without one — and the weight-gradient product leaves vec of that [P × K] matrix, column-major,
+// then its P bias sums. The flat (Flux.destructure) order of the cell is vec(Wi) [3h × in], vec(Wh) [3h × h], b [3h], state0 [h].
+constexpr int GRU_MAX_H = 64, GRU_MAX_IN = 256;   // the limits lde_rnn_create states for every cell kind
+static bool gru_dims_ok(int64_t in, int64_t h) { return in >= 1 && h >= 1 && in <= GRU_MAX_IN && h <= GRU_MAX_H; }
+static int gru_rows(int h) { return h >= 1 && h <= GRU_MAX_H ? 4 * h : 0; }
+// lanes per trajectory: one per pseudo-row of the widest cell, a power of two, at most a wave (a trajectory never leaves its wave) …
+static int gru_lanes(int hmax) {
+  int Hp = 1;
+  while (Hp < gru_rows(hmax) && Hp < 64) Hp <<= 1;
+  return Hp;
+}
+// … and the pseudo-rows a lane owns then: rows u, u + lanes, … (1 up to h = 16; 4 at h = 64)
+static int gru_rows_per_lane(int h, int lanes) { return lanes >= 1 ? (gru_rows(h) + lanes - 1) / lanes : 0; }
+// floats of one cell in the flat weight vector (−1: sizes outside the limits), and of one (step, trajectory) training record per unit
+// row: r, z, n, Wh₃·h, h′
+static int64_t gru_cell_weights(int64_t in, int64_t h) { return gru_dims_ok(in, h) ? 3 * h * in + 3 * h * h + 3 * h + h : -1; }
+constexpr int GRU_REC_ROWS = 5;
+// offsets of vec(Wh), b and state0 from the cell's start in the flat order
+struct GruFlat {
+  int64_t wh, b, s0, end;
+};
+static GruFlat gru_flat_offsets(int64_t in, int64_t h) {
+  if (!gru_dims_ok(in, h)) return {-1, -1, -1, -1};
+  return {3 * h * in, 3 * h * in + 3 * h * h, 3 * h * in + 3 * h * h + 3 * h, 3 * h * in + 3 * h * h + 3 * h + h};
+}
+// floats the staged product leaves for one cell: [4h × K] + [4h]
+// (0 for sizes outside the limits, here and below: no arithmetic is done on them)
+LDE_HD inline bool gru_sizes_ok(int in, int h) { return in >= 1 && h >= 1 && in <= 256 && h <= 64; }
+LDE_HD inline long long gru_staged_floats(int in, int h) { return gru_sizes_ok(in, h) ? 4LL * h * (in + h) + 4LL * h : 0; }
+// flat entries that come out of the staged product (everything but state0)
+LDE_HD inline long long gru_staged_count(int in, int h) { return gru_sizes_ok(in, h) ? 3LL * h * (in + h) + 3LL * h : 0; }
+// where flat entry e ∈ [0, gru_staged_count) of the cell sits in the staged result (−1: e or the sizes out of range). One-to-one, and
+// never a structural zero of the pseudo-rows (n_x × h columns, n_h × x columns, the bias of n_h).
+LDE_HD inline long long gru_staged_index(int in, int h, long long e) {
+  if (!gru_sizes_ok(in, h) || e < 0) return -1;
+  const long long R = 3LL * h, P = 4LL * h;
+  if (e < R * in) {
+    const long long k = e / R, r = e - k * R;   // Wi: rows r, z, n → pseudo-rows r, z, n_x
+    return k * P + r;
+  }
+  e -= R * in;
+  if (e < R * h) {
+    const long long k = e / R, r = e - k * R;   // Wh: rows r, z, n → pseudo-rows r, z, n_h
+    return (in + k) * P + (r < 2LL * h ? r : r + h);
+  }
+  e -= R * h;
+  return e < R ? P * (in + h) + e : -1;         // b: pseudo-rows r, z, n_x
+}
+
 static KOpts make_opts(const lde_problem_desc& d, const double* ts, int T, int B) {
   KOpts o;
   o.abstol = (float)d.abstol;

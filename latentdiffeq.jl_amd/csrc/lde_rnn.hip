@@ -5,6 +5,7 @@
 // i.e. stacks Chain(RNN(32,16,relu), RNN(16,16,relu)) / Chain(LSTM(32,16), LSTM(16,16)) [REF src/models/GOKU.jl:229-238]
 // run over the T frames of fe_out [in×B×T] (forward or reversed), keeping the last output, and their pullback.
 // Cells: Flux 0.13.6 RNNCell / LSTMCell (un-vendored [REF Manifest.toml:452]); equations and weight order in include/lde.h.
+// GRUCell (LDE_CELL_GRU): lde_rnn_gru.h — a single-wave body of its own; the two-wave pipeline below knows the cell.
 //
 // Design (gfx950). The cells are tiny (16 hidden units, K = in + h = 48) and strictly sequential in time: this is
 // latency-bound scalar work, not matrix-core work (north star: "MFMA only if latent_dim×hidden is large enough to fill
@@ -29,6 +30,7 @@
 #include <cstring>
 #include <string>
 
+#include "lde_host.h"
 #include "lde_mfma.h"
 
 namespace lde {
@@ -111,6 +113,10 @@ __device__ __forceinline__ void rnn_load_weights(const RnnDims& rd, const float*
 
 constexpr int rnn_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 __host__ __device__ constexpr int rnn_ldk(int K) { int v = (K + 3) & ~3; return ((v >> 2) & 1) ? v : v + 4; }
+
+}  // namespace lde
+#include "lde_rnn_gru.h"   // LDE_CELL_GRU: gru_load_weights, gru_body, k_gru, k_gru_gather
+namespace lde {
 
 // One workgroup = tpw trajectories × Hp lanes. mode 0: forward sweep → y. mode 1: sweep with records, then BPTT.
 // CELL_ ≥ 0 instantiates the kernel for one stack shape (cell kind, IN0_ → H_ → … → H_, L_ cells) — the reference's default
@@ -467,7 +473,8 @@ __device__ __forceinline__ void rnn_pipe_wave(const RnnDims& rd, const RnnArgs& 
                                               int* cnt) {
   constexpr int IN0 = 32, H = 16, L = 2;
   constexpr bool lstm = CELL_ == LDE_CELL_LSTM;
-  constexpr int G = lstm ? 4 : 1, Hp = rnn_pow2(G * H), TPW = 64 / Hp;
+  constexpr bool gru = CELL_ == LDE_CELL_GRU;   // its four pseudo-rows (r, z, n_x, n_h: lde_rnn_gru.h) sit where the LSTM's four gates do
+  constexpr int G = (lstm || gru) ? 4 : 1, Hp = rnn_pow2(G * H), TPW = 64 / Hp;
   constexpr int in = LY == 0 ? IN0 : H, h = H, K = in + h, ldk = rnn_ldk(K), Rl = G * h, ldr = rnn_ldk(Rl);
   constexpr int KF4 = (K + 3) / 4, RB4 = (Rl + 3) / 4, NKI = (K + Hp - 1) / Hp;
   constexpr bool keep = MODE_ == 1 || MODE_ == 2, bptt = MODE_ == 1 || MODE_ == 3;
@@ -576,7 +583,7 @@ __device__ __forceinline__ void rnn_pipe_wave(const RnnDims& rd, const RnnArgs& 
         fetch_x();
       }
       float zz[4] = {z, 0.f, 0.f, 0.f};
-      if (lstm) {   // unit lane u < 16 needs rows u, 16+u, 32+u, 48+u
+      if (lstm || gru) {   // unit lane u < 16 needs rows u, 16+u, 32+u, 48+u
         float lo, hi;
         rows32(z, lo, hi);
         rows16(lo, zz[0], zz[1]);
@@ -589,6 +596,12 @@ __device__ __forceinline__ void rnn_pipe_wave(const RnnDims& rd, const RnnArgs& 
           zz[0] = ig; zz[1] = fg; zz[2] = gg; zz[3] = og;
           cn = __builtin_fmaf(fg, creg, ig * gg);
           hn = og * fast_tanh(cn);
+        } else if (gru) {   // (gru_body's formulas, in its order: the same bits)
+          const float rg = sigm(zz[0]), zg = sigm(zz[1]), gh = zz[3];
+          const float ng = fast_tanh(__builtin_fmaf(rg, gh, zz[2]));
+          hn = __builtin_fmaf(zg, hn - ng, ng);
+          zz[0] = rg; zz[1] = zg; zz[2] = ng; zz[3] = gh;
+          cn = hn;          // the record's fifth row is h′
         } else {
           hn = CELL_ == LDE_CELL_RNN_TANH ? fast_tanh(zz[0]) : fmaxf(zz[0], 0.f);
           zz[0] = hn;
@@ -601,7 +614,7 @@ __device__ __forceinline__ void rnn_pipe_wave(const RnnDims& rd, const RnnArgs& 
           for (int g = 0; g < 4; g++)
             if (g < G) r[g * h + u] = zz[g];
           r[G * h + u] = cn;
-          r[G * h + h + u] = hn;
+          if (!gru) r[G * h + h + u] = hn;   // (a GRU record has five rows)
         }
         if (keep) rp += rstep;
       }
@@ -634,6 +647,7 @@ __device__ __forceinline__ void rnn_pipe_wave(const RnnDims& rd, const RnnArgs& 
       rq[4] = rpb[Rl];
       rq[5] = (first ? rpb : rpb - rstepb)[Rl];
     }
+    if (gru) rq[5] = (first ? rpb : rpb - rstepb)[Rl];   // h_prev: the previous record's h′ (step 0: the trainable state0, patched in at the use)
   };
   fetch_rec(T == 1);
   float* gd = a.stage[LY] + (tile * T + (T - 1)) * a.blk[LY] + NB * pad32(K) + row * pad32(Rl);
@@ -674,6 +688,15 @@ __device__ __forceinline__ void rnn_pipe_wave(const RnnDims& rd, const RnnArgs& 
         dbuf[2 * h + u] = dct * ig * __builtin_fmaf(-gg, gg, 1.f);
         dbuf[3 * h + u] = dhv * tc * og * (1.f - og);
         dcr = dct * fg;
+      } else if (gru) {
+        const float rg = cur[0], zg = cur[1], ng = cur[2], gh = cur[3];
+        const float hp = s > 0 ? cur[5] : h0;
+        const float dn = dhv * (1.f - zg) * __builtin_fmaf(-ng, ng, 1.f);
+        dbuf[u] = dn * gh * rg * (1.f - rg);
+        dbuf[h + u] = dhv * (hp - ng) * zg * (1.f - zg);
+        dbuf[2 * h + u] = dn;
+        dbuf[3 * h + u] = dn * rg;
+        dcr = dhv * zg;   // the direct path h → h′
       } else {
         const float av = cur[0];
         dbuf[u] = dhv * (CELL_ == LDE_CELL_RNN_TANH ? __builtin_fmaf(-av, av, 1.f) : (av > 0.f ? 1.f : 0.f));
@@ -718,11 +741,11 @@ __device__ __forceinline__ void rnn_pipe_wave(const RnnDims& rd, const RnnArgs& 
     }
     // ∂L/∂h_prev (outputs in … K−1) to the unit lanes: the LSTM's sit one lane row (cell 2) or two (cell 1) up; the plain cells' are the
     // lane's own last output
-    if (lstm) {
+    if (lstm || gru) {
       float ev, od;
       if (LY == 0) rows32(accl, ev, od);
       else rows16(accl, ev, od);
-      dhr = od;
+      dhr = gru ? od + dcr : od;
     } else
       dhr = accl;
     if (LY == 1) st_cnt(2, idx + 1);
@@ -743,13 +766,14 @@ __host__ __device__ inline int rnn_pipe_extra_floats(const RnnDims& rd, int tpw)
 template <int CELL_, int MODE_>
 __device__ __forceinline__ void rnn_body2(const RnnDims& rd, const RnnArgs& a, const unsigned bx) {
   extern __shared__ __attribute__((aligned(16))) float rsm[];
-  constexpr int Hp = rnn_pow2((CELL_ == LDE_CELL_LSTM ? 4 : 1) * 16), TPW = 64 / Hp;
+  constexpr int Hp = rnn_pow2(((CELL_ == LDE_CELL_LSTM || CELL_ == LDE_CELL_GRU) ? 4 : 1) * 16), TPW = 64 / Hp;
   float* lw = rsm;
   float* xring = lw + rd.lds_w + 2 * TPW * (rd.vmax + rd.rmax + 4 * 16);
   float* gring = xring + PIPE_R * TPW * 16;
   int* cnt = reinterpret_cast<int*>(gring + PIPE_R * TPW * 16);
   if (threadIdx.x < 4) cnt[threadIdx.x] = 0;
-  rnn_load_weights(rd, a.Wflat, lw, 128, MODE_ == 1 || MODE_ == 3);   // (ends with a barrier: the counters are zero for both waves)
+  if (CELL_ == LDE_CELL_GRU) gru_load_weights(rd, a.Wflat, lw, 128, MODE_ == 1 || MODE_ == 3);
+  else rnn_load_weights(rd, a.Wflat, lw, 128, MODE_ == 1 || MODE_ == 3);   // (ends with a barrier: the counters are zero for both waves)
   for (int i = threadIdx.x; i < 2 * TPW * (rd.vmax + rd.rmax + 4 * 16); i += 128) lw[rd.lds_w + i] = 0.f;
   __syncthreads();
   if (threadIdx.x < 64) rnn_pipe_wave<CELL_, MODE_, 0>(rd, a, bx, lw, xring, gring, cnt);
@@ -795,7 +819,7 @@ __device__ __forceinline__ void rnn_state0_body(const float* __restrict__ g0, in
     if (i < off + ns) break;
     off += ns;
   }
-  const int in = rd.sizes[l], h = rd.sizes[l + 1], R = rd.G * h;
+  const int in = rd.sizes[l], h = rd.sizes[l + 1], R = (rd.cell == LDE_CELL_GRU ? 3 : rd.G) * h;   // (GRU: rd.G counts its four pseudo-rows)
   float s = 0.f;
   for (int b = threadIdx.x; b < B; b += 64) s += g0[(size_t)b * g0w + i];
 #pragma unroll
@@ -860,6 +884,7 @@ struct lde_rnn {
   float* g0 = nullptr; size_t g0_cap = 0;
   float* slab = nullptr; size_t slab_cap = 0; size_t slab_layer = 0;
   int32_t* ints = nullptr; size_t ints_cap = 0;
+  float* gtmp = nullptr; size_t gtmp_off[RNN_ML] = {0, 0, 0, 0};   // GRU: the staged weight-gradient products [4h × K] + [4h] per cell, before k_gru_gather
   bool accumulate = true;   // pullback: dW += gradient (default) or dW = gradient
   int opt_generic = 0, opt_regw = 1, opt_pipe = 1;   // lde_rnn_set_option: "generic", "regw", "pipe" (kernel-choice knobs of the parity tests)
   int opt_async_dw = 1;                              // "async_dw": with a dw stream set, a grouped pullback's weight-gradient products go there (0: stay on the caller's stream)
@@ -871,7 +896,7 @@ struct lde_rnn {
 
 static int rnn_desc_ok(const lde_rnn_desc* d) {
   if (!d || d->abi_version != LDE_ABI_VERSION || d->n_layers < 1 || d->n_layers > LDE_RNN_MAX_LAYERS) return 0;
-  if (d->cell < 0 || d->cell > LDE_CELL_LSTM) return 0;
+  if (d->cell < 0 || d->cell > LDE_CELL_GRU) return 0;
   for (int l = 0; l <= d->n_layers; l++)
     if (d->sizes[l] < 1) return 0;
   return 1;
@@ -898,6 +923,16 @@ static rnn_kernel_t rnn_pick_mode(int mode) {
   }
 }
 
+template <bool ONE>
+static rnn_kernel_t gru_pick_mode(int mode) {
+  switch (mode) {
+    case 0: return k_gru<true, 0, ONE>;
+    case 1: return k_gru<true, 1, ONE>;
+    case 2: return k_gru<true, 2, ONE>;
+    default: return k_gru<true, 3, ONE>;
+  }
+}
+
 template <int CELL_>
 static rnn_kernel_t rnn_pick_pipe(int mode) {
   switch (mode) {
@@ -912,7 +947,7 @@ extern "C" {
 
 int64_t lde_rnn_num_weights(const lde_rnn_desc* d) {
   if (!rnn_desc_ok(d)) return -1;
-  const int64_t G = d->cell == LDE_CELL_LSTM ? 4 : 1, S = d->cell == LDE_CELL_LSTM ? 2 : 1;
+  const int64_t G = d->cell == LDE_CELL_LSTM ? 4 : d->cell == LDE_CELL_GRU ? 3 : 1, S = d->cell == LDE_CELL_LSTM ? 2 : 1;
   int64_t n = 0;
   for (int l = 0; l < d->n_layers; l++) {
     const int64_t in = d->sizes[l], h = d->sizes[l + 1];
@@ -931,6 +966,7 @@ void lde_rnn_destroy(lde_rnn* r) {
   if (r->g0) (void)hipFree(r->g0);
   if (r->slab) (void)hipFree(r->slab);
   if (r->ints) (void)hipFree(r->ints);
+  if (r->gtmp) (void)hipFree(r->gtmp);
   dw_sync_destroy(r->dws);
   delete r;
 }
@@ -946,17 +982,19 @@ int lde_rnn_create(const lde_rnn_desc* d, lde_rnn** out) {
   r->d = *d;
   RnnDims& rd = r->rd;
   std::memset(&rd, 0, sizeof(rd));
-  rd.cell = d->cell; rd.nL = d->n_layers; rd.reverse = d->reverse ? 1 : 0; rd.G = d->cell == LDE_CELL_LSTM ? 4 : 1;
+  rd.cell = d->cell; rd.nL = d->n_layers; rd.reverse = d->reverse ? 1 : 0; rd.G = (d->cell == LDE_CELL_LSTM || d->cell == LDE_CELL_GRU) ? 4 : 1;   // gate rows per unit (GRU: its four pseudo-rows r, z, n_x, n_h)
+  const bool gru = d->cell == LDE_CELL_GRU;
   int hmax = 0, kmax = 0, rmax = 0;
   for (int l = 0; l <= d->n_layers; l++) rd.sizes[l] = d->sizes[l];
   for (int l = 1; l <= d->n_layers; l++) hmax = std::max(hmax, d->sizes[l]);
   if (hmax > 64 || d->sizes[0] > 256) {
-    r->err = "recurrent stack: hidden width ≤ 64 and input width ≤ 256 supported";
+    r->err = "recurrent stack: hidden width ≤ 64 and input width ≤ 256 supported (every cell kind, LDE_CELL_GRU included)";
     return LDE_ERR_UNSUPPORTED;
   }
   int Hp = 1;   // lanes per trajectory: one per gate row of the widest cell (≤ 64 ⇒ a trajectory never leaves its wave)
   while (Hp < rd.G * hmax && Hp < 64) Hp <<= 1;
-  if (Hp < rd.G * hmax) {
+  if (gru) Hp = lde_host::gru_lanes(hmax);   // (the same rule; above 64 pseudo-rows a lane owns several: lde_host::gru_rows_per_lane)
+  if (!gru && Hp < rd.G * hmax) {
     r->err = "recurrent stack: G·h ≤ 64 gate rows per cell supported (LSTM: h ≤ 16, RNN: h ≤ 64)";
     return LDE_ERR_UNSUPPORTED;
   }
@@ -974,7 +1012,7 @@ int lde_rnn_create(const lde_rnn_desc* d, lde_rnn** out) {
     rd.b_off[l] = off; off += (R + 3) & ~3;
     rd.s_off[l] = off; off += (2 * h + 3) & ~3;
     rd.f_off[l] = foff;
-    foff += R * in + R * h + R + (d->cell == LDE_CELL_LSTM ? 2 : 1) * h;
+    foff += gru ? (int)lde_host::gru_cell_weights(in, h) : R * in + R * h + R + (d->cell == LDE_CELL_LSTM ? 2 : 1) * h;
     kmax = std::max(kmax, K);
     rmax = std::max(rmax, R);
     r->g0w += (d->cell == LDE_CELL_LSTM ? 2 : 1) * h;
@@ -999,7 +1037,7 @@ int lde_rnn_create(const lde_rnn_desc* d, lde_rnn** out) {
   rd.lds_w = off;
   rd.vmax = ((kmax + 3) & ~3) + 4;
   rd.rmax = (rmax + 3) & ~3;
-  rd.recw = (rd.G + 2) * hmax;
+  rd.recw = (gru ? lde_host::GRU_REC_ROWS : rd.G + 2) * hmax;
   r->nW = foff;
   r->lds = ((size_t)rd.lds_w + 16 * ((size_t)rd.vmax + rd.rmax + 4 * rd.nL * hmax)) * sizeof(float);
   if (r->lds > LDS_MAX) {
@@ -1009,6 +1047,14 @@ int lde_rnn_create(const lde_rnn_desc* d, lde_rnn** out) {
   if (hipMalloc(&r->W_dev, (size_t)r->nW * sizeof(float)) != hipSuccess) {
     r->err = "recurrent stack: hipMalloc failed";
     return LDE_ERR_ALLOC;
+  }
+  if (gru) {
+    size_t n = 0;
+    for (int l = 0; l < rd.nL; l++) { r->gtmp_off[l] = n; n += (size_t)lde_host::gru_staged_floats(rd.sizes[l], rd.sizes[l + 1]); }
+    if (hipMalloc(&r->gtmp, n * sizeof(float)) != hipSuccess) {
+      r->err = "recurrent stack: hipMalloc failed";
+      return LDE_ERR_ALLOC;
+    }
   }
   return LDE_OK;
 }
@@ -1071,6 +1117,11 @@ int lde_rnn_reserve(lde_rnn* r, int B, int T) {
 // the instantiation for this stack: the reference's default pattern extractors (32 → 16 → 16) have their own, any other shape
 // runs the run-time-shaped kernel
 static rnn_kernel_t rnn_pick(const RnnDims& rd, int mode, bool one_wave = false, bool generic_only = false) {
+  if (rd.cell == LDE_CELL_GRU) {   // a body of its own (csrc/lde_rnn_gru.h)
+    if (!generic_only && rd.wt && rd.nL == 2 && rd.sizes[0] == 32 && rd.sizes[1] == 16 && rd.sizes[2] == 16)
+      return one_wave ? gru_pick_mode<true>(mode) : gru_pick_mode<false>(mode);
+    return k_gru<false, 0, false>;
+  }
   if (!generic_only && rd.wt && rd.nL == 2 && rd.sizes[0] == 32 && rd.sizes[1] == 16 && rd.sizes[2] == 16) {
     if (one_wave) {
       if (rd.cell == LDE_CELL_LSTM) return rnn_pick_mode<LDE_CELL_LSTM, true>(mode);
@@ -1121,7 +1172,7 @@ static int rnn_launch(lde_rnn* r, const RnnArgs& a, int B, hipStream_t stream) {
   const int one = pipe ? 2 : (one_wave ? 1 : 0);
   if (!r->kernel[m][one]) {
     if (pipe)
-      r->kernel[m][one] = rd0.cell == LDE_CELL_LSTM ? rnn_pick_pipe<LDE_CELL_LSTM>(m)
+      r->kernel[m][one] = rd0.cell == LDE_CELL_LSTM ? rnn_pick_pipe<LDE_CELL_LSTM>(m) : rd0.cell == LDE_CELL_GRU ? rnn_pick_pipe<LDE_CELL_GRU>(m)
                           : rd0.cell == LDE_CELL_RNN_RELU ? rnn_pick_pipe<LDE_CELL_RNN_RELU>(m) : rnn_pick_pipe<LDE_CELL_RNN_TANH>(m);
     else
       r->kernel[m][one] = rnn_pick(r->rd, m, one != 0, generic_only);
@@ -1145,7 +1196,7 @@ static int rnn_launch(lde_rnn* r, const RnnArgs& a, int B, hipStream_t stream) {
     q.fn = r->kernel[m][one];
     const RnnDims& rd = r->rd;
     q.groupable = one && rd.wt && rd.nL == 2 && rd.sizes[0] == 32 && rd.sizes[1] == 16 && rd.sizes[2] == 16 &&
-                  q.fn != (rnn_kernel_t)k_rnn<-1, 0, 0, 0, 0>;
+                  q.fn != (rnn_kernel_t)k_rnn<-1, 0, 0, 0, 0> && rd.cell != LDE_CELL_GRU;   // (k_rnn_group switches between the RNN / LSTM bodies only)
     q.pipe = pipe;
     q.mode = m; q.rd = rd; q.a = aa; q.grid = (unsigned)(cdiv(B, 16) * (16 / tpw)); q.block = block; q.lds = lds;
     t_rrec->main_set[t_rrec->n] = true;
@@ -1286,6 +1337,7 @@ int lde_rnn_backward_dw(lde_rnn* r, float* dW, void* stream_) {
     r->err = "lde_rnn_backward: switching to the weight-gradient stream failed";
     return LDE_ERR_HIP;
   }
+  const bool gru = rd.cell == LDE_CELL_GRU;   // (never inside a grouped call's recorder: rnn_group_ok)
   for (int l = 0; l < rd.nL; l++) {
     DwArgs da;
     da.stage = r->stage[l]; da.wts = r->wts; da.nslots = nullptr; da.slab = r->slab + (size_t)l * r->slab_layer; da.cap = T; da.total = (long long)ntile * T;   // every tile staged exactly T slots
@@ -1298,6 +1350,14 @@ int lde_rnn_backward_dw(lde_rnn* r, float* dW, void* stream_) {
       q.rdm = r->dmw[l];
       q.ra = ReduceArgs{nullptr, r->ints, 0, da.slab, ntile * ks, dW + rd.f_off[l], r->ints + 2, r->accumulate ? 0 : 1};
       q.rgrid = (unsigned)cdiv(r->dmw[l].slab_n, 1024);
+      continue;
+    }
+    if (gru) {   // the product of the pseudo-rows, written; then its entries into the cell's flat order, added or written
+      int rc = launch_weight_gradient(r->dmw[l], da, ntile, ks, nullptr, r->ints, 0, r->gtmp + r->gtmp_off[l], r->ints + 2, wst, r->err, true);
+      if (rc) return rc;
+      const int in = rd.sizes[l], h = rd.sizes[l + 1];
+      hipLaunchKernelGGL(k_gru_gather, dim3(cdiv((int)lde_host::gru_staged_count(in, h), 256)), dim3(256), 0, wst, r->gtmp + r->gtmp_off[l],
+                         dW + rd.f_off[l], in, h, r->accumulate ? 0 : 1);
       continue;
     }
     int rc = launch_weight_gradient(r->dmw[l], da, ntile, ks, nullptr, r->ints, 0, dW + rd.f_off[l], r->ints + 2, wst, r->err, !r->accumulate);
@@ -1438,6 +1498,8 @@ static bool rnn_group_ok(int n) {
 }
 static bool rnn_group_fits(int n, lde_rnn* const* rs) {   // every (stack, cell) weight-gradient job must fit one table; a handle's workspace serves one call at a time
   int jobs = 0;
+  for (int i = 0; i < n; i++)
+    if (rs[i]->rd.cell == LDE_CELL_GRU) return false;   // a GRU stack's weight gradient has a gather behind its product: such a group runs its stacks one after the other
   for (int i = 0; i < n; i++) {
     jobs += rs[i]->rd.nL;
     for (int j = i + 1; j < n; j++)

@@ -4,6 +4,7 @@ around it.
     reference                                                                    here
     ---------------------------------------------------------------------------  ------------------------------------
     RNN(in, out, relu; init), LSTM(in, out; init)      [Flux; REF GOKU.jl:229-238]  RNN(in, out, act), LSTM(in, out)
+    GRU(in, out) (Flux 0.13.6, for custom encoder_layers [REF LatentDiffEqModel.jl:30-61])  GRU(in, out)
     Chain(RNN(..), RNN(..)) applied frame by frame     [REF GOKU.jl:229-238]        Recurrent(RNN(..), RNN(..), reverse=)
     apply_feature_extractor(encoder, x)                [REF GOKU.jl:19]             same  (a Chain: chain.py)
     apply_pattern_extractor(encoder, fe_out)           [REF GOKU.jl:32-51], [REF LatentODE.jl:24-33]   same
@@ -83,6 +84,12 @@ class LSTM(_Cell):
     def __init__(self, n_in: int, n_out: int):
         super().__init__(n_in, n_out)
         self._init[2][n_out:2 * n_out] = 1.0
+
+
+class GRU(_Cell):
+    """GRU(in, out)  [Flux 0.13.6 GRUCell, "GRU v1": gates reset, update, candidate; r multiplies Wh₃·h only; one bias vector] —
+    r = σ(gx₁ + gh₁ + b₁), z = σ(gx₂ + gh₂ + b₂), n = tanh(gx₃ + r ⊙ gh₃ + b₃), h′ = (1 − z) ⊙ n + z ⊙ h (include/lde.h)."""
+    G, S, code = 3, 1, L.CELL_GRU
 
 
 class _RecurrentFn(torch.autograd.Function):
@@ -419,7 +426,7 @@ class Recurrent(torch.nn.Module):
     def __init__(self, *cells, reverse: bool = False):
         super().__init__()
         if not cells or len({type(c) for c in cells}) != 1 or len({c.code for c in cells}) != 1:
-            raise TypeError("Recurrent takes cells of one kind (all RNN with one activation, or all LSTM)")
+            raise TypeError("Recurrent takes cells of one kind (all RNN with one activation, all LSTM, or all GRU)")
         for a, b in zip(cells[:-1], cells[1:]):
             if a.n_out != b.n_in:
                 raise ValueError("cell sizes do not chain")
