@@ -1038,16 +1038,6 @@ struct ChainCall {
   GroupRec* rec = nullptr;      // a grouped call: the launch sites record into slot rec->n instead of launching
 };
 
-// every kernel here may ask for the whole LDS: once per kernel
-static bool set_max_lds_(const void* fn) {
-  static std::mutex mu;
-  static std::vector<const void*> done;
-  std::lock_guard<std::mutex> lk(mu);
-  if (std::find(done.begin(), done.end(), fn) != done.end()) return true;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) return false;
-  done.push_back(fn);
-  return true;
-}
 static const char* const MAIN_NAME[4] = {"k_chain_forward", "k_chain_forward_b", "k_chain_backward", "k_chain_backward_b"};
 // (like the two below: false when the LDS attribute could not be set; a failed launch stays in hipGetLastError for the caller)
 static bool launch_main_single(const RecMain& r, hipStream_t stream) {

@@ -560,6 +560,172 @@ LDE_HD inline long long gru_staged_index(int in, int h, long long e) {
   return e < R ? P * (in + h) + e : -1;         // b: pseudo-rows r, z, n_x
 }
 
+// ---- the recurrent stacks (csrc/lde_rnn.hip's launch code asks these): weight counts, the LDS / flat-weight layout of a
+// stack, which of the four kernel forms serves a call and with what launch shape, the k-split of the weight gradient. Every threshold is a
+// measurement on the MI355X.
+using lde::RnnDims;
+static bool rnn_desc_ok(const lde_rnn_desc* d) {
+  if (!d || d->abi_version != LDE_ABI_VERSION || d->n_layers < 1 || d->n_layers > LDE_RNN_MAX_LAYERS) return false;
+  if (d->cell < 0 || d->cell > LDE_CELL_GRU) return false;
+  for (int l = 0; l <= d->n_layers; l++)
+    if (d->sizes[l] < 1) return false;
+  return true;
+}
+// per cell kind: gate rows per unit as the kernels run them (GRU: its four pseudo-rows), gate rows per unit in the flat order, state vectors
+static int rnn_gate_rows(int cell) { return cell == LDE_CELL_LSTM || cell == LDE_CELL_GRU ? 4 : 1; }
+static int rnn_flat_rows(int cell) { return cell == LDE_CELL_LSTM ? 4 : cell == LDE_CELL_GRU ? 3 : 1; }
+static int rnn_state_vectors(int cell) { return cell == LDE_CELL_LSTM ? 2 : 1; }
+// floats of one cell in the flat weight vector: vec(Wi) [F·h × in], vec(Wh) [F·h × h], b [F·h], state0 [S·h] (−1: a size < 1, or a count
+// beyond int64) …
+static int64_t rnn_cell_weights(int cell, int64_t in, int64_t h) {
+  if (in < 1 || h < 1 || in > std::numeric_limits<int32_t>::max() || h > std::numeric_limits<int32_t>::max()) return -1;
+  const int64_t R = rnn_flat_rows(cell) * h;   // ≤ 2³³
+  int64_t n = 0;
+  if (__builtin_mul_overflow(R, in + h + 1, &n) || __builtin_add_overflow(n, rnn_state_vectors(cell) * h, &n)) return -1;
+  return n;
+}
+// … and of the stack (−1: not a description)
+static int64_t rnn_num_weights(const lde_rnn_desc* d) {
+  if (!rnn_desc_ok(d)) return -1;
+  int64_t n = 0;
+  for (int l = 0; l < d->n_layers; l++) {
+    const int64_t c = rnn_cell_weights(d->cell, d->sizes[l], d->sizes[l + 1]);
+    if (c < 0 || __builtin_add_overflow(n, c, &n)) return -1;
+  }
+  return n;
+}
+
+// The four kernel forms: the run-time-shaped kernel (any stack), and for the default stacks the compile-time-shaped kernel with its weight
+// rows in LDS (any workgroup size) or in registers (one wave per workgroup), and the two-wave pipeline (one wave per cell).
+enum RnnForm { RNN_FORM_GENERIC = 0, RNN_FORM_ROWS_LDS, RNN_FORM_ROWS_REG, RNN_FORM_PIPE };
+// LDS bytes of a launch with tpw trajectories per workgroup: the weight area, then per trajectory [x; h], the gate deltas and h, c, dh, dc
+// of every cell; the pipeline: per (cell, trajectory) the two vectors and 4·16 floats, the two rings of PIPE_R steps, the four counters
+static size_t rnn_lds_bytes(const RnnDims& rd, RnnForm form, int tpw) {
+  const int64_t t = std::min(std::max(tpw, 0), 64), nL = std::min(std::max(rd.nL, 0), lde::RNN_ML), w = rd.lds_w, v = (int64_t)rd.vmax + rd.rmax;   // (clamped: any RnnDims, no overflow)
+  const int64_t fl = form == RNN_FORM_PIPE ? w + 2 * t * (v + 4 * 16) + 2 * lde::PIPE_R * t * 16 + 16 : w + t * (v + 4 * nL * rd.hmax);
+  return fl > 0 ? (size_t)fl * sizeof(float) : 0;
+}
+
+// The layout of a stack: what the kernels index LDS and the flat weight vector with (lde::RnnDims), floats per trajectory of the initial
+// states' gradient (*g0w) and the weight count (*nW). Any description: LDE_ERR_INVALID_ARG for what is none, LDE_ERR_UNSUPPORTED with *why
+// for the three limits — checked before any arithmetic on the sizes (beyond them every product below fits an int many times over).
+static int rnn_layout(const lde_rnn_desc* d, size_t lds_max, RnnDims* out, int* g0w, int64_t* nW, const char** why = nullptr) {
+  auto refuse = [&](const char* m) {
+    if (why) *why = m;
+    return (int)LDE_ERR_UNSUPPORTED;
+  };
+  if (!out || !g0w || !nW || !rnn_desc_ok(d)) return LDE_ERR_INVALID_ARG;
+  RnnDims& rd = *out;
+  rd = RnnDims{};
+  *g0w = 0;
+  *nW = 0;
+  rd.cell = d->cell; rd.nL = d->n_layers; rd.reverse = d->reverse ? 1 : 0; rd.G = rnn_gate_rows(d->cell);
+  const bool gru = d->cell == LDE_CELL_GRU;
+  int hmax = 0, kmax = 0, rmax = 0;
+  for (int l = 0; l <= rd.nL; l++) rd.sizes[l] = d->sizes[l];
+  for (int l = 1; l <= rd.nL; l++) hmax = std::max(hmax, d->sizes[l]);
+  if (hmax > GRU_MAX_H || d->sizes[0] > GRU_MAX_IN)
+    return refuse("recurrent stack: hidden width ≤ 64 and input width ≤ 256 supported (every cell kind, LDE_CELL_GRU included)");
+  int Hp = 1;   // lanes per trajectory: one per gate row of the widest cell (≤ 64 ⇒ a trajectory never leaves its wave)
+  while (Hp < rd.G * hmax && Hp < 64) Hp <<= 1;
+  if (gru) Hp = gru_lanes(hmax);   // (the same rule; above 64 pseudo-rows a lane owns several: gru_rows_per_lane)
+  if (!gru && Hp < rd.G * hmax) return refuse("recurrent stack: G·h ≤ 64 gate rows per cell supported (LSTM: h ≤ 16, RNN: h ≤ 64)");
+  rd.Hp = Hp;
+  rd.hmax = hmax;
+  int off = 0;
+  int64_t foff = 0;
+  for (int l = 0; l < rd.nL; l++) {
+    const int in = rd.sizes[l], h = rd.sizes[l + 1], R = rd.G * h, K = in + h;
+    rd.K[l] = K;
+    rd.ldk[l] = lde::rnn_ldk(K);
+    rd.w_off[l] = off; off += R * rd.ldk[l];
+    rd.b_off[l] = off; off += (R + 3) & ~3;
+    rd.s_off[l] = off; off += (2 * h + 3) & ~3;
+    rd.f_off[l] = (int)foff;
+    foff += rnn_cell_weights(rd.cell, in, h);
+    kmax = std::max(kmax, K);
+    rmax = std::max(rmax, R);
+    *g0w += rnn_state_vectors(rd.cell) * h;
+  }
+  rd.vmax = ((kmax + 3) & ~3) + 4;
+  rd.rmax = (rmax + 3) & ~3;
+  rd.recw = (gru ? GRU_REC_ROWS : rd.G + 2) * hmax;
+  rd.lds_w = off;
+  for (int l = 0; l < rd.nL; l++) {   // transposed copies for the pullback, when they fit beside everything else at 16 trajectories per workgroup
+    rd.ldr[l] = lde::rnn_ldk(rd.G * rd.sizes[l + 1]);
+    rd.wt_off[l] = rd.lds_w;
+    rd.lds_w += rd.K[l] * rd.ldr[l];
+  }
+  rd.wt = rnn_lds_bytes(rd, RNN_FORM_GENERIC, 16) <= lds_max ? 1 : 0;
+  if (!rd.wt) rd.lds_w = off;
+  *nW = foff;
+  if (rnn_lds_bytes(rd, RNN_FORM_GENERIC, 16) > lds_max) return refuse("recurrent stack: weights do not fit the 160 KiB LDS");
+  return LDE_OK;
+}
+
+// the reference's default pattern extractors (32 → 16 → 16, two cells) [REF src/models/GOKU.jl:229-238]: the shape the compile-time forms exist for
+static bool rnn_default_shape(const RnnDims& rd) { return rd.wt && rd.nL == 2 && rd.sizes[0] == 32 && rd.sizes[1] == 16 && rd.sizes[2] == 16; }
+
+// One call on B trajectories. Trajectories per workgroup: the sweep is sequential in time and every trajectory re-reads the cell's weights
+// from LDS at every step, so a small batch is spread over as many CUs as it has waves (one wave per workgroup: the LDS of a CU then serves
+// one wave instead of sixteen); only a batch that would exceed ~4 workgroups per CU (1024) packs more trajectories behind one LDS copy of
+// the weights. One wave per workgroup (tpw·Hp = 64) of a default stack runs the register-row form (option "regw"), and by default the
+// pipeline, one wave per CELL (option "pipe"; not in an LDE_PROF build). Whole staging tiles of 16 trajectories are covered: rows past B
+// write zero panels.
+struct RnnPlan {
+  RnnForm form;
+  int tpw;
+  unsigned block, grid;
+  size_t lds_bytes;
+};
+static RnnPlan rnn_launch_plan(const RnnDims& rd, int B, int opt_generic, int opt_regw, int opt_pipe, bool prof) {
+  const int Hp = std::min(std::max(rd.Hp, 1), 64);
+  const int64_t b = std::max(B, 0);
+  RnnPlan p;
+  p.tpw = std::max(1, 64 / Hp);
+  while (p.tpw < 16 && (b + p.tpw - 1) / p.tpw > 1024) p.tpw *= 2;
+  const bool one_wave = p.tpw * Hp == 64 && opt_regw != 0;
+  const bool shaped = rnn_default_shape(rd) && opt_generic == 0;
+  p.form = !shaped ? RNN_FORM_GENERIC : !one_wave ? RNN_FORM_ROWS_LDS : (!prof && opt_pipe != 0) ? RNN_FORM_PIPE : RNN_FORM_ROWS_REG;
+  p.block = p.form == RNN_FORM_PIPE ? 128u : (unsigned)(p.tpw * Hp);
+  p.grid = (unsigned)((b + 15) / 16 * (16 / p.tpw));
+  p.lds_bytes = rnn_lds_bytes(rd, p.form, p.tpw);
+  return p;
+}
+// a grouped call runs several stacks in one launch of k_rnn_group, which switches between the RNN / LSTM bodies of the two single-wave forms
+static bool rnn_groupable(const RnnDims& rd, RnnForm form) {
+  return (form == RNN_FORM_ROWS_REG || form == RNN_FORM_PIPE) && rnn_default_shape(rd) && rd.cell != LDE_CELL_GRU;
+}
+// K-split parts of a cell's weight-gradient product: (staging tiles × jobs × parts) ≈ 512 workgroups, 1 … 8 parts
+static int rnn_dw_ksplit(int ntile, int jobs) {
+  const int64_t wg = (int64_t)ntile * jobs;
+  return wg < 1 ? 8 : (int)std::min<int64_t>(std::max<int64_t>((512 + wg - 1) / wg, 1), 8);
+}
+// The template arguments of the shaped recurrent kernels: calls f(CELL, MODE) with std::integral_constants for the four cell kinds × the
+// four modes (0 forward, 1 pullback, 2 training forward, 3 pullback from kept records) and returns what f returns; anything else is
+// LDE_ERR_UNSUPPORTED. rnn_dispatch_mode: the mode alone (k_rnn_group).
+template <class F>
+static int rnn_dispatch_mode(int mode, F&& f) {
+  switch (mode) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+  }
+  return LDE_ERR_UNSUPPORTED;
+}
+template <class F>
+static int rnn_dispatch(int cell, int mode, F&& f) {
+  auto with = [&](auto C) { return rnn_dispatch_mode(mode, [&](auto M) { return f(C, M); }); };
+  switch (cell) {
+    case LDE_CELL_RNN_RELU: return with(std::integral_constant<int, LDE_CELL_RNN_RELU>{});
+    case LDE_CELL_RNN_TANH: return with(std::integral_constant<int, LDE_CELL_RNN_TANH>{});
+    case LDE_CELL_LSTM: return with(std::integral_constant<int, LDE_CELL_LSTM>{});
+    case LDE_CELL_GRU: return with(std::integral_constant<int, LDE_CELL_GRU>{});
+  }
+  return LDE_ERR_UNSUPPORTED;
+}
+
 static KOpts make_opts(const lde_problem_desc& d, const double* ts, int T, int B) {
   KOpts o;
   o.abstol = (float)d.abstol;

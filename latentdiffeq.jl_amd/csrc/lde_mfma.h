@@ -8,7 +8,9 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <mutex>
 #include <string>
+#include <vector>
 
 #include "lde_device.h"
 
@@ -281,6 +283,17 @@ inline void fill_layer_offsets(MlpDims& dm, size_t* nfrag, size_t* nfragT) {
 }
 
 static constexpr size_t LDS_MAX = 160 * 1024;
+// a kernel that may ask for the whole LDS (beyond the 64 KB a launch gets without asking) needs the attribute: once per kernel. Handles
+// may launch from several host threads at once: the list is locked.
+static bool set_max_lds_(const void* fn) {
+  static std::mutex mu;
+  static std::vector<const void*> done;
+  std::lock_guard<std::mutex> lk(mu);
+  if (std::find(done.begin(), done.end(), fn) != done.end()) return true;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) return false;
+  done.push_back(fn);
+  return true;
+}
 
 // ---- the weight gradient as one large-K product over everything the solve staged ---------------------------------------
 // grid (solve tile, K-split part, job). A job is a block of 32×32 tiles of ONE layer's gWᵀ[in×out]: a range of output

@@ -17,7 +17,7 @@
 // STAGES the (a, δ) = ([x_t;h_{t-1}], gate deltas) panels of every (step, layer) in the block layout of lde_mfma.h, so
 // that the weight gradient — the only matrix-shaped part: K' = B·T columns — is formed by the shared large-K MFMA kernel
 // k_mlp_dw, once per cell.
-// What sets the speed (DESIGN.md §4.6): trajectories per workgroup chosen at launch (a small batch runs one wave per
+// What sets the speed (DESIGN.md §4.5): trajectories per workgroup chosen at launch (a small batch runs one wave per
 // CU instead of sixteen waves queueing on one LDS), compile-time instantiations for the reference's default stacks (no
 // per-layer kernel-argument loads, run-time loops or branches: they were ≈ 60 % of a step), and branch-free prefetch of the
 // next frame / record (a load under a branch costs a vmcnt(0), which on gfx950 also drains the staging stores).
@@ -36,28 +36,6 @@
 namespace lde {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int RNN_ML = LDE_RNN_MAX_LAYERS;
-
-struct RnnDims {
-  int cell, nL, reverse, G;
-  int sizes[RNN_ML + 1];
-  int Hp;               // lanes per trajectory
-  int K[RNN_ML];        // in_l + h_l
-  int ldk[RNN_ML];      // row stride of [Wi | Wh] in LDS: ≥ pad4(K), (ldk/4) odd
-  int w_off[RNN_ML];    // LDS float offsets: rows [G·h][ldk]
-  int b_off[RNN_ML];    // bias [G·h]
-  int s_off[RNN_ML];    // state0: h0 [h] (LSTM: then c0 [h])
-  int f_off[RNN_ML];    // offset of the cell in the flat weight vector
-  int wt;               // 1: LDS also holds the transposed copies [K][ldr] (the pullback's Wᵀδ then reads 16-byte rows too)
-  int ldr[RNN_ML];      // their row stride: ≥ pad4(G·h), (ldr/4) odd
-  int wt_off[RNN_ML];
-  int lds_w;            // floats of the weight area
-  int vmax;             // floats of one trajectory's [x; h] vector (pad4(max K) + 4)
-  int rmax;             // floats of one trajectory's δ vector (pad4(max G·h))
-  int hmax;
-  int recw;             // floats of one (step, layer, trajectory) record: gates G·hmax | c hmax | h hmax
-};
 
 __device__ __forceinline__ float sigm(float x) { return fast_rcp(1.0f + __expf(-x)); }
 // tanh x = 1 − 2/(1 + e^{2x}): v_exp_f32 + v_rcp_f32, ≈ 2e-7 absolute (saturates cleanly: e^{2x} → ∞ ⇒ 1, → 0 ⇒ −1)
@@ -110,9 +88,6 @@ __device__ __forceinline__ void rnn_load_weights(const RnnDims& rd, const float*
   }
   __syncthreads();
 }
-
-constexpr int rnn_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
-__host__ __device__ constexpr int rnn_ldk(int K) { int v = (K + 3) & ~3; return ((v >> 2) & 1) ? v : v + 4; }
 
 }  // namespace lde
 #include "lde_rnn_gru.h"   // LDE_CELL_GRU: gru_load_weights, gru_body, k_gru, k_gru_gather
@@ -453,7 +428,6 @@ __device__ __forceinline__ void rnn_body(const RnnDims& rd, const RnnArgs& a, co
 // fence); wave 1 runs cell 2 on step s while wave 0 is on step s+1…. Backward the other way round: wave 1 publishes ∂L/∂h¹ₛ, wave 0
 // adds it to what its own step s+1 left. A producer PIPE_R steps ahead waits for the consumer's count. Records, staged panels, state
 // gradients: each wave its cell's, same addresses and same arithmetic as rnn_body ⇒ the same bits (tests/test_gpu_rnn.py).
-constexpr int PIPE_R = 8;
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 // v_permlane32_swap / v_permlane16_swap with both operands the same register: .x = the even rows (of 32 / 16 lanes) repeated, .y = the odd
 // rows repeated — a lane of row 0 reads its partner in row 1 in one VALU instruction instead of an LDS round trip (gfx950)
@@ -759,10 +733,7 @@ __device__ __forceinline__ void rnn_pipe_wave(const RnnDims& rd, const RnnArgs& 
   }
 }
 
-// LDS floats of the pipeline form beyond the weight area: per (cell, trajectory) buffers, the two rings, the four counters
-__host__ __device__ inline int rnn_pipe_extra_floats(const RnnDims& rd, int tpw) {
-  return 2 * tpw * (rd.vmax + rd.rmax + 4 * 16) + 2 * PIPE_R * tpw * 16 + 16;
-}
+// (LDS of the pipeline form beyond the weight area — per (cell, trajectory) buffers, the two rings, the four counters: lde_host::rnn_lds_bytes)
 template <int CELL_, int MODE_>
 __device__ __forceinline__ void rnn_body2(const RnnDims& rd, const RnnArgs& a, const unsigned bx) {
   extern __shared__ __attribute__((aligned(16))) float rsm[];
@@ -863,16 +834,17 @@ __global__ void __launch_bounds__(256) k_rnn_reduce_state0_group(ReduceState0Tab
 }  // namespace lde
 
 // ================================================ C ABI ======================================================
+// What touches no device — weight counts, the layout of a stack, which kernel form serves a call and its launch shape, the k-split of the
+// weight gradient — is decided in csrc/lde_host.h (rnn_layout, rnn_launch_plan, …: pure host logic, checked on the CPU by
+// tests/host_logic_driver.cpp). Below: the handle, the kernel lookup and the launches.
 using namespace lde;
 
 struct lde_rnn {
-  lde_rnn_desc d;
   RnnDims rd;
   MlpDims dmw[RNN_ML];     // one-layer descriptions [K_l → G·h_l] for the weight-gradient kernel
   int64_t nW = 0;
   float* W_dev = nullptr;
   bool have_W = false;
-  size_t lds = 0;
   int g0w = 0;
   DwSync dws;              // weight-gradient kernels on the dw stream (lde_set_dw_stream)
   int staged_T = 0, staged_B = 0;   // set by lde_rnn_backward_dx: the panels lde_rnn_backward_dw consumes
@@ -883,23 +855,24 @@ struct lde_rnn {
   float* wts = nullptr; size_t wts_cap = 0;
   float* g0 = nullptr; size_t g0_cap = 0;
   float* slab = nullptr; size_t slab_cap = 0; size_t slab_layer = 0;
-  int32_t* ints = nullptr; size_t ints_cap = 0;
+  int32_t* ints = nullptr;
   float* gtmp = nullptr; size_t gtmp_off[RNN_ML] = {0, 0, 0, 0};   // GRU: the staged weight-gradient products [4h × K] + [4h] per cell, before k_gru_gather
   bool accumulate = true;   // pullback: dW += gradient (default) or dW = gradient
   int opt_generic = 0, opt_regw = 1, opt_pipe = 1;   // lde_rnn_set_option: "generic", "regw", "pipe" (kernel-choice knobs of the parity tests)
   int opt_async_dw = 1;                              // "async_dw": with a dw stream set, a grouped pullback's weight-gradient products go there (0: stay on the caller's stream)
-  void (*kernel[4][3])(lde::RnnDims, lde::RnnArgs) = {};   // the k_rnn instantiations for this stack: [mode][any workgroup size, one wave per workgroup, one wave per cell]
-  int io_ldy = 0, io_lddy = 0;       // set around a call by the *_ld group entry points (0: rows are hL apart)
-  const float* io_dy2 = nullptr;
   std::string err;
 };
 
-static int rnn_desc_ok(const lde_rnn_desc* d) {
-  if (!d || d->abi_version != LDE_ABI_VERSION || d->n_layers < 1 || d->n_layers > LDE_RNN_MAX_LAYERS) return 0;
-  if (d->cell < 0 || d->cell > LDE_CELL_GRU) return 0;
-  for (int l = 0; l <= d->n_layers; l++)
-    if (d->sizes[l] < 1) return 0;
-  return 1;
+// records of a sweep (lde_rnn_forward_train) and staged panels (lde_rnn_backward_dx) the handle claims to hold: none / those of (x, T, B)
+static void rnn_drop_records(lde_rnn* r) {
+  r->kept_T = r->kept_B = 0;
+  r->kept_x = nullptr;
+  r->staged_T = r->staged_B = 0;
+}
+static void rnn_keep_records(lde_rnn* r, const float* x, int T, int B) {
+  r->kept_T = T;
+  r->kept_B = B;
+  r->kept_x = x;
 }
 
 // lde_chain.hip (lde_refresh_weights): the handle's own weight buffer, which that call fills
@@ -912,49 +885,60 @@ bool rnn_refresh_target(lde_rnn* r, float** W_dev, int64_t* nW) {
   return true;
 }
 
+// (cell, form, mode) → the kernel: the run-time-shaped one for any stack, the instantiations of the default stacks (32 → 16 → 16) otherwise
 typedef void (*rnn_kernel_t)(RnnDims, RnnArgs);
-template <int CELL_, bool ONE>
-static rnn_kernel_t rnn_pick_mode(int mode) {
-  switch (mode) {
-    case 0: return k_rnn<CELL_, 32, 16, 2, 0, ONE>;
-    case 1: return k_rnn<CELL_, 32, 16, 2, 1, ONE>;
-    case 2: return k_rnn<CELL_, 32, 16, 2, 2, ONE>;
-    default: return k_rnn<CELL_, 32, 16, 2, 3, ONE>;
-  }
+static rnn_kernel_t rnn_kernel(int cell, lde_host::RnnForm form, int mode) {
+  if (form == lde_host::RNN_FORM_GENERIC) return cell == LDE_CELL_GRU ? k_gru<false, 0, false> : k_rnn<-1, 0, 0, 0, 0>;   // (LDE_CELL_GRU: a body of its own, csrc/lde_rnn_gru.h)
+  rnn_kernel_t fn = nullptr;
+  (void)lde_host::rnn_dispatch(cell, mode, [&](auto C, auto M) {
+    constexpr int CELL_ = decltype(C)::value, MODE_ = decltype(M)::value;
+    if (form == lde_host::RNN_FORM_PIPE) fn = k_rnn2<CELL_, MODE_>;
+    else if constexpr (CELL_ == LDE_CELL_GRU) fn = form == lde_host::RNN_FORM_ROWS_REG ? k_gru<true, MODE_, true> : k_gru<true, MODE_, false>;
+    else fn = form == lde_host::RNN_FORM_ROWS_REG ? k_rnn<CELL_, 32, 16, 2, MODE_, true> : k_rnn<CELL_, 32, 16, 2, MODE_, false>;
+    return (int)LDE_OK;
+  });
+  return fn;
+}
+// (mode, pipeline or register rows) → the kernel of a grouped sweep
+static const void* rnn_group_kernel(int mode, bool pipe) {
+  const void* fn = nullptr;
+  (void)lde_host::rnn_dispatch_mode(mode, [&](auto M) {
+    constexpr int MODE_ = decltype(M)::value;
+    fn = pipe ? (const void*)k_rnn_group<MODE_, true> : (const void*)k_rnn_group<MODE_, false>;
+    return (int)LDE_OK;
+  });
+  return fn;
 }
 
-template <bool ONE>
-static rnn_kernel_t gru_pick_mode(int mode) {
-  switch (mode) {
-    case 0: return k_gru<true, 0, ONE>;
-    case 1: return k_gru<true, 1, ONE>;
-    case 2: return k_gru<true, 2, ONE>;
-    default: return k_gru<true, 3, ONE>;
-  }
-}
+// ---- grouped calls (lde_rnn_group_*): as in lde_chain.hip — a call that carries a recorder records at its launch sites; the group entry
+// point issues each stage once for all stacks where they ask for the same kernel family, one by one otherwise.
+struct RnnRecMain { rnn_kernel_t fn; bool groupable; lde_host::RnnPlan plan; RnnDims rd; RnnArgs a; };
+struct RnnRecDw { int ndw; MlpDims dm; DwArgs da; int gx, gy, gz; size_t lds; MlpDims rdm; ReduceArgs ra; unsigned rgrid; };
+struct RnnRecS0 { RnnDims rd; State0Args a; unsigned grid; };
+struct RnnGroupRec {
+  int n = 0;
+  bool main_set[RNN_GROUP_MAX] = {};
+  RnnRecMain main[RNN_GROUP_MAX];
+  int ndw = 0;
+  RnnRecDw dw[GROUP_MAX_DW];
+  int ns0 = 0;
+  RnnRecS0 s0[RNN_GROUP_MAX];
+  lde_rnn* hs[RNN_GROUP_MAX] = {};   // the stacks of the call (their weight-gradient events, when the group's products go to the dw stream)
+  int nhs = 0;
+};
+static_assert(sizeof(GroupTable<RnnDims, RnnArgs, RNN_GROUP_MAX>) <= 4096, "a group's argument table must fit the kernel-argument segment");
 
-template <int CELL_>
-static rnn_kernel_t rnn_pick_pipe(int mode) {
-  switch (mode) {
-    case 0: return k_rnn2<CELL_, 0>;
-    case 1: return k_rnn2<CELL_, 1>;
-    case 2: return k_rnn2<CELL_, 2>;
-    default: return k_rnn2<CELL_, 3>;
-  }
-}
+// What one call carries beyond its arrays; filled by the entry point, passed down by reference.
+struct RnnCall {
+  int ldy = 0, lddy = 0;         // floats between the rows of y / dy (0: the stack's output width)
+  const float* dy2 = nullptr;    // a second source of the output gradient
+  RnnGroupRec* rec = nullptr;    // a grouped call: the launch sites record into slot rec->n instead of launching, and the group entry point
+                                 // — not the stack's call — says what the handle holds afterwards
+};
 
 extern "C" {
 
-int64_t lde_rnn_num_weights(const lde_rnn_desc* d) {
-  if (!rnn_desc_ok(d)) return -1;
-  const int64_t G = d->cell == LDE_CELL_LSTM ? 4 : d->cell == LDE_CELL_GRU ? 3 : 1, S = d->cell == LDE_CELL_LSTM ? 2 : 1;
-  int64_t n = 0;
-  for (int l = 0; l < d->n_layers; l++) {
-    const int64_t in = d->sizes[l], h = d->sizes[l + 1];
-    n += G * h * in + G * h * h + G * h + S * h;
-  }
-  return n;
-}
+int64_t lde_rnn_num_weights(const lde_rnn_desc* d) { return lde_host::rnn_num_weights(d); }
 
 void lde_rnn_destroy(lde_rnn* r) {
   if (!r) return;
@@ -974,81 +958,30 @@ void lde_rnn_destroy(lde_rnn* r) {
 int lde_rnn_create(const lde_rnn_desc* d, lde_rnn** out) {
   if (!out) return LDE_ERR_INVALID_ARG;
   *out = nullptr;
-  if (!rnn_desc_ok(d)) return LDE_ERR_INVALID_ARG;
+  if (!lde_host::rnn_desc_ok(d)) return LDE_ERR_INVALID_ARG;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return LDE_ERR_NO_DEVICE;   // no CPU fallback
   lde_rnn* r = new lde_rnn();
   *out = r;
-  r->d = *d;
-  RnnDims& rd = r->rd;
-  std::memset(&rd, 0, sizeof(rd));
-  rd.cell = d->cell; rd.nL = d->n_layers; rd.reverse = d->reverse ? 1 : 0; rd.G = (d->cell == LDE_CELL_LSTM || d->cell == LDE_CELL_GRU) ? 4 : 1;   // gate rows per unit (GRU: its four pseudo-rows r, z, n_x, n_h)
-  const bool gru = d->cell == LDE_CELL_GRU;
-  int hmax = 0, kmax = 0, rmax = 0;
-  for (int l = 0; l <= d->n_layers; l++) rd.sizes[l] = d->sizes[l];
-  for (int l = 1; l <= d->n_layers; l++) hmax = std::max(hmax, d->sizes[l]);
-  if (hmax > 64 || d->sizes[0] > 256) {
-    r->err = "recurrent stack: hidden width ≤ 64 and input width ≤ 256 supported (every cell kind, LDE_CELL_GRU included)";
-    return LDE_ERR_UNSUPPORTED;
+  const char* why = "";
+  const int rc = lde_host::rnn_layout(d, LDS_MAX, &r->rd, &r->g0w, &r->nW, &why);
+  if (rc) {
+    r->err = why;
+    return rc;
   }
-  int Hp = 1;   // lanes per trajectory: one per gate row of the widest cell (≤ 64 ⇒ a trajectory never leaves its wave)
-  while (Hp < rd.G * hmax && Hp < 64) Hp <<= 1;
-  if (gru) Hp = lde_host::gru_lanes(hmax);   // (the same rule; above 64 pseudo-rows a lane owns several: lde_host::gru_rows_per_lane)
-  if (!gru && Hp < rd.G * hmax) {
-    r->err = "recurrent stack: G·h ≤ 64 gate rows per cell supported (LSTM: h ≤ 16, RNN: h ≤ 64)";
-    return LDE_ERR_UNSUPPORTED;
-  }
-  rd.Hp = Hp;
-  rd.hmax = hmax;
-  int off = 0, foff = 0;
-  r->g0w = 0;
-  for (int l = 0; l < rd.nL; l++) {
-    const int in = rd.sizes[l], h = rd.sizes[l + 1], R = rd.G * h, K = in + h;
-    rd.K[l] = K;
-    int v = (K + 3) & ~3;
-    if (((v >> 2) & 1) == 0) v += 4;
-    rd.ldk[l] = v;
-    rd.w_off[l] = off; off += R * v;
-    rd.b_off[l] = off; off += (R + 3) & ~3;
-    rd.s_off[l] = off; off += (2 * h + 3) & ~3;
-    rd.f_off[l] = foff;
-    foff += gru ? (int)lde_host::gru_cell_weights(in, h) : R * in + R * h + R + (d->cell == LDE_CELL_LSTM ? 2 : 1) * h;
-    kmax = std::max(kmax, K);
-    rmax = std::max(rmax, R);
-    r->g0w += (d->cell == LDE_CELL_LSTM ? 2 : 1) * h;
-    // one Dense-like layer [K → R] for the weight-gradient kernel: vec([Wi|Wh]) column-major then b = the cell's flat order
+  const RnnDims& rd = r->rd;
+  for (int l = 0; l < rd.nL; l++) {   // one Dense-like layer [K → R] for the weight-gradient kernel: vec([Wi|Wh]) column-major then b = the cell's flat order
     MlpDims& dm = r->dmw[l];
     std::memset(&dm, 0, sizeof(dm));
-    dm.nL = 1; dm.sizes[0] = K; dm.sizes[1] = R;
+    dm.nL = 1; dm.sizes[0] = rd.K[l]; dm.sizes[1] = rd.G * rd.sizes[l + 1];
     size_t nf, nft;
     fill_layer_offsets(dm, &nf, &nft);
-  }
-  {   // transposed copies for the pullback, when they fit beside everything else
-    int offT = off;
-    for (int l = 0; l < rd.nL; l++) {
-      rd.ldr[l] = rnn_ldk(rd.G * rd.sizes[l + 1]);
-      rd.wt_off[l] = offT;
-      offT += rd.K[l] * rd.ldr[l];
-    }
-    const size_t per_traj = (size_t)((kmax + 3) & ~3) + 4 + ((rmax + 3) & ~3) + 4 * rd.nL * hmax;
-    rd.wt = ((size_t)offT + 16 * per_traj) * sizeof(float) <= LDS_MAX ? 1 : 0;
-    if (rd.wt) off = offT;
-  }
-  rd.lds_w = off;
-  rd.vmax = ((kmax + 3) & ~3) + 4;
-  rd.rmax = (rmax + 3) & ~3;
-  rd.recw = (gru ? lde_host::GRU_REC_ROWS : rd.G + 2) * hmax;
-  r->nW = foff;
-  r->lds = ((size_t)rd.lds_w + 16 * ((size_t)rd.vmax + rd.rmax + 4 * rd.nL * hmax)) * sizeof(float);
-  if (r->lds > LDS_MAX) {
-    r->err = "recurrent stack: weights do not fit the 160 KiB LDS";
-    return LDE_ERR_UNSUPPORTED;
   }
   if (hipMalloc(&r->W_dev, (size_t)r->nW * sizeof(float)) != hipSuccess) {
     r->err = "recurrent stack: hipMalloc failed";
     return LDE_ERR_ALLOC;
   }
-  if (gru) {
+  if (rd.cell == LDE_CELL_GRU) {
     size_t n = 0;
     for (int l = 0; l < rd.nL; l++) { r->gtmp_off[l] = n; n += (size_t)lde_host::gru_staged_floats(rd.sizes[l], rd.sizes[l + 1]); }
     if (hipMalloc(&r->gtmp, n * sizeof(float)) != hipSuccess) {
@@ -1096,10 +1029,8 @@ int lde_rnn_reserve(lde_rnn* r, int B, int T) {
   size_t slab_need = 0;
   bool ok = grow(&r->rec, &r->rec_cap, (size_t)T * rd.nL * B * rd.recw) && grow(&r->wts, &r->wts_cap, ntile * T * NB) &&
             grow(&r->g0, &r->g0_cap, (size_t)B * r->g0w);
-  if (ok && !r->ints) {   // two zero words for the slab reduction (no private slabs; feedback sink)
+  if (ok && !r->ints)   // two zero words for the slab reduction (no private slabs; feedback sink)
     ok = hipMalloc(&r->ints, 64) == hipSuccess && hipMemset(r->ints, 0, 64) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
-    r->ints_cap = 16;
-  }
   for (int l = 0; l < rd.nL && ok; l++) {
     ok = grow(&r->stage[l], &r->stage_cap[l], ntile * T * r->dmw[l].blk_floats);
     slab_need = std::max(slab_need, (ntile * 8 + 1) * (size_t)r->dmw[l].slab_n);
@@ -1113,96 +1044,58 @@ int lde_rnn_reserve(lde_rnn* r, int B, int T) {
   return LDE_OK;
 }
 
+}  // extern "C"
 
-// the instantiation for this stack: the reference's default pattern extractors (32 → 16 → 16) have their own, any other shape
-// runs the run-time-shaped kernel
-static rnn_kernel_t rnn_pick(const RnnDims& rd, int mode, bool one_wave = false, bool generic_only = false) {
-  if (rd.cell == LDE_CELL_GRU) {   // a body of its own (csrc/lde_rnn_gru.h)
-    if (!generic_only && rd.wt && rd.nL == 2 && rd.sizes[0] == 32 && rd.sizes[1] == 16 && rd.sizes[2] == 16)
-      return one_wave ? gru_pick_mode<true>(mode) : gru_pick_mode<false>(mode);
-    return k_gru<false, 0, false>;
+// what every sweep checks first (`name`: the entry point the messages speak of)
+static int rnn_call_ok(lde_rnn* r, bool pointers, int T, int B, const char* name) {
+  if (!r || !r->W_dev) return LDE_ERR_INVALID_ARG;
+  if (!pointers || T < 1 || B < 1) {
+    r->err = std::string(name) + ": NULL pointer or empty batch";
+    return LDE_ERR_INVALID_ARG;
   }
-  if (!generic_only && rd.wt && rd.nL == 2 && rd.sizes[0] == 32 && rd.sizes[1] == 16 && rd.sizes[2] == 16) {
-    if (one_wave) {
-      if (rd.cell == LDE_CELL_LSTM) return rnn_pick_mode<LDE_CELL_LSTM, true>(mode);
-      if (rd.cell == LDE_CELL_RNN_RELU) return rnn_pick_mode<LDE_CELL_RNN_RELU, true>(mode);
-      if (rd.cell == LDE_CELL_RNN_TANH) return rnn_pick_mode<LDE_CELL_RNN_TANH, true>(mode);
-    } else {
-      if (rd.cell == LDE_CELL_LSTM) return rnn_pick_mode<LDE_CELL_LSTM, false>(mode);
-      if (rd.cell == LDE_CELL_RNN_RELU) return rnn_pick_mode<LDE_CELL_RNN_RELU, false>(mode);
-      if (rd.cell == LDE_CELL_RNN_TANH) return rnn_pick_mode<LDE_CELL_RNN_TANH, false>(mode);
-    }
+  if (!r->have_W) {
+    r->err = std::string(name) + ": weights not set";
+    return LDE_ERR_NO_WEIGHTS;
   }
-  return k_rnn<-1, 0, 0, 0, 0>;
+  return LDE_OK;
 }
 
-// ---- grouped calls (lde_rnn_group_*): as in lde_chain.hip — while a recorder is installed the launch sites record; the group entry point
-// issues each stage once for all stacks where they ask for the same kernel family, one by one otherwise.
-struct RnnRecMain { rnn_kernel_t fn; bool groupable, pipe; int mode; RnnDims rd; RnnArgs a; unsigned grid, block; size_t lds; };
-struct RnnRecDw { int ndw; MlpDims dm; DwArgs da; int gx, gy, gz; size_t lds; MlpDims rdm; ReduceArgs ra; unsigned rgrid; };
-struct RnnRecS0 { RnnDims rd; State0Args a; unsigned grid; };
-struct RnnGroupRec {
-  int n = 0;
-  bool main_set[RNN_GROUP_MAX] = {};
-  RnnRecMain main[RNN_GROUP_MAX];
-  int ndw = 0;
-  RnnRecDw dw[GROUP_MAX_DW];
-  int ns0 = 0;
-  RnnRecS0 s0[RNN_GROUP_MAX];
-  lde_rnn* hs[RNN_GROUP_MAX] = {};   // the stacks of the call (their weight-gradient events, when the group's products go to the dw stream)
-  int nhs = 0;
-};
-static thread_local RnnGroupRec* t_rrec = nullptr;
-static_assert(sizeof(GroupTable<RnnDims, RnnArgs, RNN_GROUP_MAX>) <= 4096, "a group's argument table must fit the kernel-argument segment");
+// the kernel arguments of a sweep (modes 1 – 3: with the handle's workspace, as lde_rnn_reserve left it)
+static RnnArgs rnn_args(const lde_rnn* r, int mode, const float* x, int T, int B, float* y, const float* dy, float* dx, const RnnCall& c) {
+  const RnnDims& rd = r->rd;
+  RnnArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.x = x; a.Wflat = r->W_dev; a.y = y; a.dy = dy; a.dx = dx; a.T = T; a.B = B; a.mode = mode;
+  a.ldy = c.ldy ? c.ldy : rd.sizes[rd.nL];
+  a.lddy = c.lddy ? c.lddy : rd.sizes[rd.nL];
+  a.dy2 = c.dy2;
+  if (mode != 0) {
+    a.rec = r->rec; a.wts = r->wts; a.g0 = r->g0; a.g0w = r->g0w;
+    for (int l = 0; l < rd.nL; l++) { a.stage[l] = r->stage[l]; a.blk[l] = r->dmw[l].blk_floats; }
+  }
+  return a;
+}
 
-static int rnn_launch(lde_rnn* r, const RnnArgs& a, int B, hipStream_t stream) {
+static int rnn_launch(lde_rnn* r, const RnnArgs& a, hipStream_t stream, const RnnCall& c) {
+  const RnnDims& rd = r->rd;
   const int m = a.mode & 3;
-  // Trajectories per workgroup. The sweep is sequential in time and every trajectory re-reads the cell's weights from LDS
-  // at every step, so a small batch is spread over as many CUs as it has waves (one wave per workgroup: the LDS of a CU then
-  // serves one wave instead of sixteen); only a batch that would exceed ~4 workgroups per CU packs more trajectories
-  // behind one LDS copy of the weights.
-  int tpw = std::max(1, 64 / r->rd.Hp);
-  while (tpw < 16 && cdiv(B, tpw) > 1024) tpw *= 2;
-  const bool one_wave = tpw * r->rd.Hp == 64 && r->opt_regw != 0;   // one wave per workgroup: the register-resident-weights instantiation (option "regw")
-  // … and, for the default shape, one wave per CELL (rnn_body2): option "pipe" = 0 keeps the single wave
-  const RnnDims& rd0 = r->rd;
-  const bool def_shape = rd0.wt && rd0.nL == 2 && rd0.sizes[0] == 32 && rd0.sizes[1] == 16 && rd0.sizes[2] == 16;
-  const bool generic_only = r->opt_generic != 0;
-  const bool pipe = one_wave && def_shape && !generic_only && !LDE_PROF && r->opt_pipe != 0;
-  const int one = pipe ? 2 : (one_wave ? 1 : 0);
-  if (!r->kernel[m][one]) {
-    if (pipe)
-      r->kernel[m][one] = rd0.cell == LDE_CELL_LSTM ? rnn_pick_pipe<LDE_CELL_LSTM>(m) : rd0.cell == LDE_CELL_GRU ? rnn_pick_pipe<LDE_CELL_GRU>(m)
-                          : rd0.cell == LDE_CELL_RNN_RELU ? rnn_pick_pipe<LDE_CELL_RNN_RELU>(m) : rnn_pick_pipe<LDE_CELL_RNN_TANH>(m);
-    else
-      r->kernel[m][one] = rnn_pick(r->rd, m, one != 0, generic_only);
-    if (hipFuncSetAttribute((const void*)r->kernel[m][one], hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) {
-      r->kernel[m][one] = nullptr;
-      r->err = "hipFuncSetAttribute(k_rnn) failed";
-      return LDE_ERR_HIP;
-    }
+  const lde_host::RnnPlan plan = lde_host::rnn_launch_plan(rd, a.B, r->opt_generic, r->opt_regw, r->opt_pipe, LDE_PROF != 0);
+  const rnn_kernel_t fn = rnn_kernel(rd.cell, plan.form, m);
+  if (!fn || !set_max_lds_((const void*)fn)) {
+    r->err = "hipFuncSetAttribute(k_rnn) failed";
+    return LDE_ERR_HIP;
   }
   RnnArgs aa = a;
-  aa.tpw = tpw;
-  const size_t lds = pipe ? ((size_t)r->rd.lds_w + rnn_pipe_extra_floats(r->rd, tpw)) * sizeof(float)
-                          : ((size_t)r->rd.lds_w + tpw * ((size_t)r->rd.vmax + r->rd.rmax + 4 * r->rd.nL * r->rd.hmax)) * sizeof(float);
-  const unsigned block = pipe ? 128u : (unsigned)(tpw * r->rd.Hp);
-  // whole staging tiles are covered (rows past B write zero panels and zero column weights)
+  aa.tpw = plan.tpw;
 #if LDE_PROF
   { long long z[64] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof(z)); }
 #endif
-  if (t_rrec) {
-    RnnRecMain& q = t_rrec->main[t_rrec->n];
-    q.fn = r->kernel[m][one];
-    const RnnDims& rd = r->rd;
-    q.groupable = one && rd.wt && rd.nL == 2 && rd.sizes[0] == 32 && rd.sizes[1] == 16 && rd.sizes[2] == 16 &&
-                  q.fn != (rnn_kernel_t)k_rnn<-1, 0, 0, 0, 0> && rd.cell != LDE_CELL_GRU;   // (k_rnn_group switches between the RNN / LSTM bodies only)
-    q.pipe = pipe;
-    q.mode = m; q.rd = rd; q.a = aa; q.grid = (unsigned)(cdiv(B, 16) * (16 / tpw)); q.block = block; q.lds = lds;
-    t_rrec->main_set[t_rrec->n] = true;
+  if (c.rec) {
+    c.rec->main[c.rec->n] = RnnRecMain{fn, lde_host::rnn_groupable(rd, plan.form), plan, rd, aa};
+    c.rec->main_set[c.rec->n] = true;
     return LDE_OK;
   }
-  hipLaunchKernelGGL(r->kernel[m][one], dim3(cdiv(B, 16) * (16 / tpw)), dim3(block), lds, stream, r->rd, aa);
+  hipLaunchKernelGGL(fn, dim3(plan.grid), dim3(plan.block), plan.lds_bytes, stream, rd, aa);
   if (hipGetLastError() != hipSuccess) {
     r->err = "k_rnn launch failed";
     return LDE_ERR_HIP;
@@ -1224,151 +1117,86 @@ static int rnn_launch(lde_rnn* r, const RnnArgs& a, int B, hipStream_t stream) {
   return LDE_OK;
 }
 
-int lde_rnn_forward(lde_rnn* r, const float* x, int T, int B, float* y, void* stream_) {
-  if (!r || !r->W_dev) return LDE_ERR_INVALID_ARG;
-  if (!x || !y || T < 1 || B < 1) {
-    r->err = "lde_rnn_forward: NULL pointer or empty batch";
-    return LDE_ERR_INVALID_ARG;
-  }
-  if (!r->have_W) {
-    r->err = "lde_rnn_forward: weights not set";
-    return LDE_ERR_NO_WEIGHTS;
-  }
-  RnnArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.x = x; a.Wflat = r->W_dev; a.y = y; a.T = T; a.B = B; a.mode = 0;
-  a.ldy = r->io_ldy ? r->io_ldy : r->rd.sizes[r->rd.nL];
-  return rnn_launch(r, a, B, (hipStream_t)stream_);
-}
-
-// Training variant of the forward call: the sweep also leaves its per-step records and the weight gradient's a-panels in the handle's
-// workspace, and the next lde_rnn_backward[_dx] on the SAME (x, T, B) runs the back-propagation alone instead of repeating the sweep
-// (what lde_chain_forward_save is to the chains; here the handle keeps the buffers — they are its staging area already).
-int lde_rnn_forward_train(lde_rnn* r, const float* x, int T, int B, float* y, void* stream_) {
-  if (!r || !r->W_dev) return LDE_ERR_INVALID_ARG;
-  if (!x || !y || T < 1 || B < 1) {
-    r->err = "lde_rnn_forward_train: NULL pointer or empty batch";
-    return LDE_ERR_INVALID_ARG;
-  }
-  if (!r->have_W) {
-    r->err = "lde_rnn_forward_train: weights not set";
-    return LDE_ERR_NO_WEIGHTS;
-  }
-  r->kept_T = r->kept_B = 0;
-  r->kept_x = nullptr;
-  r->staged_T = r->staged_B = 0;
-  int rc = lde_rnn_reserve(r, B, T);
+// The forward sweep. Training variant: it also leaves its per-step records and the weight gradient's a-panels in the handle's workspace,
+// and the next lde_rnn_backward[_dx] on the SAME (x, T, B) runs the back-propagation alone instead of repeating the sweep (what
+// lde_chain_forward_save is to the chains; here the handle keeps the buffers — they are its staging area already).
+static int rnn_forward_impl(lde_rnn* r, const float* x, int T, int B, float* y, bool train, hipStream_t stream, const RnnCall& c) {
+  const char* name = train ? "lde_rnn_forward_train" : "lde_rnn_forward";
+  int rc = rnn_call_ok(r, x && y, T, B, name);
   if (rc) return rc;
-  hipStream_t stream = (hipStream_t)stream_;
+  if (!train) return rnn_launch(r, rnn_args(r, 0, x, T, B, y, nullptr, nullptr, c), stream, c);
+  rnn_drop_records(r);
+  rc = lde_rnn_reserve(r, B, T);
+  if (rc) return rc;
   if (!dw_sync_begin(r->dws, stream)) {   // the workspace is about to be rewritten
-    r->err = "lde_rnn_forward_train: waiting for the previous weight gradient failed";
+    r->err = std::string(name) + ": waiting for the previous weight gradient failed";
     return LDE_ERR_HIP;
   }
-  const RnnDims& rd = r->rd;
-  RnnArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.x = x; a.Wflat = r->W_dev; a.y = y; a.rec = r->rec; a.wts = r->wts; a.g0 = r->g0; a.g0w = r->g0w;
-  a.ldy = r->io_ldy ? r->io_ldy : r->rd.sizes[r->rd.nL];
-  a.T = T; a.B = B; a.mode = 2;
-  for (int l = 0; l < rd.nL; l++) { a.stage[l] = r->stage[l]; a.blk[l] = r->dmw[l].blk_floats; }
-  rc = rnn_launch(r, a, B, stream);
+  rc = rnn_launch(r, rnn_args(r, 2, x, T, B, y, nullptr, nullptr, c), stream, c);
   if (rc) return rc;
-  r->kept_T = T;
-  r->kept_B = B;
-  r->kept_x = x;
+  if (!c.rec) rnn_keep_records(r, x, T, B);
   return LDE_OK;
 }
 
-// The pullback in two halves (include/lde.h): the sweep that produces dx and stages the panels, and the weight-gradient tail.
-int lde_rnn_backward_dx(lde_rnn* r, const float* x, const float* dy, int T, int B, float* dx, void* stream_) {
-  if (!r || !r->W_dev) return LDE_ERR_INVALID_ARG;
-  if (!x || !dy || T < 1 || B < 1) {
-    r->err = "lde_rnn_backward: NULL pointer or empty batch";
-    return LDE_ERR_INVALID_ARG;
-  }
-  if (!r->have_W) {
-    r->err = "lde_rnn_backward: weights not set";
-    return LDE_ERR_NO_WEIGHTS;
-  }
-  r->staged_T = r->staged_B = 0;
-  const bool kept = r->kept_T == T && r->kept_B == B && r->kept_x == x;   // lde_rnn_forward_train left the records and a-panels of this very call
-  r->kept_T = r->kept_B = 0;
-  r->kept_x = nullptr;
-  int rc = lde_rnn_reserve(r, B, T);
+// The pullback in two halves (include/lde.h): the sweep that produces dx and stages the panels …
+static int rnn_backward_dx_impl(lde_rnn* r, const float* x, const float* dy, int T, int B, float* dx, hipStream_t stream, const RnnCall& c) {
+  int rc = rnn_call_ok(r, x && dy, T, B, "lde_rnn_backward");
   if (rc) return rc;
-  hipStream_t stream = (hipStream_t)stream_;
+  const bool kept = r->kept_T == T && r->kept_B == B && r->kept_x == x;   // lde_rnn_forward_train left the records and a-panels of this very call
+  rnn_drop_records(r);
+  rc = lde_rnn_reserve(r, B, T);
+  if (rc) return rc;
   if (!kept && !dw_sync_begin(r->dws, stream)) {   // the workspace is about to be rewritten
     r->err = "lde_rnn_backward: waiting for the previous weight gradient failed";
     return LDE_ERR_HIP;
   }
-  const RnnDims& rd = r->rd;
-  RnnArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.x = x; a.Wflat = r->W_dev; a.rec = r->rec; a.dy = dy; a.dx = dx; a.wts = r->wts; a.g0 = r->g0; a.g0w = r->g0w;
-  a.lddy = r->io_lddy ? r->io_lddy : r->rd.sizes[r->rd.nL];
-  a.dy2 = r->io_dy2;
-  a.T = T; a.B = B; a.mode = kept ? 3 : 1;
-  for (int l = 0; l < rd.nL; l++) { a.stage[l] = r->stage[l]; a.blk[l] = r->dmw[l].blk_floats; }
-  rc = rnn_launch(r, a, B, stream);
+  rc = rnn_launch(r, rnn_args(r, kept ? 3 : 1, x, T, B, nullptr, dy, dx, c), stream, c);
   if (rc) return rc;
-  r->staged_T = T;
-  r->staged_B = B;
+  if (!c.rec) { r->staged_T = T; r->staged_B = B; }   // (a grouped call consumes its panels itself)
   return LDE_OK;
 }
 
-int lde_rnn_backward_dw(lde_rnn* r, float* dW, void* stream_) {
-  if (!r || !r->W_dev) return LDE_ERR_INVALID_ARG;
-  if (!dW) {
-    r->err = "lde_rnn_backward_dw: NULL pointer";
-    return LDE_ERR_INVALID_ARG;
-  }
-  if (r->staged_T < 1) {
-    r->err = "lde_rnn_backward_dw: no staged pullback (call lde_rnn_backward_dx first; its panels are consumed once)";
-    return LDE_ERR_INVALID_ARG;
-  }
-  const int T = r->staged_T, B = r->staged_B;
-  r->staged_T = r->staged_B = 0;
-  hipStream_t stream = (hipStream_t)stream_;
+// … and the weight-gradient tail over the panels of a (T, B) sweep
+static int rnn_backward_dw_impl(lde_rnn* r, int T, int B, float* dW, hipStream_t stream, const RnnCall& c) {
   const RnnDims& rd = r->rd;
   const int ntile = cdiv(B, 16);
   bool sw_ok = true;
-  hipStream_t wst = t_rrec ? stream : dw_sync_switch(r->dws, stream, &sw_ok);   // the weight-gradient kernels: on the dw stream when one is set (a grouped call's stay on the caller's)
+  hipStream_t wst = c.rec ? stream : dw_sync_switch(r->dws, stream, &sw_ok);   // the weight-gradient kernels: on the dw stream when one is set (a grouped call's: rnn_group_flush)
   if (!sw_ok) {
     r->err = "lde_rnn_backward: switching to the weight-gradient stream failed";
     return LDE_ERR_HIP;
   }
-  const bool gru = rd.cell == LDE_CELL_GRU;   // (never inside a grouped call's recorder: rnn_group_ok)
+  const int assign = r->accumulate ? 0 : 1;
   for (int l = 0; l < rd.nL; l++) {
+    const MlpDims& dm = r->dmw[l];
     DwArgs da;
     da.stage = r->stage[l]; da.wts = r->wts; da.nslots = nullptr; da.slab = r->slab + (size_t)l * r->slab_layer; da.cap = T; da.total = (long long)ntile * T;   // every tile staged exactly T slots
-    int ks = cdiv(512, ntile * dw_jobs(r->dmw[l], dw_pick_ndw(r->dmw[l])));
-    ks = ks < 1 ? 1 : (ks > 8 ? 8 : ks);
-    if (t_rrec && t_rrec->ndw < GROUP_MAX_DW) {
-      RnnRecDw& q = t_rrec->dw[t_rrec->ndw++];
-      q.ndw = dw_pick_ndw(r->dmw[l]); q.dm = r->dmw[l]; q.da = da; q.gx = ntile; q.gy = ks; q.gz = dw_jobs(r->dmw[l], q.ndw);
-      q.lds = dw_lds_floats(r->dmw[l], q.ndw) * sizeof(float);
-      q.rdm = r->dmw[l];
-      q.ra = ReduceArgs{nullptr, r->ints, 0, da.slab, ntile * ks, dW + rd.f_off[l], r->ints + 2, r->accumulate ? 0 : 1};
-      q.rgrid = (unsigned)cdiv(r->dmw[l].slab_n, 1024);
+    const int ndw = dw_pick_ndw(dm), ks = lde_host::rnn_dw_ksplit(ntile, dw_jobs(dm, ndw));
+    if (c.rec) {   // (rnn_group_fits: a slot for every (stack, cell) of the group)
+      RnnRecDw& q = c.rec->dw[c.rec->ndw++];
+      q.ndw = ndw; q.dm = dm; q.da = da; q.gx = ntile; q.gy = ks; q.gz = dw_jobs(dm, ndw);
+      q.lds = dw_lds_floats(dm, ndw) * sizeof(float);
+      q.rdm = dm;
+      q.ra = ReduceArgs{nullptr, r->ints, 0, da.slab, ntile * ks, dW + rd.f_off[l], r->ints + 2, assign};
+      q.rgrid = (unsigned)cdiv(dm.slab_n, 1024);
       continue;
     }
-    if (gru) {   // the product of the pseudo-rows, written; then its entries into the cell's flat order, added or written
-      int rc = launch_weight_gradient(r->dmw[l], da, ntile, ks, nullptr, r->ints, 0, r->gtmp + r->gtmp_off[l], r->ints + 2, wst, r->err, true);
+    if (rd.cell == LDE_CELL_GRU) {   // the product of the pseudo-rows, written; then its entries into the cell's flat order, added or written (never recorded: rnn_group_fits)
+      int rc = launch_weight_gradient(dm, da, ntile, ks, nullptr, r->ints, 0, r->gtmp + r->gtmp_off[l], r->ints + 2, wst, r->err, true);
       if (rc) return rc;
       const int in = rd.sizes[l], h = rd.sizes[l + 1];
       hipLaunchKernelGGL(k_gru_gather, dim3(cdiv((int)lde_host::gru_staged_count(in, h), 256)), dim3(256), 0, wst, r->gtmp + r->gtmp_off[l],
-                         dW + rd.f_off[l], in, h, r->accumulate ? 0 : 1);
+                         dW + rd.f_off[l], in, h, assign);
       continue;
     }
-    int rc = launch_weight_gradient(r->dmw[l], da, ntile, ks, nullptr, r->ints, 0, dW + rd.f_off[l], r->ints + 2, wst, r->err, !r->accumulate);
+    int rc = launch_weight_gradient(dm, da, ntile, ks, nullptr, r->ints, 0, dW + rd.f_off[l], r->ints + 2, wst, r->err, assign != 0);
     if (rc) return rc;
   }
-  if (t_rrec) {
-    RnnRecS0& q = t_rrec->s0[t_rrec->ns0++];
-    q.rd = rd; q.a = State0Args{r->g0, B, r->g0w, dW, r->accumulate ? 0 : 1}; q.grid = (unsigned)r->g0w;
+  if (c.rec) {
+    c.rec->s0[c.rec->ns0++] = RnnRecS0{rd, State0Args{r->g0, B, r->g0w, dW, assign}, (unsigned)r->g0w};
     return LDE_OK;
   }
-  hipLaunchKernelGGL(k_rnn_state0, dim3(r->g0w), dim3(64), 0, wst, r->g0, B, r->g0w, rd, dW, r->accumulate ? 0 : 1);
+  hipLaunchKernelGGL(k_rnn_state0, dim3(r->g0w), dim3(64), 0, wst, r->g0, B, r->g0w, rd, dW, assign);
   if (hipGetLastError() != hipSuccess || !dw_sync_end(r->dws, wst, stream)) {
     r->err = "recurrent stack: gradient kernels failed to launch";
     return LDE_ERR_HIP;
@@ -1376,39 +1204,34 @@ int lde_rnn_backward_dw(lde_rnn* r, float* dW, void* stream_) {
   return LDE_OK;
 }
 
-int lde_rnn_backward(lde_rnn* r, const float* x, const float* dy, int T, int B, float* dx, float* dW, void* stream_) {
-  if (r && r->W_dev && !dW) {
-    r->err = "lde_rnn_backward: NULL pointer or empty batch";
-    return LDE_ERR_INVALID_ARG;
-  }
-  const int rc = lde_rnn_backward_dx(r, x, dy, T, B, dx, stream_);
-  return rc ? rc : lde_rnn_backward_dw(r, dW, stream_);
+static int rnn_backward_impl(lde_rnn* r, const float* x, const float* dy, int T, int B, float* dx, float* dW, hipStream_t stream, const RnnCall& c) {
+  const int rc = rnn_backward_dx_impl(r, x, dy, T, B, dx, stream, c);
+  if (rc) return rc;
+  r->staged_T = r->staged_B = 0;   // consumed here
+  return rnn_backward_dw_impl(r, T, B, dW, stream, c);
 }
 
 static int rnn_group_flush(RnnGroupRec& g, hipStream_t stream) {
   const int n = g.n;
   {   // the sweeps
     bool any = false, same = n >= 2;
-    for (int j = 0; j < n; j++) { any = any || g.main_set[j]; same = same && g.main_set[j] && g.main[j].groupable && g.main[j].mode == g.main[0].mode && g.main[j].pipe == g.main[0].pipe; }
+    for (int j = 0; j < n; j++) {
+      any = any || g.main_set[j];
+      same = same && g.main_set[j] && g.main[j].groupable && g.main[j].a.mode == g.main[0].a.mode && g.main[j].plan.form == g.main[0].plan.form;
+    }
     if (any && same) {
       GroupTable<RnnDims, RnnArgs, RNN_GROUP_MAX> t{};
       t.n = n;
       size_t lds = 0;
-      for (int j = 0; j < n; j++) { t.start[j + 1] = t.start[j] + (int)g.main[j].grid; t.dims[j] = g.main[j].rd; t.args[j] = g.main[j].a; lds = std::max(lds, g.main[j].lds); }
-      static bool attr[8] = {};
-      const int m = g.main[0].mode;
-      const bool pipe = g.main[0].pipe;
-      const void* fn = pipe ? (m == 0 ? (const void*)k_rnn_group<0, true> : m == 1 ? (const void*)k_rnn_group<1, true> : m == 2 ? (const void*)k_rnn_group<2, true> : (const void*)k_rnn_group<3, true>)
-                            : (m == 0 ? (const void*)k_rnn_group<0> : m == 1 ? (const void*)k_rnn_group<1> : m == 2 ? (const void*)k_rnn_group<2> : (const void*)k_rnn_group<3>);
-      if (!attr[m + (pipe ? 4 : 0)]) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) return LDE_ERR_HIP;
-        attr[m + (pipe ? 4 : 0)] = true;
-      }
+      for (int j = 0; j < n; j++) { t.start[j + 1] = t.start[j] + (int)g.main[j].plan.grid; t.dims[j] = g.main[j].rd; t.args[j] = g.main[j].a; lds = std::max(lds, g.main[j].plan.lds_bytes); }
+      const bool pipe = g.main[0].plan.form == lde_host::RNN_FORM_PIPE;
+      const void* fn = rnn_group_kernel(g.main[0].a.mode & 3, pipe);
+      if (!fn || !set_max_lds_(fn)) return LDE_ERR_HIP;
       void* argv[] = {(void*)&t};
       (void)hipLaunchKernel(fn, dim3(t.start[n]), dim3(pipe ? 128 : 64), argv, lds, stream);
     } else if (any) {
       for (int j = 0; j < n; j++)
-        if (g.main_set[j]) hipLaunchKernelGGL(g.main[j].fn, dim3(g.main[j].grid), dim3(g.main[j].block), g.main[j].lds, stream, g.main[j].rd, g.main[j].a);
+        if (g.main_set[j]) hipLaunchKernelGGL(g.main[j].fn, dim3(g.main[j].plan.grid), dim3(g.main[j].plan.block), g.main[j].plan.lds_bytes, stream, g.main[j].rd, g.main[j].a);
     }
   }
   // With a weight-gradient stream set (lde_set_dw_stream) the products, their slab sums and the initial-state sums of the whole group go
@@ -1426,7 +1249,6 @@ static int rnn_group_flush(RnnGroupRec& g, hipStream_t stream) {
   if (g.ndw > 0) {   // the weight-gradient products of every (stack, cell), then their slab sums
     bool same = g.ndw >= 2;
     for (int j = 0; j < g.ndw; j++) same = same && g.dw[j].ndw == 1;
-    static bool attr[3] = {false, false, false};
     if (same) {
       GroupTable<MlpDims, DwArgs, GROUP_MAX_DW> t{};
       GroupTable<MlpDims, ReduceArgs, GROUP_MAX_DW> u{};
@@ -1437,10 +1259,7 @@ static int rnn_group_flush(RnnGroupRec& g, hipStream_t stream) {
         t.start[j + 1] = t.start[j] + q.gx * q.gy * q.gz; t.gx[j] = q.gx; t.gy[j] = q.gy; t.dims[j] = q.dm; t.args[j] = q.da; lds = std::max(lds, q.lds);
         u.start[j + 1] = u.start[j] + (int)q.rgrid; u.dims[j] = q.rdm; u.args[j] = q.ra;
       }
-      if (!attr[0]) {
-        if (hipFuncSetAttribute((const void*)k_mlp_dw_group<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) return LDE_ERR_HIP;
-        attr[0] = true;
-      }
+      if (!set_max_lds_((const void*)k_mlp_dw_group<1>)) return LDE_ERR_HIP;
       void* argv[] = {(void*)&t};
       (void)hipLaunchKernel((const void*)k_mlp_dw_group<1>, dim3(t.start[g.ndw]), dim3(512), argv, lds, stream);
       if (g.ns0 >= 2) {   // … and the initial-state sums ride on the slab sums' launch
@@ -1507,86 +1326,7 @@ static bool rnn_group_fits(int n, lde_rnn* const* rs) {   // every (stack, cell)
   }
   return jobs <= GROUP_MAX_DW;
 }
-int lde_rnn_group_forward(int n, lde_rnn* const* rs, const float* const* xs, int T, int B, float* const* ys, void* stream) {
-  if (n < 1 || !rs || !xs || !ys) return LDE_ERR_INVALID_ARG;
-  for (int i = 0; i < n; i++)
-    if (!rs[i]) return LDE_ERR_INVALID_ARG;
-  if (!rnn_group_ok(n) || !rnn_group_fits(n, rs)) {
-    for (int i = 0; i < n; i++) {
-      const int rc = lde_rnn_forward(rs[i], xs[i], T, B, ys[i], stream);
-      if (rc) return rc;
-    }
-    return LDE_OK;
-  }
-  RnnGroupRec g;
-  t_rrec = &g;
-  for (int i = 0; i < n; i++) {
-    g.n = i;
-    const int rc = lde_rnn_forward(rs[i], xs[i], T, B, ys[i], stream);
-    if (rc) { t_rrec = nullptr; return rc; }
-  }
-  g.n = n;
-  t_rrec = nullptr;
-  const int rc = rnn_group_flush(g, (hipStream_t)stream);
-  if (rc) rs[0]->err = "lde_rnn_group_forward: launch failed";
-  return rc;
-}
-int lde_rnn_group_forward_train(int n, lde_rnn* const* rs, const float* const* xs, int T, int B, float* const* ys, void* stream) {
-  if (n < 1 || !rs || !xs || !ys) return LDE_ERR_INVALID_ARG;
-  for (int i = 0; i < n; i++)
-    if (!rs[i]) return LDE_ERR_INVALID_ARG;
-  if (!rnn_group_ok(n) || !rnn_group_fits(n, rs)) {
-    for (int i = 0; i < n; i++) {
-      const int rc = lde_rnn_forward_train(rs[i], xs[i], T, B, ys[i], stream);
-      if (rc) return rc;
-    }
-    return LDE_OK;
-  }
-  RnnGroupRec g;
-  t_rrec = &g;
-  for (int i = 0; i < n; i++) {
-    g.n = i;
-    const int rc = lde_rnn_forward_train(rs[i], xs[i], T, B, ys[i], stream);
-    if (rc) { t_rrec = nullptr; return rc; }
-  }
-  g.n = n;
-  t_rrec = nullptr;
-  const int rc = rnn_group_flush(g, (hipStream_t)stream);
-  if (rc) rs[0]->err = "lde_rnn_group_forward_train: launch failed";
-  return rc;
-}
-int lde_rnn_group_backward(int n, lde_rnn* const* rs, const float* const* xs, const float* const* dys, int T, int B, float* const* dxs,
-                           float* const* dWs, void* stream) {
-  if (n < 1 || !rs || !xs || !dys || !dWs) return LDE_ERR_INVALID_ARG;
-  for (int i = 0; i < n; i++)
-    if (!rs[i] || !dWs[i]) return LDE_ERR_INVALID_ARG;
-  if (!rnn_group_ok(n) || !rnn_group_fits(n, rs)) {
-    for (int i = 0; i < n; i++) {
-      const int rc = lde_rnn_backward(rs[i], xs[i], dys[i], T, B, dxs ? dxs[i] : nullptr, dWs[i], stream);
-      if (rc) return rc;
-    }
-    return LDE_OK;
-  }
-  RnnGroupRec g;
-  t_rrec = &g;
-  g.nhs = n;
-  for (int i = 0; i < n; i++) g.hs[i] = rs[i];
-  for (int i = 0; i < n; i++) {
-    g.n = i;
-    int rc = lde_rnn_backward_dx(rs[i], xs[i], dys[i], T, B, dxs ? dxs[i] : nullptr, stream);
-    if (!rc) rc = lde_rnn_backward_dw(rs[i], dWs[i], stream);
-    if (rc) { t_rrec = nullptr; return rc; }
-  }
-  g.n = n;
-  t_rrec = nullptr;
-  const int rc = rnn_group_flush(g, (hipStream_t)stream);
-  if (rc) rs[0]->err = "lde_rnn_group_backward: launch failed";
-  return rc;
-}
-
-// The grouped calls with the stacks' outputs (and output gradients) as column blocks of wider [B × ld] arrays, and a second source for
-// each output gradient: what the GOKU encoder needs to run pattern extractor → vcat → latent_in and back without a concatenation, two
-// strided copies and two additions as launches of their own (include/lde.h).
+// The stacks' outputs (and output gradients) may be column blocks of wider [B × ld] arrays (the *_ld entry points; lds == nullptr: none is)
 static int rnn_ld_ok(int n, lde_rnn* const* rs, const int* lds, const char* what) {
   for (int i = 0; i < n; i++) {
     if (!rs[i]) return LDE_ERR_INVALID_ARG;
@@ -1597,31 +1337,116 @@ static int rnn_ld_ok(int n, lde_rnn* const* rs, const int* lds, const char* what
   }
   return LDE_OK;
 }
+// One grouped call: per_stack(i, call) makes stack i's call(s). A group the recorder cannot serve (one stack, a GRU stack, a repeated handle)
+// runs them one after the other, each launching and accounting for itself; otherwise they record, the stages are launched once, and only
+// then do the handles claim the records their sweeps left — a stack refused mid-group leaves every stack of the group without any.
+template <class F>
+static int rnn_group_run(int n, lde_rnn* const* rs, hipStream_t stream, const char* name, F&& per_stack) {
+  RnnCall c;
+  if (!rnn_group_ok(n) || !rnn_group_fits(n, rs)) {
+    for (int i = 0; i < n; i++) {
+      const int rc = per_stack(i, c);
+      if (rc) return rc;
+    }
+    return LDE_OK;
+  }
+  RnnGroupRec g;
+  c.rec = &g;
+  g.nhs = n;
+  for (int i = 0; i < n; i++) g.hs[i] = rs[i];
+  int rc = LDE_OK;
+  for (int i = 0; i < n && !rc; i++) {
+    g.n = i;
+    rc = per_stack(i, c);
+  }
+  if (!rc) {
+    g.n = n;
+    rc = rnn_group_flush(g, stream);
+    if (rc) rs[0]->err = std::string(name) + ": launch failed";
+  }
+  for (int i = 0; i < n; i++) {
+    if (rc) rnn_drop_records(rs[i]);
+    else if (g.main_set[i] && g.main[i].a.mode == 2) rnn_keep_records(rs[i], g.main[i].a.x, g.main[i].a.T, g.main[i].a.B);
+  }
+  return rc;
+}
+static int rnn_group_forward(int n, lde_rnn* const* rs, const float* const* xs, int T, int B, float* const* ys, const int* ldys, bool train,
+                             void* stream, const char* ld_name) {
+  if (n < 1 || !rs || !xs || !ys) return LDE_ERR_INVALID_ARG;
+  const int rc = rnn_ld_ok(n, rs, ldys, ld_name);
+  if (rc) return rc;
+  return rnn_group_run(n, rs, (hipStream_t)stream, train ? "lde_rnn_group_forward_train" : "lde_rnn_group_forward", [&](int i, RnnCall c) {
+    c.ldy = ldys ? ldys[i] : 0;
+    return rnn_forward_impl(rs[i], xs[i], T, B, ys[i], train, (hipStream_t)stream, c);
+  });
+}
+static int rnn_group_backward(int n, lde_rnn* const* rs, const float* const* xs, const float* const* dys, const float* const* dys2,
+                              const int* lddys, int T, int B, float* const* dxs, float* const* dWs, void* stream, const char* ld_name) {
+  if (n < 1 || !rs || !xs || !dys || !dWs) return LDE_ERR_INVALID_ARG;
+  const int rc = rnn_ld_ok(n, rs, lddys, ld_name);
+  if (rc) return rc;
+  for (int i = 0; i < n; i++)
+    if (!dWs[i]) return LDE_ERR_INVALID_ARG;
+  return rnn_group_run(n, rs, (hipStream_t)stream, "lde_rnn_group_backward", [&](int i, RnnCall c) {
+    c.lddy = lddys ? lddys[i] : 0;
+    c.dy2 = dys2 ? dys2[i] : nullptr;
+    return rnn_backward_impl(rs[i], xs[i], dys[i], T, B, dxs ? dxs[i] : nullptr, dWs[i], (hipStream_t)stream, c);
+  });
+}
+
+extern "C" {
+
+int lde_rnn_forward(lde_rnn* r, const float* x, int T, int B, float* y, void* stream) {
+  return rnn_forward_impl(r, x, T, B, y, false, (hipStream_t)stream, RnnCall{});
+}
+int lde_rnn_forward_train(lde_rnn* r, const float* x, int T, int B, float* y, void* stream) {
+  return rnn_forward_impl(r, x, T, B, y, true, (hipStream_t)stream, RnnCall{});
+}
+int lde_rnn_backward_dx(lde_rnn* r, const float* x, const float* dy, int T, int B, float* dx, void* stream) {
+  return rnn_backward_dx_impl(r, x, dy, T, B, dx, (hipStream_t)stream, RnnCall{});
+}
+int lde_rnn_backward_dw(lde_rnn* r, float* dW, void* stream) {
+  if (!r || !r->W_dev) return LDE_ERR_INVALID_ARG;
+  if (!dW) {
+    r->err = "lde_rnn_backward_dw: NULL pointer";
+    return LDE_ERR_INVALID_ARG;
+  }
+  if (r->staged_T < 1) {
+    r->err = "lde_rnn_backward_dw: no staged pullback (call lde_rnn_backward_dx first; its panels are consumed once)";
+    return LDE_ERR_INVALID_ARG;
+  }
+  const int T = r->staged_T, B = r->staged_B;
+  r->staged_T = r->staged_B = 0;
+  return rnn_backward_dw_impl(r, T, B, dW, (hipStream_t)stream, RnnCall{});
+}
+int lde_rnn_backward(lde_rnn* r, const float* x, const float* dy, int T, int B, float* dx, float* dW, void* stream) {
+  if (r && r->W_dev && !dW) {
+    r->err = "lde_rnn_backward: NULL pointer or empty batch";
+    return LDE_ERR_INVALID_ARG;
+  }
+  return rnn_backward_impl(r, x, dy, T, B, dx, dW, (hipStream_t)stream, RnnCall{});
+}
+
+int lde_rnn_group_forward(int n, lde_rnn* const* rs, const float* const* xs, int T, int B, float* const* ys, void* stream) {
+  return rnn_group_forward(n, rs, xs, T, B, ys, nullptr, false, stream, "");
+}
+int lde_rnn_group_forward_train(int n, lde_rnn* const* rs, const float* const* xs, int T, int B, float* const* ys, void* stream) {
+  return rnn_group_forward(n, rs, xs, T, B, ys, nullptr, true, stream, "");
+}
+int lde_rnn_group_backward(int n, lde_rnn* const* rs, const float* const* xs, const float* const* dys, int T, int B, float* const* dxs,
+                           float* const* dWs, void* stream) {
+  return rnn_group_backward(n, rs, xs, dys, nullptr, nullptr, T, B, dxs, dWs, stream, "");
+}
+// The grouped calls with the stacks' outputs (and output gradients) as column blocks of wider [B × ld] arrays, and a second source for
+// each output gradient: what the GOKU encoder needs to run pattern extractor → vcat → latent_in and back without a concatenation, two
+// strided copies and two additions as launches of their own (include/lde.h).
 int lde_rnn_group_forward_ld(int n, lde_rnn* const* rs, const float* const* xs, int T, int B, float* const* ys, const int* ldys, int train,
                              void* stream) {
-  if (n < 1 || !rs || !xs || !ys) return LDE_ERR_INVALID_ARG;
-  int rc = rnn_ld_ok(n, rs, ldys, "lde_rnn_group_forward_ld");
-  if (rc) return rc;
-  for (int i = 0; i < n; i++) rs[i]->io_ldy = ldys ? ldys[i] : 0;
-  rc = train ? lde_rnn_group_forward_train(n, rs, xs, T, B, ys, stream) : lde_rnn_group_forward(n, rs, xs, T, B, ys, stream);
-  for (int i = 0; i < n; i++) rs[i]->io_ldy = 0;
-  return rc;
+  return rnn_group_forward(n, rs, xs, T, B, ys, ldys, train != 0, stream, "lde_rnn_group_forward_ld");
 }
 int lde_rnn_group_backward_ld(int n, lde_rnn* const* rs, const float* const* xs, const float* const* dys, const float* const* dys2,
                               const int* lddys, int T, int B, float* const* dxs, float* const* dWs, void* stream) {
-  if (n < 1 || !rs || !xs || !dys || !dWs) return LDE_ERR_INVALID_ARG;
-  int rc = rnn_ld_ok(n, rs, lddys, "lde_rnn_group_backward_ld");
-  if (rc) return rc;
-  for (int i = 0; i < n; i++) {
-    rs[i]->io_lddy = lddys ? lddys[i] : 0;
-    rs[i]->io_dy2 = dys2 ? dys2[i] : nullptr;
-  }
-  rc = lde_rnn_group_backward(n, rs, xs, dys, T, B, dxs, dWs, stream);
-  for (int i = 0; i < n; i++) {
-    rs[i]->io_lddy = 0;
-    rs[i]->io_dy2 = nullptr;
-  }
-  return rc;
+  return rnn_group_backward(n, rs, xs, dys, dys2, lddys, T, B, dxs, dWs, stream, "lde_rnn_group_backward_ld");
 }
 
 int lde_rnn_set_accumulate(lde_rnn* r, int on) {
@@ -1639,8 +1464,6 @@ int lde_rnn_set_option(lde_rnn* r, const char* key, double value) {
     return LDE_ERR_INVALID_ARG;
   }
   *slot = (int)value;
-  for (auto& km : r->kernel)      // the instantiations are cached per (mode, form): picked afresh under the new options
-    for (auto& k : km) k = nullptr;
   return LDE_OK;
 }
 

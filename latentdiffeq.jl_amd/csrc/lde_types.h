@@ -106,6 +106,32 @@ struct ChainLdsDims {
   size_t xs_per_cg = 0;       // bf16 forward reading x in place: bytes of the first layer's chunk buffers per column group (else 0)
 };
 
+// The layout of a recurrent stack (csrc/lde_rnn.hip), filled by csrc/lde_host.h: rnn_layout and handed to the kernels by value: the rows
+// of [Wi | Wh], biases and initial states of every cell in LDS, the cells' places in the flat weight vector, the per-trajectory buffers.
+constexpr int RNN_ML = LDE_RNN_MAX_LAYERS;
+struct RnnDims {
+  int cell, nL, reverse, G;
+  int sizes[RNN_ML + 1];
+  int Hp;               // lanes per trajectory
+  int K[RNN_ML];        // in_l + h_l
+  int ldk[RNN_ML];      // row stride of [Wi | Wh] in LDS: ≥ pad4(K), (ldk/4) odd
+  int w_off[RNN_ML];    // LDS float offsets: rows [G·h][ldk]
+  int b_off[RNN_ML];    // bias [G·h]
+  int s_off[RNN_ML];    // state0: h0 [h] (LSTM: then c0 [h])
+  int f_off[RNN_ML];    // offset of the cell in the flat weight vector
+  int wt;               // 1: LDS also holds the transposed copies [K][ldr] (the pullback's Wᵀδ then reads 16-byte rows too)
+  int ldr[RNN_ML];      // their row stride: ≥ pad4(G·h), (ldr/4) odd
+  int wt_off[RNN_ML];
+  int lds_w;            // floats of the weight area
+  int vmax;             // floats of one trajectory's [x; h] vector (pad4(max K) + 4)
+  int rmax;             // floats of one trajectory's δ vector (pad4(max G·h))
+  int hmax;
+  int recw;             // floats of one (step, layer, trajectory) record: gates G·hmax | c hmax | h hmax
+};
+LDE_HD constexpr int rnn_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
+LDE_HD constexpr int rnn_ldk(int K) { int v = (K + 3) & ~3; return ((v >> 2) & 1) ? v : v + 4; }
+constexpr int PIPE_R = 8;   // steps of the LDS rings of the two-wave pipeline (rnn_body2)
+
 // Options handed to every kernel by value (mirrors the `kwargs...` splat into solve()).
 struct KOpts {
   float abstol, reltol;

@@ -535,8 +535,268 @@ int main() {
     assert(chain_dw_parts_bf16(8, 12800, 64) == 32 && chain_dw_parts_bf16(8, 100, 64) == 2 && chain_dw_parts_bf16(300, 12800, 64) == 1);
     assert(chain_dw_parts_bf16(8, 64, 64) == 1 && chain_dw_parts_bf16(8, 65, 64) == 2 && chain_dw_parts_bf16(1, 1 << 20, 64) == 256);
   }
+  // 11. the recurrent stacks (csrc/lde_rnn.hip's launch code asks these): weight counts, the LDS / flat-weight layout, the kernel form and
+  //     launch shape of a call, groupability, the k-split of the weight gradient. Pins: the formulas lde_rnn_create / rnn_launch had inline.
+  int n_rnn_ok = 0, n_rnn_bad = 0;
+  {
+    const size_t CAP = 160 * 1024;
+    auto desc = [](int cell, std::vector<int> sizes, int reverse = 0) {
+      lde_rnn_desc d;
+      std::memset(&d, 0, sizeof(d));
+      d.abi_version = LDE_ABI_VERSION; d.cell = cell; d.n_layers = (int)sizes.size() - 1; d.reverse = reverse;
+      for (size_t i = 0; i < sizes.size(); i++) d.sizes[i] = sizes[i];
+      return d;
+    };
+    struct Laid { int rc; lde::RnnDims rd; int g0w; int64_t nW; const char* why; };
+    auto lay = [&](int cell, std::vector<int> sizes, size_t cap = 160 * 1024) {
+      Laid r;
+      r.why = "";
+      const lde_rnn_desc d = desc(cell, sizes, 1);
+      r.rc = rnn_layout(&d, cap, &r.rd, &r.g0w, &r.nW, &r.why);
+      assert(r.rc != LDE_OK || r.nW == rnn_num_weights(&d));
+      return r;
+    };
+    auto two = [](const int* a, int x, int y) { return a[0] == x && a[1] == y; };
+    // per-cell constants and counts
+    assert(rnn_gate_rows(LDE_CELL_RNN_RELU) == 1 && rnn_gate_rows(LDE_CELL_RNN_TANH) == 1 && rnn_gate_rows(LDE_CELL_LSTM) == 4 && rnn_gate_rows(LDE_CELL_GRU) == 4);
+    assert(rnn_flat_rows(LDE_CELL_RNN_RELU) == 1 && rnn_flat_rows(LDE_CELL_LSTM) == 4 && rnn_flat_rows(LDE_CELL_GRU) == 3);
+    assert(rnn_state_vectors(LDE_CELL_RNN_TANH) == 1 && rnn_state_vectors(LDE_CELL_LSTM) == 2 && rnn_state_vectors(LDE_CELL_GRU) == 1);
+    assert(rnn_cell_weights(LDE_CELL_LSTM, 32, 16) == 3168 && rnn_cell_weights(LDE_CELL_RNN_RELU, 32, 16) == 800 && rnn_cell_weights(LDE_CELL_RNN_TANH, 3, 2) == 14);
+    assert(rnn_cell_weights(LDE_CELL_RNN_RELU, 8, 100) == 100 * 8 + 100 * 100 + 100 + 100);   // (the count is defined beyond what lde_rnn_create serves)
+    for (int in : {1, 5, 32, 256}) for (int h : {1, 7, 16, 64}) assert(rnn_cell_weights(LDE_CELL_GRU, in, h) == gru_cell_weights(in, h));
+    assert(rnn_cell_weights(LDE_CELL_LSTM, 0, 16) == -1 && rnn_cell_weights(LDE_CELL_LSTM, 16, -3) == -1);
+    assert(rnn_cell_weights(LDE_CELL_LSTM, std::numeric_limits<int>::max(), std::numeric_limits<int>::max()) == -1);   // 4·2⁶² does not fit
+    assert(rnn_cell_weights(LDE_CELL_RNN_RELU, std::numeric_limits<int>::max(), 1) == (int64_t)std::numeric_limits<int>::max() + 3);
+    assert(rnn_cell_weights(LDE_CELL_RNN_RELU, std::numeric_limits<int64_t>::max(), 1) == -1);
+    {
+      lde_rnn_desc d = desc(LDE_CELL_LSTM, {32, 16, 16});
+      assert(rnn_num_weights(&d) == 5312 && rnn_num_weights(nullptr) == -1);
+      d.abi_version++;
+      assert(rnn_num_weights(&d) == -1 && !rnn_desc_ok(&d));
+      d = desc(LDE_CELL_RNN_RELU, {8, 100});
+      assert(rnn_num_weights(&d) == 11000);
+      d = desc(LDE_CELL_LSTM, {std::numeric_limits<int>::max(), std::numeric_limits<int>::max()});
+      assert(rnn_desc_ok(&d) && rnn_num_weights(&d) == -1);
+    }
+    // the layout of the default LSTM stack 32 → 16 → 16
+    const Laid lstm = lay(LDE_CELL_LSTM, {32, 16, 16});
+    {
+      const lde::RnnDims& r = lstm.rd;
+      assert(lstm.rc == LDE_OK && r.cell == LDE_CELL_LSTM && r.nL == 2 && r.reverse == 1 && r.G == 4 && r.Hp == 64 && r.hmax == 16);
+      assert(two(r.K, 48, 32) && two(r.ldk, 52, 36) && two(r.w_off, 0, 3424) && two(r.b_off, 3328, 5728) && two(r.s_off, 3392, 5792) && two(r.f_off, 0, 3168));
+      assert(lstm.nW == 5312 && two(r.ldr, 68, 68) && two(r.wt_off, 5824, 9088) && r.wt == 1 && r.lds_w == 11264);
+      assert(r.vmax == 52 && r.rmax == 64 && r.recw == 96 && lstm.g0w == 64 && r.sizes[0] == 32 && r.sizes[1] == 16 && r.sizes[2] == 16);
+    }
+    // … of the default RNN stack …
+    const Laid relu = lay(LDE_CELL_RNN_RELU, {32, 16, 16});
+    {
+      const lde::RnnDims& r = relu.rd;
+      assert(relu.rc == LDE_OK && r.G == 1 && r.Hp == 16 && r.hmax == 16 && two(r.K, 48, 32) && two(r.ldk, 52, 36));
+      assert(two(r.w_off, 0, 880) && two(r.b_off, 832, 1456) && two(r.s_off, 848, 1472) && two(r.f_off, 0, 800) && relu.nW == 1344);
+      assert(two(r.ldr, 20, 20) && two(r.wt_off, 1504, 2464) && r.wt == 1 && r.lds_w == 3104 && r.vmax == 52 && r.rmax == 16 && r.recw == 48 && relu.g0w == 32);
+    }
+    // … and of the default GRU stack: the LSTM's LDS layout (four pseudo-rows), three gate rows in the flat order, records of five rows
+    const Laid gru = lay(LDE_CELL_GRU, {32, 16, 16});
+    {
+      const lde::RnnDims& r = gru.rd;
+      assert(gru.rc == LDE_OK && r.G == 4 && r.Hp == 64 && two(r.ldk, 52, 36) && two(r.w_off, 0, 3424) && two(r.b_off, 3328, 5728) && two(r.s_off, 3392, 5792));
+      assert(two(r.f_off, 0, 2368) && gru.nW == 3968 && gru.nW == gru_cell_weights(32, 16) + gru_cell_weights(16, 16) && r.f_off[1] == gru_cell_weights(32, 16));
+      assert(two(r.ldr, 68, 68) && two(r.wt_off, 5824, 9088) && r.wt == 1 && r.lds_w == 11264 && r.vmax == 52 && r.rmax == 64 && r.recw == 80 && gru.g0w == 32);
+    }
+    // a run-time shape with three cells, and a one-layer RNN 256 → 64: served, but the transposed copy does not fit beside 16 trajectories
+    const Laid nd = lay(LDE_CELL_RNN_TANH, {5, 7, 3, 9}), wide = lay(LDE_CELL_RNN_TANH, {256, 64});
+    {
+      const lde::RnnDims& r = nd.rd;
+      assert(nd.rc == LDE_OK && r.Hp == 16 && r.hmax == 9 && r.ldk[0] == 12 && r.ldk[1] == 12 && r.ldk[2] == 12 && r.w_off[2] == 156 && r.s_off[2] == 276);
+      assert(r.f_off[1] == 98 && r.f_off[2] == 134 && nd.nW == 260 && r.ldr[1] == 4 && r.wt_off[0] == 296 && r.wt_off[2] == 480 && r.wt == 1 && r.lds_w == 624);
+      assert(r.vmax == 16 && r.rmax == 12 && r.recw == 27 && nd.g0w == 19);
+      const lde::RnnDims& w = wide.rd;
+      assert(wide.rc == LDE_OK && w.wt == 0 && w.Hp == 64 && w.ldk[0] == 324 && w.b_off[0] == 20736 && w.s_off[0] == 20800 && w.lds_w == 20928 && w.wt_off[0] == 20928);
+      assert(w.ldr[0] == 68 && w.vmax == 324 && w.rmax == 64 && w.recw == 192 && wide.nW == 20608 && wide.g0w == 64);
+      assert(rnn_lds_bytes(w, RNN_FORM_GENERIC, 16) == 124928 && rnn_lds_bytes(w, RNN_FORM_GENERIC, 1) == 86288);
+      assert(lay(LDE_CELL_RNN_TANH, {256, 64}, 124927).rc == LDE_ERR_UNSUPPORTED && lay(LDE_CELL_RNN_TANH, {256, 64}, 124928).rc == LDE_OK);
+      // with room for (20928 + 320·68 + 16·644)·4 bytes the copy is there
+      assert(lay(LDE_CELL_RNN_TANH, {256, 64}, 211967).rd.wt == 0 && lay(LDE_CELL_RNN_TANH, {256, 64}, 211968).rd.wt == 1 && lay(LDE_CELL_RNN_TANH, {256, 64}, 211968).rd.lds_w == 42688);
+    }
+    // the three refusals, each with its text; what is no description at all
+    {
+      Laid r = lay(LDE_CELL_RNN_RELU, {8, 65});
+      assert(r.rc == LDE_ERR_UNSUPPORTED && !std::strcmp(r.why, "recurrent stack: hidden width ≤ 64 and input width ≤ 256 supported (every cell kind, LDE_CELL_GRU included)"));
+      r = lay(LDE_CELL_GRU, {257, 8});
+      assert(r.rc == LDE_ERR_UNSUPPORTED && std::strstr(r.why, "input width ≤ 256"));
+      assert(lay(LDE_CELL_RNN_RELU, {256, 64}).rc == LDE_OK && lay(LDE_CELL_GRU, {256, 16}).rc == LDE_OK && lay(LDE_CELL_GRU, {8, 64}).rc == LDE_OK);
+      r = lay(LDE_CELL_LSTM, {8, 17});
+      assert(r.rc == LDE_ERR_UNSUPPORTED && !std::strcmp(r.why, "recurrent stack: G·h ≤ 64 gate rows per cell supported (LSTM: h ≤ 16, RNN: h ≤ 64)"));
+      assert(lay(LDE_CELL_LSTM, {8, 16}).rc == LDE_OK && lay(LDE_CELL_GRU, {8, 17}).rc == LDE_OK && lay(LDE_CELL_LSTM, {20, 24, 8}).rc == LDE_ERR_UNSUPPORTED);
+      r = lay(LDE_CELL_RNN_RELU, {256, 64, 64, 64, 64});
+      assert(r.rc == LDE_ERR_UNSUPPORTED && !std::strcmp(r.why, "recurrent stack: weights do not fit the 160 KiB LDS"));
+      assert(lay(LDE_CELL_GRU, {256, 64, 64, 64, 64}).rc == LDE_ERR_UNSUPPORTED);
+      lde_rnn_desc d = desc(LDE_CELL_LSTM, {32, 16, 16});
+      lde::RnnDims rd;
+      int g0w;
+      int64_t nW;
+      assert(rnn_layout(nullptr, CAP, &rd, &g0w, &nW) == LDE_ERR_INVALID_ARG && rnn_layout(&d, CAP, nullptr, &g0w, &nW) == LDE_ERR_INVALID_ARG);
+      d.cell = -1;
+      assert(rnn_layout(&d, CAP, &rd, &g0w, &nW) == LDE_ERR_INVALID_ARG);
+      d.cell = LDE_CELL_GRU + 1;
+      assert(rnn_layout(&d, CAP, &rd, &g0w, &nW) == LDE_ERR_INVALID_ARG);
+      d.cell = LDE_CELL_LSTM; d.n_layers = LDE_RNN_MAX_LAYERS + 1;
+      assert(rnn_layout(&d, CAP, &rd, &g0w, &nW) == LDE_ERR_INVALID_ARG);
+      d.n_layers = 2; d.sizes[1] = 0;
+      assert(rnn_layout(&d, CAP, &rd, &g0w, &nW) == LDE_ERR_INVALID_ARG);
+    }
+    // the default shape: two cells 32 → 16 → 16 WITH the transposed copies
+    {
+      assert(rnn_default_shape(lstm.rd) && rnn_default_shape(relu.rd) && rnn_default_shape(gru.rd) && !rnn_default_shape(nd.rd) && !rnn_default_shape(wide.rd));
+      lde::RnnDims r = lstm.rd;
+      r.wt = 0;
+      assert(!rnn_default_shape(r));
+      assert(!rnn_default_shape(lay(LDE_CELL_LSTM, {32, 16}).rd) && !rnn_default_shape(lay(LDE_CELL_LSTM, {32, 16, 16, 16}).rd));
+      assert(!rnn_default_shape(lay(LDE_CELL_LSTM, {31, 16, 16}).rd) && !rnn_default_shape(lay(LDE_CELL_LSTM, {32, 15, 16}).rd) && !rnn_default_shape(lay(LDE_CELL_LSTM, {32, 16, 12}).rd));
+    }
+    // the per-call plan on both sides of every threshold; LDS bytes as the two expressions rnn_launch had
+    auto plan_is = [](const RnnPlan& p, RnnForm f, int tpw, unsigned block, unsigned grid, size_t lds) {
+      return p.form == f && p.tpw == tpw && p.block == block && p.grid == grid && p.lds_bytes == lds;
+    };
+    auto plan = [](const Laid& s, int B, int generic = 0, int regw = 1, int pipe = 1, bool prof = false) { return rnn_launch_plan(s.rd, B, generic, regw, pipe, prof); };
+    auto old_lds = [](const lde::RnnDims& r, bool pipe, int tpw) {
+      return pipe ? ((size_t)r.lds_w + 2 * tpw * (r.vmax + r.rmax + 4 * 16) + 2 * 8 * tpw * 16 + 16) * sizeof(float)
+                  : ((size_t)r.lds_w + tpw * ((size_t)r.vmax + r.rmax + 4 * r.nL * r.hmax)) * sizeof(float);
+    };
+    for (const Laid* s : {&lstm, &gru}) {   // 64 lanes per trajectory: one trajectory per workgroup up to B = 1024, then 2, 4, 8, 16
+      assert(plan_is(plan(*s, 1), RNN_FORM_PIPE, 1, 128, 16, 47584) && plan_is(plan(*s, 5), RNN_FORM_PIPE, 1, 128, 16, 47584));
+      assert(plan_is(plan(*s, 1024), RNN_FORM_PIPE, 1, 128, 1024, 47584) && plan_is(plan(*s, 1025), RNN_FORM_ROWS_LDS, 2, 128, 520, 47008));
+      assert(plan_is(plan(*s, 2048), RNN_FORM_ROWS_LDS, 2, 128, 1024, 47008) && plan_is(plan(*s, 2049), RNN_FORM_ROWS_LDS, 4, 256, 516, 48960));
+      assert(plan_is(plan(*s, 4096), RNN_FORM_ROWS_LDS, 4, 256, 1024, 48960) && plan_is(plan(*s, 4097), RNN_FORM_ROWS_LDS, 8, 512, 514, 52864));
+      assert(plan_is(plan(*s, 8192), RNN_FORM_ROWS_LDS, 8, 512, 1024, 52864) && plan_is(plan(*s, 8193), RNN_FORM_ROWS_LDS, 16, 1024, 513, 60672));
+      assert(plan_is(plan(*s, 16385), RNN_FORM_ROWS_LDS, 16, 1024, 1025, 60672) && plan_is(plan(*s, 100000), RNN_FORM_ROWS_LDS, 16, 1024, 6250, 60672));
+      // the options: "pipe" = 0 and an LDE_PROF build keep the single wave, "regw" = 0 the LDS rows, "generic" the run-time-shaped kernel
+      assert(plan_is(plan(*s, 1024, 0, 1, 0), RNN_FORM_ROWS_REG, 1, 64, 1024, 46032) && plan_is(plan(*s, 1024, 0, 1, 1, true), RNN_FORM_ROWS_REG, 1, 64, 1024, 46032));
+      assert(plan_is(plan(*s, 1024, 0, 0, 1), RNN_FORM_ROWS_LDS, 1, 64, 1024, 46032) && plan_is(plan(*s, 1024, 1, 1, 1), RNN_FORM_GENERIC, 1, 64, 1024, 46032));
+      assert(plan(*s, 1025, 0, 1, 0).form == RNN_FORM_ROWS_LDS && plan(*s, 1025, 0, 1, 1, true).form == RNN_FORM_ROWS_LDS && plan(*s, 1025, 1).form == RNN_FORM_GENERIC);
+      assert(plan(*s, 5, 0, 7, 3).form == RNN_FORM_PIPE && plan(*s, 5, 2).form == RNN_FORM_GENERIC);   // any non-zero value switches
+    }
+    // 16 lanes per trajectory: four trajectories fill the wave up to B = 4096
+    assert(plan_is(plan(relu, 1), RNN_FORM_PIPE, 4, 128, 4, 20800) && plan_is(plan(relu, 4096), RNN_FORM_PIPE, 4, 128, 1024, 20800));
+    assert(plan_is(plan(relu, 4097), RNN_FORM_ROWS_LDS, 8, 128, 514, 18688) && plan_is(plan(relu, 8192), RNN_FORM_ROWS_LDS, 8, 128, 1024, 18688));
+    assert(plan_is(plan(relu, 8193), RNN_FORM_ROWS_LDS, 16, 256, 513, 24960) && plan_is(plan(relu, 100000), RNN_FORM_ROWS_LDS, 16, 256, 6250, 24960));
+    assert(plan_is(plan(relu, 4096, 0, 1, 0), RNN_FORM_ROWS_REG, 4, 64, 1024, 15552) && plan_is(plan(relu, 4096, 0, 0), RNN_FORM_ROWS_LDS, 4, 64, 1024, 15552));
+    assert(plan(relu, 4096, 0, 1, 1, true).form == RNN_FORM_ROWS_REG && plan(relu, 4096, 1).form == RNN_FORM_GENERIC && plan(relu, 4097, 0, 1, 0).form == RNN_FORM_ROWS_LDS);
+    assert(plan(lay(LDE_CELL_RNN_TANH, {8, 4}), 5).tpw == 16 && plan(lay(LDE_CELL_RNN_TANH, {8, 4}), 5).grid == 1 && plan(lay(LDE_CELL_RNN_TANH, {8, 2}), 5).tpw == 32 && plan(lay(LDE_CELL_RNN_TANH, {8, 2}), 5).grid == 0);
+    // a shape without instantiation: always the run-time-shaped kernel, the same workgroup rule
+    for (int B : {1, 5, 1024, 4096, 4097, 8193, 100000})
+      for (int o = 0; o < 16; o++) assert(plan(nd, B, o & 1, (o >> 1) & 1, (o >> 2) & 1, (o >> 3) & 1).form == RNN_FORM_GENERIC && plan(wide, B, o & 1, (o >> 1) & 1, (o >> 2) & 1, (o >> 3) & 1).form == RNN_FORM_GENERIC);
+    assert(plan_is(plan(nd, 4096), RNN_FORM_GENERIC, 4, 64, 1024, 4672) && plan_is(plan(nd, 4097), RNN_FORM_GENERIC, 8, 128, 514, 6848) && plan_is(plan(nd, 8193), RNN_FORM_GENERIC, 16, 256, 513, 11200));
+    assert(plan_is(plan(wide, 1024), RNN_FORM_GENERIC, 1, 64, 1024, 86288) && plan_is(plan(wide, 1025), RNN_FORM_GENERIC, 2, 128, 520, 88864) && plan_is(plan(wide, 8193), RNN_FORM_GENERIC, 16, 1024, 513, 124928));
+    for (const Laid* s : {&lstm, &relu, &gru, &nd, &wide})
+      for (int tpw : {1, 2, 4, 8, 16}) {
+        for (RnnForm f : {RNN_FORM_GENERIC, RNN_FORM_ROWS_LDS, RNN_FORM_ROWS_REG}) assert(rnn_lds_bytes(s->rd, f, tpw) == old_lds(s->rd, false, tpw));
+        assert(rnn_lds_bytes(s->rd, RNN_FORM_PIPE, tpw) == old_lds(s->rd, true, tpw));
+      }
+    // groupable: the two single-wave forms of a default RNN / LSTM stack
+    assert(rnn_groupable(lstm.rd, RNN_FORM_PIPE) && rnn_groupable(lstm.rd, RNN_FORM_ROWS_REG) && rnn_groupable(relu.rd, RNN_FORM_PIPE) && rnn_groupable(relu.rd, RNN_FORM_ROWS_REG));
+    assert(!rnn_groupable(lstm.rd, RNN_FORM_ROWS_LDS) && !rnn_groupable(lstm.rd, RNN_FORM_GENERIC) && !rnn_groupable(relu.rd, RNN_FORM_GENERIC));
+    for (RnnForm f : {RNN_FORM_GENERIC, RNN_FORM_ROWS_LDS, RNN_FORM_ROWS_REG, RNN_FORM_PIPE}) assert(!rnn_groupable(gru.rd, f) && !rnn_groupable(nd.rd, f) && !rnn_groupable(wide.rd, f));
+    // the k-split of the weight gradient: ⌈512 / (tiles × jobs)⌉ clamped to 1 … 8
+    assert(rnn_dw_ksplit(1, 1) == 8 && rnn_dw_ksplit(16, 4) == 8 && rnn_dw_ksplit(64, 1) == 8 && rnn_dw_ksplit(65, 1) == 8 && rnn_dw_ksplit(73, 1) == 8 && rnn_dw_ksplit(74, 1) == 7);
+    assert(rnn_dw_ksplit(16, 8) == 4 && rnn_dw_ksplit(256, 1) == 2 && rnn_dw_ksplit(511, 1) == 2 && rnn_dw_ksplit(512, 1) == 1 && rnn_dw_ksplit(513, 1) == 1 && rnn_dw_ksplit(6250, 4) == 1);
+    assert(rnn_dw_ksplit(0, 4) == 8 && rnn_dw_ksplit(-3, 4) == 8 && rnn_dw_ksplit(std::numeric_limits<int>::max(), std::numeric_limits<int>::max()) == 1);
+    // the shaped kernels' template arguments: four cell kinds × four modes, nothing else
+    {
+      int seen[4][4] = {};
+      auto rec = [&](auto C, auto M) -> int { seen[decltype(C)::value][decltype(M)::value]++; return 10 * decltype(C)::value + decltype(M)::value; };
+      static_assert(LDE_CELL_RNN_RELU == 0 && LDE_CELL_RNN_TANH == 1 && LDE_CELL_LSTM == 2 && LDE_CELL_GRU == 3, "cell codes");
+      for (int c = 0; c < 4; c++)
+        for (int m = 0; m < 4; m++) assert(rnn_dispatch(c, m, rec) == 10 * c + m && seen[c][m] == 1);
+      assert(rnn_dispatch(-1, 0, rec) == LDE_ERR_UNSUPPORTED && rnn_dispatch(4, 0, rec) == LDE_ERR_UNSUPPORTED && rnn_dispatch(2, 4, rec) == LDE_ERR_UNSUPPORTED && rnn_dispatch(2, -1, rec) == LDE_ERR_UNSUPPORTED);
+      int modes = 0;
+      for (int m = -2; m < 7; m++) assert(rnn_dispatch_mode(m, [&](auto M) -> int { modes++; return decltype(M)::value; }) == (m >= 0 && m < 4 ? m : (int)LDE_ERR_UNSUPPORTED));
+      assert(modes == 4);
+      for (int it = 0; it < 20000; it++) {
+        const int c = hostile_int(), m = hostile_int();
+        int called = 0;
+        const int rc = rnn_dispatch(c, m, [&](auto, auto) -> int { called++; return LDE_OK; });
+        assert(called == (c >= 0 && c < 4 && m >= 0 && m < 4) && rc == (called ? LDE_OK : LDE_ERR_UNSUPPORTED));
+      }
+    }
+    // hostile descriptions: a status for every one, no arithmetic on what is refused; an accepted layout has its areas in ascending order
+    // and inside the weight area, the weight area with 16 trajectories' buffers inside the LDS, the cells in order in the flat vector
+    for (int it = 0; it < 200000; it++) {
+      lde_rnn_desc d = desc((int)(rnd() % 4), {32, 16, 16}, (int)(rnd() & 1));
+      d.n_layers = 1 + (int)(rnd() % LDE_RNN_MAX_LAYERS);
+      for (int l = 0; l <= LDE_RNN_MAX_LAYERS; l++) d.sizes[l] = (rnd() % 3) ? 1 + (int)(rnd() % (l == 0 ? 300 : 70)) : 1 + (int)(rnd() % 20);
+      const int nmut = (int)(rnd() % 3);
+      for (int m = 0; m < nmut; m++) {
+        switch (rnd() % 5) {
+          case 0: d.abi_version = hostile_int(); break;
+          case 1: d.cell = hostile_int(); break;
+          case 2: d.n_layers = hostile_int(); break;
+          case 3: d.reverse = hostile_int(); break;
+          default: d.sizes[rnd() % (LDE_RNN_MAX_LAYERS + 1)] = hostile_int(); break;
+        }
+      }
+      const size_t cap = (rnd() & 3) ? CAP : (rnd() & 1) ? (size_t)(rnd() % (2 * CAP)) : (size_t)rnd();
+      lde::RnnDims rd;
+      int g0w = -1;
+      int64_t nW = -1;
+      const char* why = nullptr;
+      const int rc = rnn_layout(&d, cap, &rd, &g0w, &nW, &why);
+      const int64_t cnt = rnn_num_weights(&d);
+      assert((cnt >= 0) == rnn_desc_ok(&d) || cnt == -1);
+      if (rc != LDE_OK) {
+        n_rnn_bad++;
+        assert(rc == LDE_ERR_INVALID_ARG ? !rnn_desc_ok(&d) : (rc == LDE_ERR_UNSUPPORTED && why && std::strstr(why, "recurrent stack: ")));
+        continue;
+      }
+      n_rnn_ok++;
+      assert(nW == cnt && nW > 0 && g0w > 0 && rd.Hp >= 1 && rd.Hp <= 64 && (rd.Hp & (rd.Hp - 1)) == 0 && rd.nL == d.n_layers && rd.reverse == (d.reverse ? 1 : 0));
+      assert(rd.cell == LDE_CELL_GRU ? rd.Hp == gru_lanes(rd.hmax) : rd.Hp >= rd.G * rd.hmax);
+      int end = 0;
+      int64_t fend = 0;
+      for (int l = 0; l < rd.nL; l++) {
+        const int h = rd.sizes[l + 1], R = rd.G * h;
+        assert(rd.K[l] == rd.sizes[l] + h && rd.ldk[l] >= rd.K[l] && rd.ldk[l] % 4 == 0 && ((rd.ldk[l] / 4) & 1) && rd.ldk[l] <= rd.vmax && R <= rd.rmax);
+        assert(rd.w_off[l] == end && rd.b_off[l] == rd.w_off[l] + R * rd.ldk[l] && rd.s_off[l] >= rd.b_off[l] + R && rd.s_off[l] % 4 == 0);
+        end = rd.s_off[l] + ((2 * h + 3) & ~3);
+        assert(rd.f_off[l] == fend);
+        fend += rnn_cell_weights(rd.cell, rd.sizes[l], h);
+      }
+      assert(fend == nW);
+      for (int l = 0; l < rd.nL; l++) {
+        assert(rd.wt_off[l] == end && rd.ldr[l] >= rd.G * rd.sizes[l + 1] && ((rd.ldr[l] / 4) & 1) && rd.ldr[l] % 4 == 0);
+        end += rd.K[l] * rd.ldr[l];
+      }
+      assert(rd.lds_w == (rd.wt ? end : rd.wt_off[0]) && rnn_lds_bytes(rd, RNN_FORM_GENERIC, 16) <= cap);
+      // … and its plan for any batch and options: a form the stack has, a grid that covers whole staging tiles, LDS within the 16-trajectory bound
+      const int B = (rnd() & 1) ? 1 + (int)(rnd() % 20000) : hostile_int();
+      const RnnPlan p = rnn_launch_plan(rd, B, (int)(rnd() & 1), (int)(rnd() & 1), (int)(rnd() & 1), rnd() & 1);
+      // (a stack no wider than two gate rows — Hp ≤ 2 — starts at 32 / 64 trajectories per workgroup, more than a staging tile: grid 0, a
+      //  launch the runtime refuses. As the launch code always had it; pinned, not served.)
+      assert(p.tpw >= 1 && p.tpw <= 64 && (p.tpw & (p.tpw - 1)) == 0 && p.tpw * rd.Hp >= 64 && p.block >= 64 && p.block <= 1024 && (p.tpw <= 16) == (rd.Hp >= 4));
+      assert(rnn_default_shape(rd) || p.form == RNN_FORM_GENERIC);
+      if (p.form == RNN_FORM_PIPE || p.form == RNN_FORM_ROWS_REG) assert(p.tpw * rd.Hp == 64);
+      if (p.form != RNN_FORM_PIPE && p.tpw <= 16) assert(p.lds_bytes <= cap);
+      if (p.tpw > 16) assert(p.grid == 0);
+      else if (B >= 1) assert((int64_t)p.grid * p.tpw >= B && (int64_t)p.grid * p.tpw % 16 == 0 && (int64_t)p.grid * p.tpw < (int64_t)B + 16);
+      else assert(p.grid == 0);
+      (void)rnn_dw_ksplit(hostile_int(), hostile_int());
+    }
+    assert(n_rnn_ok > 1000 && n_rnn_bad > 1000);
+    {   // a plan never divides by what a layout did not produce
+      lde::RnnDims z{};
+      const RnnPlan p = rnn_launch_plan(z, std::numeric_limits<int>::max(), 0, 1, 1, false);
+      assert(p.form == RNN_FORM_GENERIC && p.tpw == 64 && p.block == 64 && p.grid == 0);
+      z.Hp = 4;
+      assert(rnn_launch_plan(z, std::numeric_limits<int>::max(), 0, 1, 1, false).grid == 134217728u);
+      z.Hp = std::numeric_limits<int>::max(); z.lds_w = z.vmax = z.rmax = z.hmax = z.nL = std::numeric_limits<int>::max();
+      (void)rnn_launch_plan(z, std::numeric_limits<int>::min(), 1, 1, 1, true);
+      (void)rnn_lds_bytes(z, RNN_FORM_PIPE, std::numeric_limits<int>::max());
+    }
+  }
   std::printf("host logic under ASan + UBSan: %d accepted, %d refused hostile descriptions; forward mappings as measured; "
               "pullback mappings, ring shapes and kernel dispatch checked; MLP family mappings as measured, reserve rows and solver dispatch checked\n", n_ok, n_bad);
   std::printf("dense chains: LDS bytes, tile picks, call layouts, tile narrowing and weight-gradient splits as measured; hostile sizes checked\n");
+  std::printf("recurrent stacks: weight counts, layouts, refusals, launch plans, groupability, k-split and kernel dispatch as in the launch code; "
+              "%d accepted, %d refused hostile descriptions\n", n_rnn_ok, n_rnn_bad);
   return 0;
 }

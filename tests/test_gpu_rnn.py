@@ -410,3 +410,122 @@ def test_training_forward_keeps_the_records_for_the_pullback(cell):
         dxb, dWb = back(x, torch.empty_like(x), torch.empty(m.num_weights, device=dev))
         assert torch.equal(dxa, dxb) and torch.equal(dWa, dWb)
 
+
+def _group_of_two():
+    """A default LSTM stack and a default RNN-relu stack (32 → 16 → 16) on the same frames, T = 3, B = 5 (one ragged staging tile), in
+    overwrite mode: what the two tests below share. handles() makes a fresh pair; plain(pair, dys) is lde_rnn_forward + lde_rnn_backward on
+    each handle, arrays pre-filled with 7."""
+    import ctypes as C
+    import torch
+    from latentdiffeq_amd import _lib as L
+    from tests.gpu_util import NativeRnn
+    sizes, T, B = (32, 16, 16), 3, 5
+    g = torch.Generator().manual_seed(21)
+    x = torch.randn(T, B, 32, generator=g).to("cuda")
+    dys = [(torch.randn(B, 16, generator=g) / B).to("cuda") for _ in range(2)]
+    s = L.raw_stream(0)
+    p = lambda t: C.c_void_p(t.data_ptr())
+
+    def handles():
+        pair = []
+        for cell, rev in ((O.CELL_LSTM, False), (O.CELL_RNN_RELU, True)):
+            nat = NativeRnn(cell, sizes, rev)
+            nat.set_weights(O.rnn_weights(cell, sizes, seed=13))
+            assert nat.lib.lde_rnn_set_accumulate(nat.h, 0) == 0
+            pair.append(nat)
+        return pair
+
+    def back(nat, dy):
+        dx, dW = torch.full_like(x, 7.0), torch.full((nat.nW,), 7.0, device="cuda")
+        assert nat.lib.lde_rnn_backward(nat.h, p(x), p(dy), T, B, p(dx), p(dW), s) == 0
+        torch.cuda.synchronize()
+        return dx, dW
+
+    def plain(pair, dys_):
+        out = []
+        for nat, dy in zip(pair, dys_):
+            y = torch.full((B, 16), 7.0, device="cuda")
+            assert nat.lib.lde_rnn_forward(nat.h, p(x), T, B, p(y), s) == 0
+            out.append((y,) + back(nat, dy))
+        return out
+
+    return dict(T=T, B=B, x=x, dys=dys, s=s, p=p, g=g, handles=handles, plain=plain, back=back)
+
+
+def test_extras_of_a_grouped_call_stay_with_that_call():
+    """What a grouped call carries beyond its arrays — the row strides of y and dy, the second source of the output gradient — belongs to
+    THAT call: on one pair of handles, after lde_rnn_group_forward_ld into a wider array (ldy = 40 > 16, train = 1), lde_rnn_group_backward_ld
+    (lddy = 40, a second gradient source) and a refused *_ld call (row stride 8 < 16), a plain lde_rnn_forward + lde_rnn_backward on each
+    handle gives the bits (y, dx, dW) a fresh handle gives. The *_ld results themselves equal the plain results on the gradient added
+    beforehand, bit for bit: rnn_dy adds exactly the two floats, one rounding on both sides. C ABI through ctypes."""
+    import ctypes as C
+    import torch
+    q = _group_of_two()
+    T, B, x, dys, s, p = q["T"], q["B"], q["x"], q["dys"], q["s"], q["p"]
+    dys2 = [(torch.randn(B, 16, generator=q["g"]) / B).to("cuda") for _ in range(2)]
+    ref = q["plain"](q["handles"](), dys)
+    presum = q["plain"](q["handles"](), [(a + b).contiguous() for a, b in zip(dys, dys2)])
+    pair = q["handles"]()
+    lib = pair[0].lib
+    arr = lambda ptrs: (C.c_void_p * 2)(*ptrs)
+    hs, xs, ld = arr([n.h.value for n in pair]), arr([x.data_ptr()] * 2), (C.c_int32 * 2)(40, 40)
+
+    def still_plain(after):
+        for i, (got, want) in enumerate(zip(q["plain"](pair, dys), ref)):
+            for a, b, what in zip(got, want, ("y", "dx", "dW")):
+                assert torch.equal(a, b), (after, i, what, float((a - b).abs().max()))
+
+    # (i) the outputs as column blocks 0:16 and 16:32 of a [B × 40] array; the sweep leaves its records (train = 1)
+    wide = torch.full((B, 40), 7.0, device="cuda")
+    assert lib.lde_rnn_group_forward_ld(2, hs, xs, T, B, arr([wide.data_ptr() + 64 * i for i in range(2)]), ld, 1, s) == 0
+    torch.cuda.synchronize()
+    for i in range(2):
+        assert torch.equal(wide[:, 16 * i:16 * i + 16], ref[i][0]), i
+    assert bool((wide[:, 32:] == 7.0).all())
+    # (ii) the output gradients as column blocks of two [B × 40] arrays, added where they are read; the pullback starts from the records
+    g1, g2 = torch.full((B, 40), 3.0, device="cuda"), torch.full((B, 40), 3.0, device="cuda")
+    for i in range(2):
+        g1[:, 16 * i:16 * i + 16] = dys[i]
+        g2[:, 16 * i:16 * i + 16] = dys2[i]
+    dxs = [torch.full_like(x, 7.0) for _ in pair]
+    dWs = [torch.full((n.nW,), 7.0, device="cuda") for n in pair]
+    assert lib.lde_rnn_group_backward_ld(2, hs, xs, arr([g1.data_ptr() + 64 * i for i in range(2)]), arr([g2.data_ptr() + 64 * i for i in range(2)]),
+                                         ld, T, B, arr([d.data_ptr() for d in dxs]), arr([d.data_ptr() for d in dWs]), s) == 0
+    torch.cuda.synchronize()
+    for i in range(2):
+        assert torch.equal(dxs[i], presum[i][1]) and torch.equal(dWs[i], presum[i][2]), i
+    still_plain("forward_ld + backward_ld")
+    # (iii) refused: a row stride below the output width, forward (with records asked for) and backward
+    ld8 = (C.c_int32 * 2)(40, 8)
+    assert lib.lde_rnn_group_forward_ld(2, hs, xs, T, B, arr([wide.data_ptr() + 64 * i for i in range(2)]), ld8, 1, s) == -1   # LDE_ERR_INVALID_ARG
+    assert b"row stride" in lib.lde_rnn_last_error(pair[1].h)
+    assert lib.lde_rnn_group_backward_ld(2, hs, xs, arr([g1.data_ptr() + 64 * i for i in range(2)]), arr([g2.data_ptr() + 64 * i for i in range(2)]),
+                                         ld8, T, B, arr([d.data_ptr() for d in dxs]), arr([d.data_ptr() for d in dWs]), s) == -1
+    still_plain("refused *_ld calls")
+    # … and once more with the strided training forward right before the plain pullback: its records are used, its extras are not
+    assert lib.lde_rnn_group_forward_ld(2, hs, xs, T, B, arr([wide.data_ptr() + 64 * i for i in range(2)]), ld, 1, s) == 0
+    for i, nat in enumerate(pair):
+        dx, dW = q["back"](nat, dys[i])
+        assert torch.equal(dx, ref[i][1]) and torch.equal(dW, ref[i][2]), i
+
+
+def test_a_refused_group_leaves_no_records_behind():
+    """lde_rnn_group_forward_train with xs[1] = NULL is refused (LDE_ERR_INVALID_ARG) after stack 0's sweep was taken down but before
+    anything was launched: no stack of the group may believe it holds the records of (x, T, B). lde_rnn_backward on stack 0 with that very
+    (x, T, B) then sweeps itself and equals, bit for bit, the result on a fresh handle that never saw a training forward."""
+    import ctypes as C
+    import torch
+    q = _group_of_two()
+    T, B, x, dys, s = q["T"], q["B"], q["x"], q["dys"], q["s"]
+    fresh = q["handles"]()
+    want = [q["back"](nat, dy) for nat, dy in zip(fresh, dys)]
+    pair = q["handles"]()
+    lib = pair[0].lib
+    hs = (C.c_void_p * 2)(*[n.h.value for n in pair])
+    ys = [torch.full((B, 16), 7.0, device="cuda") for _ in pair]
+    rc = lib.lde_rnn_group_forward_train(2, hs, (C.c_void_p * 2)(x.data_ptr(), None), T, B, (C.c_void_p * 2)(*[y.data_ptr() for y in ys]), s)
+    assert rc == -1   # LDE_ERR_INVALID_ARG
+    torch.cuda.synchronize()
+    for i, nat in enumerate(pair):
+        dx, dW = q["back"](nat, dys[i])
+        assert torch.equal(dx, want[i][0]) and torch.equal(dW, want[i][1]), i

@@ -2,7 +2,7 @@
 not available on this pool): (1) the oracle — everything the parity tests trust — driven at small, ragged, degenerate and failing shapes
 through every family of its entry points (oracle/asan_driver.c, f32 and f64 builds); (2) the C ABI's host-side logic — validation of a
 problem description, the weight count, the step-record layout arithmetic, the option block, grid checks, the analytic path's kernel
-choices, the MLP path's kernel families and the dense chains' tile / layout / split choices (csrc/lde_host.h, which lde_api.hip and the launch code are built from) — with 200 000 hostile descriptions (tests/host_logic_driver.cpp)."""
+choices, the MLP path's kernel families, the dense chains' tile / layout / split choices and the recurrent stacks' layout / launch plan (csrc/lde_host.h, which lde_api.hip and the launch code are built from) — with 200 000 hostile descriptions (tests/host_logic_driver.cpp)."""
 import os
 import shutil
 import subprocess
@@ -39,6 +39,7 @@ def test_c_abi_host_logic_under_asan_ubsan(tmp_path):
     assert "pullback mappings, ring shapes and kernel dispatch checked" in r.stdout
     assert "MLP family mappings as measured, reserve rows and solver dispatch checked" in r.stdout
     assert "dense chains: LDS bytes, tile picks, call layouts, tile narrowing and weight-gradient splits as measured; hostile sizes checked" in r.stdout
+    assert "recurrent stacks: weight counts, layouts, refusals, launch plans, groupability, k-split and kernel dispatch as in the launch code" in r.stdout
 
 
 def test_lde_api_is_built_from_the_checked_logic():
@@ -64,5 +65,13 @@ def test_lde_api_is_built_from_the_checked_logic():
         assert used in chain, used
     for gone in ("thread_local", "attr[", "< 192", "256 /"):
         assert gone not in chain, gone
+    assert "bool set_max_lds_(" not in chain   # (shared with the recurrent stacks: csrc/lde_mfma.h)
+    # the recurrent stacks: the layout, the kernel form and launch shape of a call and the weight count come from lde_host.h; the launch code
+    # keeps no threshold, no spelled-out default shape, no per-call state outside its arguments and no per-function attribute table
+    rnn = open(os.path.join(ROOT, "latentdiffeq.jl_amd", "csrc", "lde_rnn.hip")).read()
+    for used in ("lde_host::rnn_layout(", "lde_host::rnn_launch_plan(", "lde_host::rnn_num_weights("):
+        assert used in rnn, used
+    for gone in ("thread_local", "attr[", "io_ld", "io_dy2", "> 1024", "cdiv(512", "sizes[0] == 32"):
+        assert gone not in rnn, gone
     for fn in ("static int validate(", "static size_t rec_bytes(", "static lde::StepRec rec_view(", "static lde::KOpts make_opts("):
         assert fn not in src, fn
