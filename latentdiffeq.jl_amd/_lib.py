@@ -248,22 +248,21 @@ def set_async_weight_gradients(on: bool = True, device=None):
     call it after `loss.backward()` and before anything reads `.grad` (optimiser step, all-reduce, clipping). Opt-in."""
     global dw_stream
     import torch
-    lib = load()
     if on:
         if dw_stream is None:
             dw_stream = torch.cuda.Stream(device)
-        check(lib.lde_set_dw_stream(C.c_void_p(dw_stream.cuda_stream)), None, "lde_set_dw_stream")
+        call("lde_set_dw_stream", None, C.c_void_p(dw_stream.cuda_stream))
     else:
         if dw_stream is not None:
             join_weight_gradients()
-        check(lib.lde_set_dw_stream(None), None, "lde_set_dw_stream")
+        call("lde_set_dw_stream", None, None)
         dw_stream = None
 
 
 def join_weight_gradients():
     """lde_join_dw on the current stream (a device-side wait; the host does not block). No-op when the mode is off."""
     if dw_stream is not None:
-        check(load().lde_join_dw(raw_stream(dw_stream.device.index)), None, "lde_join_dw")
+        call("lde_join_dw", None, raw_stream(dw_stream.device.index))
 
 
 class AdamTensor(C.Structure):
@@ -285,7 +284,6 @@ def refresh_weights(modules, stream=None):
     mods = [m for m in modules if hasattr(m, "_native") and hasattr(m, "theta") and m.theta.is_cuda]
     if not mods:
         return 0
-    lib = load()
     n = len(mods)
     kinds, handles, ptrs, keep = (C.c_int32 * n)(), (C.c_void_p * n)(), (C.c_void_p * n)(), []
     for i, m in enumerate(mods):
@@ -296,8 +294,7 @@ def refresh_weights(modules, stream=None):
         kinds[i] = MODULE_RNN if getattr(m, "_is_recurrent", False) else MODULE_CHAIN
         handles[i] = m._native().value
         ptrs[i] = W.data_ptr()
-    check(lib.lde_refresh_weights(n, kinds, handles, ptrs, stream if stream is not None else raw_stream(mods[0].theta.device.index)),
-          None, "lde_refresh_weights")
+    call("lde_refresh_weights", None, n, kinds, handles, ptrs, stream if stream is not None else raw_stream(mods[0].theta.device.index))
     for m, W in zip(mods, keep):
         m._wkey = weights_key(m.theta) if W.data_ptr() == m.theta.data_ptr() else None
     return n
@@ -312,3 +309,116 @@ def check(rc: int, handle=None, what: str = "", chain: bool = False, rnn: bool =
         if detail:
             msg += ": " + detail.decode()
     raise LdeError(f"{what} failed: {msg}")
+
+
+# ---- the call layer: what api.py / chain.py / recurrent.py / loss.py reach the library through ------------------
+
+def ptr(t, byte_offset: int = 0) -> C.c_void_p:
+    """The data of tensor `t` (`byte_offset` bytes in) as a pointer argument; NULL for None."""
+    return C.c_void_p(t.data_ptr() + byte_offset) if t is not None else C.c_void_p()
+
+
+def ptr_array(items):
+    """A void*[] argument in the order given, from tensors, None (NULL) or raw integers (handle values, offset pointers)."""
+    return (C.c_void_p * len(items))(*[x.data_ptr() if hasattr(x, "data_ptr") else x for x in items])
+
+
+def call(name: str, handle, *args, err=None):
+    """`name(handle, *args)` on the loaded library (`name(*args)` when handle is None); a status other than LDE_OK raises LdeError with
+    the function's name and the text of lde_chain_last_error / lde_rnn_last_error / lde_last_error, chosen by the name's prefix. `err`:
+    the handle to ask for that text when the entry point takes none first (the group calls)."""
+    fn = getattr(_lib or load(), name)
+    rc = fn(*args) if handle is None else fn(handle, *args)
+    if rc != 0:
+        _fail(rc, handle if handle is not None else err, name)
+
+
+def _fail(rc: int, handle, name: str):
+    check(rc, handle, name, chain=name.startswith("lde_chain_"), rnn=name.startswith("lde_rnn_"))
+
+
+def need_gpu(on_gpu: bool, what: str):
+    if not on_gpu:
+        raise LdeError(f"{what} runs on the GPU only (no CPU fallback): it needs CUDA/HIP tensors")
+
+
+class NativeModule:
+    """Mixin of the torch modules that own a native handle (chain.Chain, recurrent.Recurrent). The class names its entry points
+    (`_create`, `_destroy`), builds its descriptor in `_desc()` and finishes a new handle in `_created(h)`."""
+
+    _create = _destroy = None
+    _handle = None
+    _lib = None
+    _wkey = None               # set by refresh_weights: the parameter value the handle already holds
+    _is_recurrent = False
+
+    def _desc(self):
+        raise NotImplementedError
+
+    def _created(self, h):
+        pass
+
+    def _native(self):
+        if self._handle is None:
+            self._lib = load()
+            d, h = self._desc(), C.c_void_p()
+            rc = getattr(self._lib, self._create)(C.byref(d), C.byref(h))
+            if rc != 0:
+                try:
+                    _fail(rc, h if h else None, self._create)
+                finally:
+                    if h:
+                        getattr(self._lib, self._destroy)(h)
+            self._created(h)
+            self._handle = h
+        return self._handle
+
+    def __del__(self):
+        try:
+            if self._handle is not None and self._lib is not None:
+                getattr(self._lib, self._destroy)(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+
+def hand_over_weights(m, W, stream, side_stream=None):
+    """The handle of module `m`, holding the value of its flat parameter W: uploaded on `stream` unless refresh_weights() handed this
+    value over already (`m._wkey`). `side_stream`: the torch stream behind `stream` when it is not the current one."""
+    h = m._native()
+    if m._wkey != weights_key(W):
+        Wc = W.detach().contiguous().float()
+        call("lde_rnn_set_weights_device" if m._is_recurrent else "lde_chain_set_weights_device", h, ptr(Wc), Wc.numel(), stream)
+        if side_stream is not None:
+            Wc.record_stream(side_stream)
+        m._wkey = None
+    return h
+
+
+def new_weight_gradient(m, device, also_stream=None):
+    """A fresh buffer for module `m`'s weight gradient (written, not accumulated: set_accumulate(0)), recorded on the weight-gradient
+    stream when set_async_weight_gradients is on, and on `also_stream` when the pullback runs on a side stream."""
+    import torch
+    dW = torch.empty((m.num_weights,), device=device, dtype=torch.float32)
+    if also_stream is not None:
+        dW.record_stream(also_stream)
+    if dw_stream is not None:
+        dW.record_stream(dw_stream)
+    return dW
+
+
+def sum_gradients(dxs):
+    """Σ of the input gradients of branches that read the same input, in order (None when there are none)."""
+    if not dxs:
+        return None
+    dx = dxs[0]
+    for d in dxs[1:]:
+        dx = dx + d
+    return dx
+
+
+def loss_scratch(device, floats: int = LOSS_SCRATCH_FLOATS):
+    """(ws, &ws[0], &ws[1]): the result of a loss reduction followed by `floats` of scratch, and the two pointers the kernels take."""
+    import torch
+    ws = torch.empty(floats + 1, device=device, dtype=torch.float32)
+    return ws, ptr(ws), ptr(ws, 4)

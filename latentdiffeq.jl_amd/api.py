@@ -155,8 +155,7 @@ class _Handle:
 
     def stats(self, which: int = 0) -> dict:
         s = L.Stats()
-        stream = torch.cuda.current_stream().cuda_stream
-        L.check(self.lib.lde_get_stats(self.ptr, which, C.byref(s), C.c_void_p(stream)), self.ptr, "lde_get_stats")
+        L.call("lde_get_stats", self.ptr, which, C.byref(s), C.c_void_p(torch.cuda.current_stream().cuda_stream))
         return dict(nfe=s.nfe, naccept=s.naccept, nreject=s.nreject, nfailed=s.nfailed, max_steps=s.max_steps)
 
 
@@ -275,7 +274,7 @@ class SPendulum(_PhysicsDiffEq):
 
 def _set_noise(handle: _Handle, nz):
     seed, offset, first, epoch = nz
-    L.check(handle.lib.lde_set_noise(handle.ptr, seed & (2**64 - 1), offset & (2**64 - 1), first, _ptr(epoch)), handle.ptr, "lde_set_noise")
+    L.call("lde_set_noise", handle.ptr, seed & (2**64 - 1), offset & (2**64 - 1), first, L.ptr(epoch))
 
 
 class NeuralODE:
@@ -343,8 +342,6 @@ class NODE:
     def set_global_sum(self, fn, global_batch: int):
         """lde_set_global_sum_hook: `fn(vals: numpy float64 array of 1 or 2 entries)` replaces the entries in place by their sums
         over all ranks (a HOST collective — the device is busy with the solve). `fn=None` clears the hook."""
-        import numpy as np
-        lib = L.load()
         h = self._native()
         if fn is None:
             cb = L.SUM_HOOK(0)
@@ -356,22 +353,19 @@ class NODE:
                 except Exception:      # noqa: BLE001  (an exception must not unwind through the C frame)
                     return 1
             cb = L.SUM_HOOK(_cb)
-        L.check(lib.lde_set_global_sum_hook(h.ptr, cb, None, int(global_batch)), h.ptr, "lde_set_global_sum_hook")
+        L.call("lde_set_global_sum_hook", h.ptr, cb, None, int(global_batch))
         self._sum_cb = cb              # keep the trampoline alive as long as the handle uses it
 
     def set_global_sum_peers(self, rank: int, nranks: int, mailboxes, global_batch: int):
         """lde_set_global_sum_peers: the same exchange device to device — `mailboxes` = every rank's mailbox as mapped on this device, in rank
         order (`dist.GlobalSumMailboxes(group).pointers()`; integers or tensors). The calls stay asynchronous. nranks = 0 switches it off."""
-        import ctypes as C
-        lib = L.load()
         h = self._native()
         if nranks == 0:
-            L.check(lib.lde_set_global_sum_peers(h.ptr, 0, 0, None, 0), h.ptr, "lde_set_global_sum_peers")
+            L.call("lde_set_global_sum_peers", h.ptr, 0, 0, None, 0)
             self._mailboxes = None
             return
-        ptrs = [m.data_ptr() if hasattr(m, "data_ptr") else int(m) for m in mailboxes]
-        arr = (C.c_void_p * len(ptrs))(*ptrs)
-        L.check(lib.lde_set_global_sum_peers(h.ptr, int(rank), int(nranks), arr, int(global_batch)), h.ptr, "lde_set_global_sum_peers")
+        L.call("lde_set_global_sum_peers", h.ptr, int(rank), int(nranks),
+               L.ptr_array([m if hasattr(m, "data_ptr") else int(m) for m in mailboxes]), int(global_batch))
         self._mailboxes = mailboxes       # kept alive as long as the handle uses them
 
     def flat_weights(self) -> torch.Tensor:
@@ -434,18 +428,13 @@ def _ts_array(t) -> np.ndarray:
     return ts
 
 
-def _ptr(x: Optional[torch.Tensor]):
-    return C.c_void_p(x.data_ptr()) if x is not None else C.c_void_p()
-
-
 class _SolveFn(torch.autograd.Function):
     """ẑ = solve(z0, θ, W); backward = lde_adjoint. Buffers are batch-major: z0 (B,D), θ (B,P), ẑ (T,B,D')."""
 
     @staticmethod
     def forward(ctx, handle: _Handle, ts: np.ndarray, z0: torch.Tensor, theta: Optional[torch.Tensor],
                 W: Optional[torch.Tensor], noise=None):
-        if not z0.is_cuda:
-            raise L.LdeError("diffeq_layer needs CUDA/HIP tensors: the solve runs on the GPU only (no CPU fallback)")
+        L.need_gpu(z0.is_cuda, "diffeq_layer")
         lib = handle.lib
         B, D = z0.shape
         T = int(ts.shape[0])
@@ -453,8 +442,7 @@ class _SolveFn(torch.autograd.Function):
         stream = L.raw_stream(z0.device.index)
         if W is not None:
             Wc = W.detach().contiguous().float()
-            L.check(lib.lde_set_weights_device(handle.ptr, _ptr(Wc), Wc.numel(), stream), handle.ptr,
-                    "lde_set_weights_device")
+            L.call("lde_set_weights_device", handle.ptr, L.ptr(Wc), Wc.numel(), stream)
         z_out = torch.empty((T, B, Dp), device=z0.device, dtype=torch.float32)
         retcode = torch.empty((B,), device=z0.device, dtype=torch.int32)
         tsp = ts.ctypes.data_as(C.POINTER(C.c_double))
@@ -467,13 +455,12 @@ class _SolveFn(torch.autograd.Function):
             # before their pullbacks)
             nbytes = int(lib.lde_step_record_bytes(handle.ptr, B, T))
             ctx.rec = torch.empty((nbytes,), device=z0.device, dtype=torch.uint8)
-            L.check(lib.lde_set_step_record(handle.ptr, _ptr(ctx.rec), nbytes), handle.ptr, "lde_set_step_record")
+            L.call("lde_set_step_record", handle.ptr, L.ptr(ctx.rec), nbytes)
         try:
-            L.check(lib.lde_forward(handle.ptr, _ptr(z0), _ptr(theta), tsp, T, B, _ptr(z_out), _ptr(retcode), stream),
-                    handle.ptr, "lde_forward")
+            L.call("lde_forward", handle.ptr, L.ptr(z0), L.ptr(theta), tsp, T, B, L.ptr(z_out), L.ptr(retcode), stream)
         finally:
             if ctx.rec is not None:       # the handle must not keep a pointer into a block this graph node owns (and torch recycles)
-                lib.lde_set_step_record(handle.ptr, C.c_void_p(), 0)
+                lib.lde_set_step_record(handle.ptr, None, 0)
         ctx.handle, ctx.ts = handle, ts
         ctx.has_theta, ctx.has_W = theta is not None, W is not None
         ctx.save_for_backward(z_out, theta if theta is not None else z0.new_empty(0))
@@ -506,13 +493,12 @@ class _SolveFn(torch.autograd.Function):
         if ctx.noise is not None:
             _set_noise(handle, ctx.noise)
         if rec is not None:
-            L.check(lib.lde_set_step_record(handle.ptr, _ptr(rec), rec.numel()), handle.ptr, "lde_set_step_record")
+            L.call("lde_set_step_record", handle.ptr, L.ptr(rec), rec.numel())
         try:
-            L.check(lib.lde_adjoint(handle.ptr, _ptr(z_out), _ptr(theta), tsp, T, B, _ptr(dz_out), _ptr(dz0), _ptr(dth),
-                                    _ptr(dW), stream), handle.ptr, "lde_adjoint")
+            L.call("lde_adjoint", handle.ptr, L.ptr(z_out), L.ptr(theta), tsp, T, B, L.ptr(dz_out), L.ptr(dz0), L.ptr(dth), L.ptr(dW), stream)
         finally:
             if rec is not None:
-                lib.lde_set_step_record(handle.ptr, C.c_void_p(), 0)
+                lib.lde_set_step_record(handle.ptr, None, 0)
         return None, None, dz0, dth, dW, None
 
     @staticmethod
@@ -525,8 +511,7 @@ class _SolveFn(torch.autograd.Function):
         lib = handle.lib
         T, B, Dp = z_out.shape
         nmax, cap = C.c_int32(0), C.c_int32(0)
-        L.check(lib.lde_step_record_status(handle.ptr, _ptr(rec), B, T, C.byref(nmax), C.byref(cap), stream), handle.ptr,
-                "lde_step_record_status")
+        L.call("lde_step_record_status", handle.ptr, L.ptr(rec), B, T, C.byref(nmax), C.byref(cap), stream)
         have = (rec.numel(), int(lib.lde_step_record_bytes(handle.ptr, B, T)))
         if nmax.value <= cap.value and have[0] >= have[1]:
             return rec
@@ -538,18 +523,17 @@ class _SolveFn(torch.autograd.Function):
             want = min(int(handle.desc.maxiters), max(nmax.value + 8, 2 * cap.value))
             if want <= cap.value:
                 raise L.LdeError(f"the solve accepted {nmax.value} steps, more than maxiters = {handle.desc.maxiters} lets a step record hold")
-            L.check(lib.lde_set_option(handle.ptr, b"record_capacity", float(want)), handle.ptr, "lde_set_option")
+            L.call("lde_set_option", handle.ptr, b"record_capacity", float(want))
         nbytes = int(lib.lde_step_record_bytes(handle.ptr, B, T))
         rec2 = torch.empty((nbytes,), device=z_out.device, dtype=torch.uint8)
         z0 = z_out[0, :, :handle.desc.state_dim].contiguous()    # ẑ(t₁) is ẑ₀ itself; the augmented rows start at zero
         z_tmp = torch.empty_like(z_out)
         tsp = ts.ctypes.data_as(C.POINTER(C.c_double))
-        L.check(lib.lde_set_step_record(handle.ptr, _ptr(rec2), nbytes), handle.ptr, "lde_set_step_record")
+        L.call("lde_set_step_record", handle.ptr, L.ptr(rec2), nbytes)
         try:
-            L.check(lib.lde_forward(handle.ptr, _ptr(z0), _ptr(theta), tsp, T, B, _ptr(z_tmp), C.c_void_p(), stream), handle.ptr,
-                    "lde_forward")
+            L.call("lde_forward", handle.ptr, L.ptr(z0), L.ptr(theta), tsp, T, B, L.ptr(z_tmp), None, stream)
         finally:
-            lib.lde_set_step_record(handle.ptr, C.c_void_p(), 0)
+            lib.lde_set_step_record(handle.ptr, None, 0)
         return rec2
 
 

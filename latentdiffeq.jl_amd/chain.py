@@ -17,7 +17,6 @@ views of batch-major torch buffers, exactly like `diffeq_layer` (api.py).
 from __future__ import annotations
 
 import ctypes as C
-import os
 import math
 from typing import Optional, Sequence
 
@@ -80,17 +79,9 @@ class _ChainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, chain: "Chain", x: torch.Tensor, W: torch.Tensor):
-        if not x.is_cuda:
-            raise L.LdeError("Chain needs CUDA/HIP tensors: it runs on the GPU only (no CPU fallback)")
-        h = chain._native()
-        lib = chain._lib
+        L.need_gpu(x.is_cuda, "Chain")
         stream = L.raw_stream(x.device.index)
-        key = L.weights_key(W)
-        if chain._wkey != key:          # not handed over by refresh_weights() since the parameter last changed
-            Wc = W.detach().contiguous().float()
-            L.check(lib.lde_chain_set_weights_device(h, C.c_void_p(Wc.data_ptr()), Wc.numel(), stream), h,
-                    "lde_chain_set_weights_device", chain=True)
-            chain._wkey = None
+        h = L.hand_over_weights(chain, W, stream)
         N = x.shape[0]
         y = torch.empty((N, chain.sizes[-1]), device=x.device, dtype=torch.float32)
         # (inside Function.forward grad mode is always off — torch.is_grad_enabled() is False here whether or not a pullback will
@@ -99,12 +90,10 @@ class _ChainFn(torch.autograd.Function):
         train = bool(ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
         saved = None
         if train:
-            saved = torch.empty((int(lib.lde_chain_saved_floats(h, N)),), device=x.device, dtype=torch.float32)
-            L.check(lib.lde_chain_forward_save(h, C.c_void_p(x.data_ptr()), N, C.c_void_p(y.data_ptr()),
-                                               C.c_void_p(saved.data_ptr()), stream), h, "lde_chain_forward_save", chain=True)
+            saved = chain._new_saved(N, x.device)
+            L.call("lde_chain_forward_save", h, L.ptr(x), N, L.ptr(y), L.ptr(saved), stream)
         else:
-            L.check(lib.lde_chain_forward(h, C.c_void_p(x.data_ptr()), N, C.c_void_p(y.data_ptr()), stream), h,
-                    "lde_chain_forward", chain=True)
+            L.call("lde_chain_forward", h, L.ptr(x), N, L.ptr(y), stream)
         ctx.chain = chain
         ctx.need_dx = x.requires_grad
         ctx.has_saved = saved is not None
@@ -115,22 +104,15 @@ class _ChainFn(torch.autograd.Function):
     def backward(ctx, dy):
         chain = ctx.chain
         h = chain._native()
-        lib = chain._lib
         x, y, saved = ctx.saved_tensors
         dy = dy.contiguous().float()
         stream = L.raw_stream(x.device.index)
         dx = torch.empty_like(x) if ctx.need_dx else None
-        dW = torch.empty((chain.num_weights,), device=x.device, dtype=torch.float32)     # written, not accumulated (set_accumulate(0))
-        if L.dw_stream is not None:
-            dW.record_stream(L.dw_stream)          # written on the weight-gradient stream (set_async_weight_gradients)
-        pdx = C.c_void_p(dx.data_ptr()) if dx is not None else C.c_void_p()
+        dW = L.new_weight_gradient(chain, x.device)
         if ctx.has_saved:
-            L.check(lib.lde_chain_backward_saved(h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(dy.data_ptr()),
-                                                 C.c_void_p(saved.data_ptr()), x.shape[0], pdx, C.c_void_p(dW.data_ptr()), stream),
-                    h, "lde_chain_backward_saved", chain=True)
+            L.call("lde_chain_backward_saved", h, L.ptr(x), L.ptr(y), L.ptr(dy), L.ptr(saved), x.shape[0], L.ptr(dx), L.ptr(dW), stream)
         else:
-            L.check(lib.lde_chain_backward(h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(dy.data_ptr()),
-                                           x.shape[0], pdx, C.c_void_p(dW.data_ptr()), stream), h, "lde_chain_backward", chain=True)
+            L.call("lde_chain_backward", h, L.ptr(x), L.ptr(y), L.ptr(dy), x.shape[0], L.ptr(dx), L.ptr(dW), stream)
         return None, dx, dW
 
 
@@ -144,56 +126,33 @@ class _ChainMseFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, chain: "Chain", x, W, target, scale: float, base, want_y: bool = True):
-        if not x.is_cuda:
-            raise L.LdeError("Chain needs CUDA/HIP tensors: it runs on the GPU only (no CPU fallback)")
-        h = chain._native()
-        lib = chain._lib
+        L.need_gpu(x.is_cuda, "Chain")
         stream = L.raw_stream(x.device.index)
-        if chain._wkey != L.weights_key(W):
-            Wc = W.detach().contiguous().float()
-            L.check(lib.lde_chain_set_weights_device(h, C.c_void_p(Wc.data_ptr()), Wc.numel(), stream), h, "lde_chain_set_weights_device", chain=True)
-            chain._wkey = None
+        h = L.hand_over_weights(chain, W, stream)
         N = x.shape[0]
         train = bool(ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        saved = torch.empty((int(lib.lde_chain_saved_floats(h, N)),), device=x.device, dtype=torch.float32) if train else None
-        ctx.delta = False
-        if _RECON_MSE_FWD and train and chain.dtype == "bf16" and chain.sizes[-1] % 8 == 0:
-            # bf16 chains: the forward launch leaves δ_L′ for the pullback (lde_chain_forward_save_mse_delta) — the pullback reads neither x̂
-            # nor the frames, and x̂ itself is stored only when the caller wants it
-            y = torch.empty((N, chain.sizes[-1]), device=x.device, dtype=torch.float32) if want_y else None
-            ws = torch.empty(int(lib.lde_chain_mse_scratch_floats(h, N)) + 1, device=x.device, dtype=torch.float32)
-            L.check(lib.lde_chain_forward_save_mse_delta(h, C.c_void_p(x.data_ptr()), N, C.c_void_p(y.data_ptr()) if want_y else C.c_void_p(),
-                                                         C.c_void_p(saved.data_ptr()), C.c_void_p(target.data_ptr()), scale,
-                                                         C.c_void_p(base.data_ptr()) if base is not None else C.c_void_p(), C.c_void_p(ws.data_ptr()),
-                                                         C.c_void_p(ws.data_ptr() + 4), stream), h, "lde_chain_forward_save_mse_delta", chain=True)
-            ctx.chain, ctx.scale, ctx.has_base, ctx.need_dx, ctx.has_saved, ctx.delta = chain, scale, base is not None, x.requires_grad, True, True
-            ctx.save_for_backward(x, y if want_y else x.new_empty(0), saved, target)
-            ctx.set_materialize_grads(False)
-            return ws[0], (y if want_y else x.new_empty(0))
-        y = torch.empty((N, chain.sizes[-1]), device=x.device, dtype=torch.float32)
-        if _RECON_MSE_FWD:      # the loss value from the forward launch itself: squares summed in the last layer's epilogue
-            ws = torch.empty(int(lib.lde_chain_mse_scratch_floats(h, N)) + 1, device=x.device, dtype=torch.float32)     # [0]: the result, then tile sums
-            L.check(lib.lde_chain_forward_save_mse(h, C.c_void_p(x.data_ptr()), N, C.c_void_p(y.data_ptr()),
-                                                   C.c_void_p(saved.data_ptr()) if train else C.c_void_p(), C.c_void_p(target.data_ptr()), scale,
-                                                   C.c_void_p(base.data_ptr()) if base is not None else C.c_void_p(), C.c_void_p(ws.data_ptr()),
-                                                   C.c_void_p(ws.data_ptr() + 4), stream), h, "lde_chain_forward_save_mse", chain=True)
-            ctx.chain, ctx.scale, ctx.has_base, ctx.need_dx, ctx.has_saved = chain, scale, base is not None, x.requires_grad, train
-            ctx.save_for_backward(x, y, saved if train else x.new_empty(0), target)
-            ctx.set_materialize_grads(False)
-            return ws[0], y
-        if train:
-            L.check(lib.lde_chain_forward_save(h, C.c_void_p(x.data_ptr()), N, C.c_void_p(y.data_ptr()), C.c_void_p(saved.data_ptr()), stream),
-                    h, "lde_chain_forward_save", chain=True)
-        else:
-            L.check(lib.lde_chain_forward(h, C.c_void_p(x.data_ptr()), N, C.c_void_p(y.data_ptr()), stream), h, "lde_chain_forward", chain=True)
-        ws = torch.empty(L.LOSS_SCRATCH_FLOATS + 1, device=x.device, dtype=torch.float32)
-        if base is not None:
-            L.check(lib.lde_mse_forward_add(C.c_void_p(target.data_ptr()), C.c_void_p(y.data_ptr()), y.numel(), scale, C.c_void_p(base.data_ptr()),
-                                            C.c_void_p(ws.data_ptr()), C.c_void_p(ws.data_ptr() + 4), stream), None, "lde_mse_forward_add")
-        else:
-            L.check(lib.lde_mse_forward(C.c_void_p(target.data_ptr()), C.c_void_p(y.data_ptr()), y.numel(), scale, C.c_void_p(ws.data_ptr()),
-                                        C.c_void_p(ws.data_ptr() + 4), stream), None, "lde_mse_forward")
+        saved = chain._new_saved(N, x.device) if train else None
         ctx.chain, ctx.scale, ctx.has_base, ctx.need_dx, ctx.has_saved = chain, scale, base is not None, x.requires_grad, train
+        # bf16 chains: the forward launch leaves δ_L′ for the pullback (lde_chain_forward_save_mse_delta) — the pullback reads neither x̂
+        # nor the frames, and x̂ itself is stored only when the caller wants it
+        ctx.delta = bool(_RECON_MSE_FWD and train and chain.dtype == "bf16" and chain.sizes[-1] % 8 == 0)
+        y = torch.empty((N, chain.sizes[-1]), device=x.device, dtype=torch.float32) if want_y or not ctx.delta else None
+        if _RECON_MSE_FWD:      # the loss value from the forward launch itself: squares summed in the last layer's epilogue
+            ws, p_out, p_tiles = L.loss_scratch(x.device, int(chain._lib.lde_chain_mse_scratch_floats(h, N)))     # [0]: the result, then tile sums
+            L.call("lde_chain_forward_save_mse_delta" if ctx.delta else "lde_chain_forward_save_mse", h, L.ptr(x), N, L.ptr(y), L.ptr(saved),
+                   L.ptr(target), scale, L.ptr(base), p_out, p_tiles, stream)
+        else:
+            if train:
+                L.call("lde_chain_forward_save", h, L.ptr(x), N, L.ptr(y), L.ptr(saved), stream)
+            else:
+                L.call("lde_chain_forward", h, L.ptr(x), N, L.ptr(y), stream)
+            ws, p_out, p_tiles = L.loss_scratch(x.device)
+            if base is not None:
+                L.call("lde_mse_forward_add", None, L.ptr(target), L.ptr(y), y.numel(), scale, L.ptr(base), p_out, p_tiles, stream)
+            else:
+                L.call("lde_mse_forward", None, L.ptr(target), L.ptr(y), y.numel(), scale, p_out, p_tiles, stream)
+        if y is None:
+            y = x.new_empty(0)
         ctx.save_for_backward(x, y, saved if train else x.new_empty(0), target)
         ctx.set_materialize_grads(False)
         return ws[0], y
@@ -202,16 +161,12 @@ class _ChainMseFn(torch.autograd.Function):
     def backward(ctx, g, dy):
         chain = ctx.chain
         h = chain._native()
-        lib = chain._lib
         x, y, saved, target = ctx.saved_tensors
         stream = L.raw_stream(x.device.index)
         N = x.shape[0]
         dx = torch.empty_like(x) if ctx.need_dx else None
-        dW = torch.empty((chain.num_weights,), device=x.device, dtype=torch.float32)
-        if L.dw_stream is not None:
-            dW.record_stream(L.dw_stream)
-        pdx = C.c_void_p(dx.data_ptr()) if dx is not None else C.c_void_p()
-        psv = C.c_void_p(saved.data_ptr()) if ctx.has_saved else C.c_void_p()
+        dW = L.new_weight_gradient(chain, x.device)
+        psv = L.ptr(saved if ctx.has_saved else None)
         if dy is not None:
             dy = dy.contiguous().float()
         if g is None:          # only y was used downstream: the plain pullback
@@ -219,28 +174,23 @@ class _ChainMseFn(torch.autograd.Function):
                 raise L.LdeError("decode_loss(want_x_hat=False): x̂ was not kept, so it cannot carry a cotangent of its own")
             if dy is None:
                 dy = torch.zeros_like(y)
-            fn = lib.lde_chain_backward_saved if ctx.has_saved else None
-            if fn is not None:
-                L.check(fn(h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(dy.data_ptr()), psv, N, pdx, C.c_void_p(dW.data_ptr()), stream),
-                        h, "lde_chain_backward_saved", chain=True)
+            if ctx.has_saved:
+                L.call("lde_chain_backward_saved", h, L.ptr(x), L.ptr(y), L.ptr(dy), psv, N, L.ptr(dx), L.ptr(dW), stream)
             else:
-                L.check(lib.lde_chain_backward(h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(dy.data_ptr()), N, pdx,
-                                               C.c_void_p(dW.data_ptr()), stream), h, "lde_chain_backward", chain=True)
+                L.call("lde_chain_backward", h, L.ptr(x), L.ptr(y), L.ptr(dy), N, L.ptr(dx), L.ptr(dW), stream)
             return None, dx, dW, None, None, None, None
         g = g.contiguous().float()
         # δ_L′ staged in the chain's workspace by THIS node's forward (lde_chain_delta_is_staged: another forward of the same decoder before this
         # pullback re-stages it — then the two-pass pullback below runs from x̂ and the frames instead): no pass over x̂ / the frames; g
         # multiplies dx and dW at the end
-        if ctx.delta and dy is None and lib.lde_chain_delta_is_staged(h, psv, N):
-            L.check(lib.lde_chain_backward_saved_delta(h, C.c_void_p(x.data_ptr()), C.c_void_p(g.data_ptr()), psv, N, pdx, C.c_void_p(dW.data_ptr()), stream),
-                    h, "lde_chain_backward_saved_delta", chain=True)
+        if ctx.delta and dy is None and chain._lib.lde_chain_delta_is_staged(h, psv, N):
+            L.call("lde_chain_backward_saved_delta", h, L.ptr(x), L.ptr(g), psv, N, L.ptr(dx), L.ptr(dW), stream)
             return None, dx, dW, None, None, (g if ctx.has_base else None), None
         if y.numel() == 0:
             raise L.LdeError("decode_loss(want_x_hat=False): x̂ was not kept — it cannot carry a cotangent of its own, and another forward of this "
                              "decoder has re-staged the loss's δ since (keep x̂, or run each forward's backward before the next forward)")
-        L.check(lib.lde_chain_backward_saved_mse(h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(target.data_ptr()),
-                                                 C.c_void_p(g.data_ptr()), ctx.scale, C.c_void_p(dy.data_ptr()) if dy is not None else C.c_void_p(),
-                                                 psv, N, pdx, C.c_void_p(dW.data_ptr()), stream), h, "lde_chain_backward_saved_mse", chain=True)
+        L.call("lde_chain_backward_saved_mse", h, L.ptr(x), L.ptr(y), L.ptr(target), L.ptr(g), ctx.scale, L.ptr(dy), psv, N, L.ptr(dx), L.ptr(dW),
+               stream)
         return None, dx, dW, None, None, (g if ctx.has_base else None), None
 
 
@@ -255,31 +205,16 @@ class _ChainGroupFn(torch.autograd.Function):
     def forward(ctx, chains, *xw):
         n = len(chains)
         xs, Ws = xw[:n], xw[n:]
-        if not all(x.is_cuda for x in xs):
-            raise L.LdeError("Chain needs CUDA/HIP tensors: it runs on the GPU only (no CPU fallback)")
-        lib = chains[0]._lib if chains[0]._handle is not None else None
+        L.need_gpu(all(x.is_cuda for x in xs), "Chain")
         stream = L.raw_stream(xs[0].device.index)
-        hs = []
-        for c, W in zip(chains, Ws):
-            h = c._native()
-            lib = c._lib
-            key = L.weights_key(W)
-            if c._wkey != key:
-                Wc = W.detach().contiguous().float()
-                L.check(lib.lde_chain_set_weights_device(h, C.c_void_p(Wc.data_ptr()), Wc.numel(), stream), h,
-                        "lde_chain_set_weights_device", chain=True)
-                c._wkey = None
-            hs.append(h)
+        hs = [L.hand_over_weights(c, W, stream) for c, W in zip(chains, Ws)]
         ys = [torch.empty((x.shape[0], c.sizes[-1]), device=x.device, dtype=torch.float32) for c, x in zip(chains, xs)]
         train = any(ctx.needs_input_grad[1:])
-        saveds = [torch.empty((int(lib.lde_chain_saved_floats(h, x.shape[0])),), device=x.device, dtype=torch.float32) for h, x in zip(hs, xs)] \
-            if train else None
-        arr = lambda ptrs: (C.c_void_p * n)(*ptrs)
-        ctx.c_handles = arr([h.value for h in hs])
+        saveds = [c._new_saved(x.shape[0], x.device) for c, x in zip(chains, xs)] if train else None
+        ctx.c_handles = L.ptr_array([h.value for h in hs])
         ctx.c_Ns = (C.c_int64 * n)(*[x.shape[0] for x in xs])
-        rc = lib.lde_chain_group_forward_save(n, ctx.c_handles, arr([x.data_ptr() for x in xs]), ctx.c_Ns, arr([y.data_ptr() for y in ys]),
-                                              arr([t.data_ptr() for t in saveds]) if train else None, stream)
-        L.check(rc, hs[0], "lde_chain_group_forward_save", chain=True)
+        L.call("lde_chain_group_forward_save", None, n, ctx.c_handles, L.ptr_array(xs), ctx.c_Ns, L.ptr_array(ys),
+               L.ptr_array(saveds) if train else None, stream, err=hs[0])
         ctx.chains, ctx.n, ctx.train = chains, n, train
         ctx.need_dx = [bool(g) for g in ctx.needs_input_grad[1:1 + n]]
         ctx.save_for_backward(*xs, *ys, *(saveds if train else []))
@@ -290,20 +225,12 @@ class _ChainGroupFn(torch.autograd.Function):
         chains, n = ctx.chains, ctx.n
         t = ctx.saved_tensors
         xs, ys, saveds = t[:n], t[n:2 * n], (t[2 * n:] if ctx.train else None)
-        lib = chains[0]._lib
         stream = L.raw_stream(xs[0].device.index)
         dys = [dy.contiguous().float() for dy in dys]
         dxs = [torch.empty_like(x) if need else None for x, need in zip(xs, ctx.need_dx)]
-        dWs = [torch.empty((c.num_weights,), device=x.device, dtype=torch.float32) for c, x in zip(chains, xs)]   # written, not accumulated
-        if L.dw_stream is not None:
-            for dW in dWs:
-                dW.record_stream(L.dw_stream)
-        arr = lambda ptrs: (C.c_void_p * n)(*ptrs)
-        rc = lib.lde_chain_group_backward_saved(n, ctx.c_handles, arr([x.data_ptr() for x in xs]), arr([y.data_ptr() for y in ys]),
-                                                arr([d.data_ptr() for d in dys]), arr([s_.data_ptr() for s_ in saveds]) if saveds is not None else None,
-                                                ctx.c_Ns, arr([d.data_ptr() if d is not None else None for d in dxs]),
-                                                arr([d.data_ptr() for d in dWs]), stream)
-        L.check(rc, chains[0]._native(), "lde_chain_group_backward_saved", chain=True)
+        dWs = [L.new_weight_gradient(c, x.device) for c, x in zip(chains, xs)]
+        L.call("lde_chain_group_backward_saved", None, n, ctx.c_handles, L.ptr_array(xs), L.ptr_array(ys), L.ptr_array(dys),
+               L.ptr_array(saveds) if saveds is not None else None, ctx.c_Ns, L.ptr_array(dxs), L.ptr_array(dWs), stream, err=chains[0]._native())
         return (None, *dxs, *dWs)
 
 
@@ -322,8 +249,10 @@ def apply_chains_grouped(pairs):
     return [y.t() for y in ys]
 
 
-class Chain(torch.nn.Module):
+class Chain(L.NativeModule, torch.nn.Module):
     """Chain(layers...) of Dense / SkipConnection(Dense) applied to the first dimension of x ([in, B] or [in, B, T])."""
+
+    _create, _destroy = "lde_chain_create", "lde_chain_destroy"
 
     def __init__(self, *layers):
         super().__init__()
@@ -349,9 +278,6 @@ class Chain(torch.nn.Module):
         self.theta = torch.nn.Parameter(torch.cat(parts).float())
         for d in dense:
             d._owner, d._w0, d._b0 = self, None, None
-        self._handle = None
-        self._lib = None
-        self._wkey = None          # set by _lib.refresh_weights: the parameter value the handle already holds
         self.dtype = "f32"
 
     def set_dtype(self, dtype: str) -> "Chain":
@@ -361,40 +287,27 @@ class Chain(torch.nn.Module):
             raise ValueError("dtype: 'f32' or 'bf16'")
         self.dtype = dtype
         if self._handle is not None:
-            L.check(self._lib.lde_chain_set_dtype(self._handle, L.DTYPE_BF16 if dtype == "bf16" else L.DTYPE_F32), self._handle,
-                    "lde_chain_set_dtype", chain=True)
+            L.call("lde_chain_set_dtype", self._handle, L.DTYPE_BF16 if dtype == "bf16" else L.DTYPE_F32)
         return self
 
-    def _native(self):
-        if self._handle is None:
-            self._lib = L.load()
-            d = L.ChainDesc()
-            d.abi_version = L.LDE_ABI_VERSION
-            d.n_layers = len(self._dense)
-            for i, s in enumerate(self.sizes):
-                d.sizes[i] = s
-            for i, (a, k) in enumerate(zip(self.acts, self.skips)):
-                d.activation[i], d.skip[i] = a, k
-            h = C.c_void_p()
-            rc = self._lib.lde_chain_create(C.byref(d), C.byref(h))
-            if rc != 0:
-                try:
-                    L.check(rc, h if h else None, "lde_chain_create", chain=True)
-                finally:
-                    if h:
-                        self._lib.lde_chain_destroy(h)
-            L.check(self._lib.lde_chain_set_accumulate(h, 0), h, "lde_chain_set_accumulate", chain=True)   # the pullback hands autograd a fresh gradient
-            if self.dtype == "bf16":
-                L.check(self._lib.lde_chain_set_dtype(h, L.DTYPE_BF16), h, "lde_chain_set_dtype", chain=True)
-            self._handle = h
-        return self._handle
+    def _desc(self):
+        d = L.ChainDesc()
+        d.abi_version = L.LDE_ABI_VERSION
+        d.n_layers = len(self._dense)
+        for i, s in enumerate(self.sizes):
+            d.sizes[i] = s
+        for i, (a, k) in enumerate(zip(self.acts, self.skips)):
+            d.activation[i], d.skip[i] = a, k
+        return d
 
-    def __del__(self):
-        try:
-            if self._handle is not None and self._lib is not None:
-                self._lib.lde_chain_destroy(self._handle)
-        except Exception:
-            pass
+    def _created(self, h):
+        L.call("lde_chain_set_accumulate", h, 0)          # the pullback hands autograd a fresh gradient
+        if self.dtype == "bf16":
+            L.call("lde_chain_set_dtype", h, L.DTYPE_BF16)
+
+    def _new_saved(self, N: int, device) -> torch.Tensor:
+        """The buffer a training forward of N columns keeps its hidden activations in (lde_chain_saved_floats)."""
+        return torch.empty((int(self._lib.lde_chain_saved_floats(self._handle, N)),), device=device, dtype=torch.float32)
 
     def flat_weights(self) -> torch.Tensor:
         """Flux.destructure order: per Dense vec(W) column-major [out×in], then b — the parameter itself."""

@@ -249,8 +249,7 @@ class LdeComm:
         if buf.dtype != torch.float32 or not buf.is_cuda or not buf.is_contiguous():
             raise self._L.LdeError("lde_comm_allreduce_f32 takes a contiguous f32 device buffer")
         sp = self._L.raw_stream(buf.device.index) if stream is None else self._C.c_void_p(stream.cuda_stream)
-        self._L.check(self._lib.lde_comm_allreduce_f32(self.handle, self._C.c_void_p(buf.data_ptr()), buf.numel(), sp), None,
-                      "lde_comm_allreduce_f32")
+        self._L.call("lde_comm_allreduce_f32", None, self.handle, self._L.ptr(buf), buf.numel(), sp)   # (a comm handle has no lde_last_error)
         return buf
 
     def close(self):

@@ -12,16 +12,10 @@ On HIP tensors every function is one liblde.so kernel (two for the reductions) f
 by lde_randn from the state of torch's CUDA generator (`randn` below), like the reference draws it with randn. There is no CPU path."""
 from __future__ import annotations
 
-import ctypes as C
-import os
 
 import torch
 
 from . import _lib as L
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
 
 
 def _stream():
@@ -29,18 +23,16 @@ def _stream():
 
 
 def _need_gpu(t):
-    if not t.is_cuda:
-        raise L.LdeError("the loss kernels run on the GPU only (no CPU fallback)")
+    L.need_gpu(t.is_cuda, "a loss kernel")
 
 
 class _SampleFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mu, logvar, eps):
         _need_gpu(mu)
-        lib = L.load()
         mu, logvar = mu.contiguous().float(), logvar.contiguous().float()
         out = torch.empty_like(mu)
-        L.check(lib.lde_sample_forward(_p(mu), _p(logvar), _p(eps), mu.numel(), _p(out), _stream()), None, "lde_sample_forward")
+        L.call("lde_sample_forward", None, L.ptr(mu), L.ptr(logvar), L.ptr(eps), mu.numel(), L.ptr(out), _stream())
         ctx.save_for_backward(logvar, eps)
         return out
 
@@ -49,8 +41,7 @@ class _SampleFn(torch.autograd.Function):
         logvar, eps = ctx.saved_tensors
         dl = dl.contiguous()
         dlv = torch.empty_like(logvar)
-        L.check(L.load().lde_sample_backward(_p(logvar), _p(eps), _p(dl), dl.numel(), _p(dlv), _stream()), None,
-                "lde_sample_backward")
+        L.call("lde_sample_backward", None, L.ptr(logvar), L.ptr(eps), L.ptr(dl), dl.numel(), L.ptr(dlv), _stream())
         return dl, dlv, None
 
 
@@ -58,11 +49,9 @@ class _KlFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mu, logvar, scale):
         _need_gpu(mu)
-        lib = L.load()
         mu, logvar = mu.contiguous().float(), logvar.contiguous().float()
-        ws = torch.empty(L.LOSS_SCRATCH_FLOATS + 1, device=mu.device, dtype=torch.float32)     # [0]: the result, then scratch
-        L.check(lib.lde_kl_forward(_p(mu), _p(logvar), mu.numel(), scale, _p(ws), C.c_void_p(ws.data_ptr() + 4), _stream()),
-                None, "lde_kl_forward")
+        ws, p_out, p_scratch = L.loss_scratch(mu.device)
+        L.call("lde_kl_forward", None, L.ptr(mu), L.ptr(logvar), mu.numel(), scale, p_out, p_scratch, _stream())
         ctx.save_for_backward(mu, logvar)
         ctx.scale = scale
         return ws[0]
@@ -72,8 +61,7 @@ class _KlFn(torch.autograd.Function):
         mu, logvar = ctx.saved_tensors
         g = g.contiguous().float()
         dmu, dlv = torch.empty_like(mu), torch.empty_like(logvar)
-        L.check(L.load().lde_kl_backward(_p(mu), _p(logvar), mu.numel(), ctx.scale, _p(g), _p(dmu), _p(dlv), _stream()), None,
-                "lde_kl_backward")
+        L.call("lde_kl_backward", None, L.ptr(mu), L.ptr(logvar), mu.numel(), ctx.scale, L.ptr(g), L.ptr(dmu), L.ptr(dlv), _stream())
         return dmu, dlv, None
 
 
@@ -81,10 +69,8 @@ class _MseFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, xhat, scale):
         _need_gpu(xhat)
-        lib = L.load()
-        ws = torch.empty(L.LOSS_SCRATCH_FLOATS + 1, device=xhat.device, dtype=torch.float32)
-        L.check(lib.lde_mse_forward(_p(x), _p(xhat), xhat.numel(), scale, _p(ws), C.c_void_p(ws.data_ptr() + 4), _stream()),
-                None, "lde_mse_forward")
+        ws, p_out, p_scratch = L.loss_scratch(xhat.device)
+        L.call("lde_mse_forward", None, L.ptr(x), L.ptr(xhat), xhat.numel(), scale, p_out, p_scratch, _stream())
         ctx.save_for_backward(x, xhat)
         ctx.scale = scale
         return ws[0]
@@ -94,8 +80,7 @@ class _MseFn(torch.autograd.Function):
         x, xhat = ctx.saved_tensors
         g = g.contiguous().float()
         dxh = torch.empty_like(xhat)
-        L.check(L.load().lde_mse_backward(_p(x), _p(xhat), xhat.numel(), ctx.scale, _p(g), _p(dxh), _stream()), None,
-                "lde_mse_backward")
+        L.call("lde_mse_backward", None, L.ptr(x), L.ptr(xhat), xhat.numel(), ctx.scale, L.ptr(g), L.ptr(dxh), _stream())
         return None, dxh, None
 
 
@@ -106,11 +91,10 @@ class _SampleKlFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mu, logvar, eps, scale, base):
         _need_gpu(mu)
-        lib = L.load()
         out = torch.empty_like(mu)
-        ws = torch.empty(L.LOSS_SCRATCH_FLOATS + 1, device=mu.device, dtype=torch.float32)
-        L.check(lib.lde_sample_kl_forward(_p(mu), _p(logvar), _p(eps), mu.numel(), scale, _p(base) if base is not None else C.c_void_p(),
-                                          _p(out), _p(ws), C.c_void_p(ws.data_ptr() + 4), _stream()), None, "lde_sample_kl_forward")
+        ws, p_out, p_scratch = L.loss_scratch(mu.device)
+        L.call("lde_sample_kl_forward", None, L.ptr(mu), L.ptr(logvar), L.ptr(eps), mu.numel(), scale, L.ptr(base), L.ptr(out), p_out, p_scratch,
+               _stream())
         ctx.save_for_backward(mu, logvar, eps)
         ctx.scale, ctx.has_base = scale, base is not None
         return out, ws[0]
@@ -120,8 +104,8 @@ class _SampleKlFn(torch.autograd.Function):
         mu, logvar, eps = ctx.saved_tensors
         dl, g = dl.contiguous(), g.contiguous().float()
         dmu, dlv = torch.empty_like(mu), torch.empty_like(logvar)
-        L.check(L.load().lde_sample_kl_backward(_p(mu), _p(logvar), _p(eps), _p(dl), _p(g), ctx.scale, mu.numel(), _p(dmu), _p(dlv),
-                                                _stream()), None, "lde_sample_kl_backward")
+        L.call("lde_sample_kl_backward", None, L.ptr(mu), L.ptr(logvar), L.ptr(eps), L.ptr(dl), L.ptr(g), ctx.scale, mu.numel(), L.ptr(dmu),
+               L.ptr(dlv), _stream())
         return dmu, dlv, None, None, (g if ctx.has_base else None)
 
 
@@ -131,9 +115,8 @@ class _MseAddFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, xhat, scale, base):
         _need_gpu(xhat)
-        ws = torch.empty(L.LOSS_SCRATCH_FLOATS + 1, device=xhat.device, dtype=torch.float32)
-        L.check(L.load().lde_mse_forward_add(_p(x), _p(xhat), xhat.numel(), scale, _p(base), _p(ws), C.c_void_p(ws.data_ptr() + 4),
-                                             _stream()), None, "lde_mse_forward_add")
+        ws, p_out, p_scratch = L.loss_scratch(xhat.device)
+        L.call("lde_mse_forward_add", None, L.ptr(x), L.ptr(xhat), xhat.numel(), scale, L.ptr(base), p_out, p_scratch, _stream())
         ctx.save_for_backward(x, xhat)
         ctx.scale = scale
         return ws[0]
@@ -143,8 +126,7 @@ class _MseAddFn(torch.autograd.Function):
         x, xhat = ctx.saved_tensors
         g = g.contiguous().float()
         dxh = torch.empty_like(xhat)
-        L.check(L.load().lde_mse_backward(_p(x), _p(xhat), xhat.numel(), ctx.scale, _p(g), _p(dxh), _stream()), None,
-                "lde_mse_backward")
+        L.call("lde_mse_backward", None, L.ptr(x), L.ptr(xhat), xhat.numel(), ctx.scale, L.ptr(g), L.ptr(dxh), _stream())
         return None, dxh, None, g
 
 
@@ -197,7 +179,7 @@ def _draw_key(n: int, idx: int):
     if capturing:
         seed, off = _noise_base[idx]
         _noise_call[0] += 1
-        return seed, (off + (1 << 40)) & 0xFFFFFFFFFFFFFFFF, _noise_call[0], _p(_noise_epoch[idx])
+        return seed, (off + (1 << 40)) & 0xFFFFFFFFFFFFFFFF, _noise_call[0], L.ptr(_noise_epoch[idx])
     gen = torch.cuda.default_generators[idx]
     seed, off = gen.initial_seed() & 0xFFFFFFFFFFFFFFFF, gen.get_offset()
     gen.set_offset(off + 4 * ((n + 3) // 4))
@@ -208,15 +190,14 @@ def _draw_key(n: int, idx: int):
 def randn(shape, device) -> torch.Tensor:
     """ε ~ N(0, 1) of the given shape on `device` (float32)."""
     device = torch.device(device)
-    if device.type != "cuda":
-        raise L.LdeError("the loss kernels run on the GPU only (no CPU fallback)")
+    L.need_gpu(device.type == "cuda", "a loss kernel")
     idx = device.index if device.index is not None else torch.cuda.current_device()
     out = torch.empty(shape, device=device, dtype=torch.float32)
     key = _draw_key(out.numel(), idx)
     if key is None:
         return torch.randn(shape, device=device, dtype=torch.float32)
     seed, off, call, ep = key
-    L.check(L.load().lde_randn(_p(out), out.numel(), seed, off, call, ep, None, L.raw_stream(idx)), None, "lde_randn")
+    L.call("lde_randn", None, L.ptr(out), out.numel(), seed, off, call, ep, None, L.raw_stream(idx))
     return out
 
 
@@ -228,13 +209,11 @@ class _SampleKlPairFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mu_a, lv_a, mu_b, lv_b, scale_a, scale_b, keys):
-        lib = L.load()
         (seed, off_a, call_a, ep), (_, off_b, call_b, _) = keys
         eps_a, eps_b, l_a, l_b = torch.empty_like(mu_a), torch.empty_like(mu_b), torch.empty_like(mu_a), torch.empty_like(mu_b)
-        ws = torch.empty(3, device=mu_a.device, dtype=torch.float32)          # [0]: the total, then two partial sums
-        L.check(lib.lde_sample_kl_pair_forward(_p(mu_a), _p(lv_a), mu_a.numel(), scale_a, _p(mu_b), _p(lv_b), mu_b.numel(), scale_b, C.c_void_p(),
-                                               seed, off_a, off_b, call_a, call_b, ep, _p(eps_a), _p(eps_b), _p(l_a), _p(l_b), _p(ws),
-                                               C.c_void_p(ws.data_ptr() + 4), _stream()), None, "lde_sample_kl_pair_forward")
+        ws, p_out, p_parts = L.loss_scratch(mu_a.device, 2)          # [0]: the total, then two partial sums
+        L.call("lde_sample_kl_pair_forward", None, L.ptr(mu_a), L.ptr(lv_a), mu_a.numel(), scale_a, L.ptr(mu_b), L.ptr(lv_b), mu_b.numel(), scale_b,
+               None, seed, off_a, off_b, call_a, call_b, ep, L.ptr(eps_a), L.ptr(eps_b), L.ptr(l_a), L.ptr(l_b), p_out, p_parts, _stream())
         ctx.save_for_backward(mu_a, lv_a, eps_a, mu_b, lv_b, eps_b)
         ctx.scales = (scale_a, scale_b)
         return l_a, l_b, ws[0]
@@ -244,9 +223,9 @@ class _SampleKlPairFn(torch.autograd.Function):
         mu_a, lv_a, eps_a, mu_b, lv_b, eps_b = ctx.saved_tensors
         dl_a, dl_b, g = dl_a.contiguous(), dl_b.contiguous(), g.contiguous().float()
         dmu_a, dlv_a, dmu_b, dlv_b = torch.empty_like(mu_a), torch.empty_like(lv_a), torch.empty_like(mu_b), torch.empty_like(lv_b)
-        L.check(L.load().lde_sample_kl_pair_backward(_p(mu_a), _p(lv_a), _p(eps_a), _p(dl_a), mu_a.numel(), ctx.scales[0], _p(mu_b), _p(lv_b),
-                                                     _p(eps_b), _p(dl_b), mu_b.numel(), ctx.scales[1], _p(g), _p(dmu_a), _p(dlv_a), _p(dmu_b),
-                                                     _p(dlv_b), _stream()), None, "lde_sample_kl_pair_backward")
+        L.call("lde_sample_kl_pair_backward", None, L.ptr(mu_a), L.ptr(lv_a), L.ptr(eps_a), L.ptr(dl_a), mu_a.numel(), ctx.scales[0], L.ptr(mu_b),
+               L.ptr(lv_b), L.ptr(eps_b), L.ptr(dl_b), mu_b.numel(), ctx.scales[1], L.ptr(g), L.ptr(dmu_a), L.ptr(dlv_a), L.ptr(dmu_b), L.ptr(dlv_b),
+               _stream())
         return dmu_a, dlv_a, dmu_b, dlv_b, None, None, None
 
 

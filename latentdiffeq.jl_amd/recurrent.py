@@ -19,7 +19,6 @@ latent_in are `Chain`s (lde_chain_*). `sample` (loss.py) draws ε with torch's g
 from __future__ import annotations
 
 import ctypes as C
-import os
 import math
 
 import torch
@@ -97,20 +96,14 @@ class _RecurrentFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rec: "Recurrent", x: torch.Tensor, W: torch.Tensor):
-        if not x.is_cuda:
-            raise L.LdeError("Recurrent needs CUDA/HIP tensors: it runs on the GPU only (no CPU fallback)")
-        h = rec._native()
-        lib = rec._lib
+        L.need_gpu(x.is_cuda, "Recurrent")
         stream = L.raw_stream(x.device.index)
-        if rec._wkey != L.weights_key(W):   # not handed over by refresh_weights() since the parameter last changed
-            Wc = W.detach().contiguous().float()
-            L.check(lib.lde_rnn_set_weights_device(h, C.c_void_p(Wc.data_ptr()), Wc.numel(), stream), h, "lde_rnn_set_weights_device", rnn=True)
-            rec._wkey = None
+        h = L.hand_over_weights(rec, W, stream)
         T, B, _ = x.shape
         y = torch.empty((B, rec.sizes[-1]), device=x.device, dtype=torch.float32)
         # a pullback will follow (grad mode is off inside Function.forward: ctx.needs_input_grad says so): the sweep keeps its records
-        fwd = lib.lde_rnn_forward_train if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) else lib.lde_rnn_forward
-        L.check(fwd(h, C.c_void_p(x.data_ptr()), T, B, C.c_void_p(y.data_ptr()), stream), h, "lde_rnn_forward", rnn=True)
+        train = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        L.call("lde_rnn_forward_train" if train else "lde_rnn_forward", h, L.ptr(x), T, B, L.ptr(y), stream)
         ctx.rec, ctx.need_dx = rec, x.requires_grad
         ctx.save_for_backward(x)
         return y
@@ -118,19 +111,13 @@ class _RecurrentFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         rec = ctx.rec
-        h = rec._native()
-        lib = rec._lib
         (x,) = ctx.saved_tensors
         T, B, _ = x.shape
         dy = dy.contiguous().float()
         stream = L.raw_stream(x.device.index)
         dx = torch.empty_like(x) if ctx.need_dx else None
-        dW = torch.empty((rec.num_weights,), device=x.device, dtype=torch.float32)       # written, not accumulated (set_accumulate(0))
-        if L.dw_stream is not None:
-            dW.record_stream(L.dw_stream)          # written on the weight-gradient stream (set_async_weight_gradients)
-        L.check(lib.lde_rnn_backward(h, C.c_void_p(x.data_ptr()), C.c_void_p(dy.data_ptr()), T, B,
-                                     C.c_void_p(dx.data_ptr()) if dx is not None else C.c_void_p(), C.c_void_p(dW.data_ptr()), stream),
-                h, "lde_rnn_backward", rnn=True)
+        dW = L.new_weight_gradient(rec, x.device)
+        L.call("lde_rnn_backward", rec._native(), L.ptr(x), L.ptr(dy), T, B, L.ptr(dx), L.ptr(dW), stream)
         return None, dx, dW
 
 
@@ -144,8 +131,7 @@ class _RecurrentGroupFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, recs, x, *Ws):
-        if not x.is_cuda:
-            raise L.LdeError("Recurrent needs CUDA/HIP tensors: it runs on the GPU only (no CPU fallback)")
+        L.need_gpu(x.is_cuda, "Recurrent")
         dev = x.device
         main = torch.cuda.current_stream(dev)
         streams = _side_streams.setdefault((dev.index, len(recs)), [torch.cuda.Stream(dev) for _ in recs])
@@ -153,16 +139,12 @@ class _RecurrentGroupFn(torch.autograd.Function):
         ready = main.record_event()
         ys = []
         for rec, W, st in zip(recs, Ws, streams):
-            h, raw = rec._native(), C.c_void_p(st.cuda_stream)
+            raw = C.c_void_p(st.cuda_stream)
             st.wait_event(ready)
-            if rec._wkey != L.weights_key(W):
-                Wc = W.detach().contiguous().float()
-                L.check(rec._lib.lde_rnn_set_weights_device(h, C.c_void_p(Wc.data_ptr()), Wc.numel(), raw), h, "lde_rnn_set_weights_device", rnn=True)
-                Wc.record_stream(st)
-                rec._wkey = None
+            h = L.hand_over_weights(rec, W, raw, side_stream=st)
             y = torch.empty((B, rec.sizes[-1]), device=dev, dtype=torch.float32)
             y.record_stream(st)
-            L.check(rec._lib.lde_rnn_forward(h, C.c_void_p(x.data_ptr()), T, B, C.c_void_p(y.data_ptr()), raw), h, "lde_rnn_forward", rnn=True)
+            L.call("lde_rnn_forward", h, L.ptr(x), T, B, L.ptr(y), raw)
             ys.append(y)
         for st in streams:
             x.record_stream(st)
@@ -183,32 +165,21 @@ class _RecurrentGroupFn(torch.autograd.Function):
         ready = main.record_event()
         dxs, dWs = [], []
         for rec, dy, st in zip(recs, dys, streams):               # the sweeps first …
-            h, raw = rec._native(), C.c_void_p(st.cuda_stream)
             st.wait_event(ready)
             dx = torch.empty_like(x) if ctx.need_dx else None
             dy.record_stream(st)
             x.record_stream(st)
             if dx is not None:
                 dx.record_stream(st)
-            L.check(rec._lib.lde_rnn_backward_dx(h, C.c_void_p(x.data_ptr()), C.c_void_p(dy.data_ptr()), T, B,
-                                                 C.c_void_p(dx.data_ptr()) if dx is not None else C.c_void_p(), raw), h, "lde_rnn_backward_dx", rnn=True)
-            dxs.append(dx)
+                dxs.append(dx)
+            L.call("lde_rnn_backward_dx", rec._native(), L.ptr(x), L.ptr(dy), T, B, L.ptr(dx), C.c_void_p(st.cuda_stream))
         for rec, st in zip(recs, streams):                        # … then the weight-gradient tails
-            dW = torch.empty((rec.num_weights,), device=dev, dtype=torch.float32)     # written, not accumulated (set_accumulate(0))
-            dW.record_stream(st)
-            if L.dw_stream is not None:
-                dW.record_stream(L.dw_stream)
-            L.check(rec._lib.lde_rnn_backward_dw(rec._native(), C.c_void_p(dW.data_ptr()), C.c_void_p(st.cuda_stream)), rec._native(),
-                    "lde_rnn_backward_dw", rnn=True)
+            dW = L.new_weight_gradient(rec, dev, also_stream=st)
+            L.call("lde_rnn_backward_dw", rec._native(), L.ptr(dW), C.c_void_p(st.cuda_stream))
             dWs.append(dW)
         for st in streams:
             main.wait_stream(st)
-        dx = None
-        if ctx.need_dx:
-            dx = dxs[0]
-            for d in dxs[1:]:
-                dx = dx + d
-        return (None, dx, *dWs)
+        return (None, L.sum_gradients(dxs), *dWs)
 
 
 class _RecurrentLaunchGroupFn(torch.autograd.Function):
@@ -220,28 +191,17 @@ class _RecurrentLaunchGroupFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, recs, x, *Ws):
-        if not x.is_cuda:
-            raise L.LdeError("Recurrent needs CUDA/HIP tensors: it runs on the GPU only (no CPU fallback)")
+        L.need_gpu(x.is_cuda, "Recurrent")
         n = len(recs)
         dev = x.device
         stream = L.raw_stream(dev.index)
         T, B, _ = x.shape
-        hs = []
-        for rec, W in zip(recs, Ws):
-            h = rec._native()
-            if rec._wkey != L.weights_key(W):
-                Wc = W.detach().contiguous().float()
-                L.check(rec._lib.lde_rnn_set_weights_device(h, C.c_void_p(Wc.data_ptr()), Wc.numel(), stream), h, "lde_rnn_set_weights_device", rnn=True)
-                rec._wkey = None
-            hs.append(h)
-        lib = recs[0]._lib
+        hs = [L.hand_over_weights(rec, W, stream) for rec, W in zip(recs, Ws)]
         ys = [torch.empty((B, rec.sizes[-1]), device=dev, dtype=torch.float32) for rec in recs]
-        arr = lambda ptrs: (C.c_void_p * n)(*ptrs)
-        ctx.c_handles = arr([h.value for h in hs])
+        ctx.c_handles = L.ptr_array([h.value for h in hs])
         train = any(ctx.needs_input_grad[1:])          # a pullback will follow: the sweeps keep their records (lde_rnn_forward_train)
-        fwd = lib.lde_rnn_group_forward_train if train else lib.lde_rnn_group_forward
-        rc = fwd(n, ctx.c_handles, arr([x.data_ptr()] * n), T, B, arr([y.data_ptr() for y in ys]), stream)
-        L.check(rc, hs[0], "lde_rnn_group_forward", rnn=True)
+        L.call("lde_rnn_group_forward_train" if train else "lde_rnn_group_forward", None, n, ctx.c_handles, L.ptr_array([x] * n), T, B,
+               L.ptr_array(ys), stream, err=hs[0])
         ctx.recs, ctx.need_dx = recs, x.requires_grad
         ctx.save_for_backward(x)
         return tuple(ys)
@@ -256,18 +216,10 @@ class _RecurrentLaunchGroupFn(torch.autograd.Function):
         stream = L.raw_stream(dev.index)
         dys = [dy.contiguous().float() for dy in dys]
         dxs = [torch.empty_like(x) for _ in recs] if ctx.need_dx else None
-        dWs = [torch.empty((rec.num_weights,), device=dev, dtype=torch.float32) for rec in recs]     # written, not accumulated (set_accumulate(0))
-        arr = lambda ptrs: (C.c_void_p * n)(*ptrs)
-        lib = recs[0]._lib
-        rc = lib.lde_rnn_group_backward(n, ctx.c_handles, arr([x.data_ptr()] * n), arr([d.data_ptr() for d in dys]), T, B,
-                                        arr([d.data_ptr() for d in dxs]) if dxs is not None else None, arr([d.data_ptr() for d in dWs]), stream)
-        L.check(rc, recs[0]._native(), "lde_rnn_group_backward", rnn=True)
-        dx = None
-        if dxs is not None:
-            dx = dxs[0]
-            for d in dxs[1:]:
-                dx = dx + d
-        return (None, dx, *dWs)
+        dWs = [L.new_weight_gradient(rec, dev) for rec in recs]
+        L.call("lde_rnn_group_backward", None, n, ctx.c_handles, L.ptr_array([x] * n), L.ptr_array(dys), T, B,
+               L.ptr_array(dxs) if dxs is not None else None, L.ptr_array(dWs), stream, err=recs[0]._native())
+        return (None, L.sum_gradients(dxs), *dWs)
 
 
 class _GokuEncoderFn(torch.autograd.Function):
@@ -287,64 +239,39 @@ class _GokuEncoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mods, x, *Ws):
         fe, pes, lis, (T, B) = mods
-        if not x.is_cuda:
-            raise L.LdeError("the encoder needs CUDA/HIP tensors: it runs on the GPU only (no CPU fallback)")
+        L.need_gpu(x.is_cuda, "the encoder")
         dev = x.device
         stream = L.raw_stream(dev.index)
         N = T * B
-        W_fe, W_pes, W_lis = Ws[0], Ws[1:4], Ws[4:8]
         # weights not handed over by refresh_weights() since the parameters last changed
-        h_fe = fe._native()
-        lib = fe._lib
-        if fe._wkey != L.weights_key(W_fe):
-            Wc = W_fe.detach().contiguous().float()
-            L.check(lib.lde_chain_set_weights_device(h_fe, C.c_void_p(Wc.data_ptr()), Wc.numel(), stream), h_fe, "lde_chain_set_weights_device", chain=True)
-            fe._wkey = None
-        h_pes, h_lis = [], []
-        for rec, W in zip(pes, W_pes):
-            h = rec._native()
-            if rec._wkey != L.weights_key(W):
-                Wc = W.detach().contiguous().float()
-                L.check(lib.lde_rnn_set_weights_device(h, C.c_void_p(Wc.data_ptr()), Wc.numel(), stream), h, "lde_rnn_set_weights_device", rnn=True)
-                rec._wkey = None
-            h_pes.append(h)
-        for c, W in zip(lis, W_lis):
-            h = c._native()
-            if c._wkey != L.weights_key(W):
-                Wc = W.detach().contiguous().float()
-                L.check(lib.lde_chain_set_weights_device(h, C.c_void_p(Wc.data_ptr()), Wc.numel(), stream), h, "lde_chain_set_weights_device", chain=True)
-                c._wkey = None
-            h_lis.append(h)
+        h_fe = L.hand_over_weights(fe, Ws[0], stream)
+        h_pes = [L.hand_over_weights(rec, W, stream) for rec, W in zip(pes, Ws[1:4])]
+        h_lis = [L.hand_over_weights(c, W, stream) for c, W in zip(lis, Ws[4:8])]
         train = any(ctx.needs_input_grad[1:])
         f32 = dict(device=dev, dtype=torch.float32)
         # 1. the frames' features, (T, B, f) = the stacks' [f × B × T]
         y_fe = torch.empty((N, fe.sizes[-1]), **f32)
-        sv_fe = torch.empty((int(lib.lde_chain_saved_floats(h_fe, N)),), **f32) if train else None
+        sv_fe = fe._new_saved(N, dev) if train else None
         if train:
-            L.check(lib.lde_chain_forward_save(h_fe, C.c_void_p(x.data_ptr()), N, C.c_void_p(y_fe.data_ptr()), C.c_void_p(sv_fe.data_ptr()), stream),
-                    h_fe, "lde_chain_forward_save", chain=True)
+            L.call("lde_chain_forward_save", h_fe, L.ptr(x), N, L.ptr(y_fe), L.ptr(sv_fe), stream)
         else:
-            L.check(lib.lde_chain_forward(h_fe, C.c_void_p(x.data_ptr()), N, C.c_void_p(y_fe.data_ptr()), stream), h_fe, "lde_chain_forward", chain=True)
+            L.call("lde_chain_forward", h_fe, L.ptr(x), N, L.ptr(y_fe), stream)
         # 2. the three stacks; the θ stacks write the two column blocks of their vcat
         hz, hf, hb = (rec.sizes[-1] for rec in pes)
         y_z0 = torch.empty((B, hz), **f32)
         y_th = torch.empty((B, hf + hb), **f32)
-        arr3 = lambda ptrs: (C.c_void_p * 3)(*ptrs)
-        ctx.c_pes = arr3([h.value for h in h_pes])
+        ctx.c_pes = L.ptr_array([h.value for h in h_pes])
         ctx.c_ld = (C.c_int32 * 3)(hz, hf + hb, hf + hb)
-        rc = lib.lde_rnn_group_forward_ld(3, ctx.c_pes, arr3([y_fe.data_ptr()] * 3), T, B,
-                                          arr3([y_z0.data_ptr(), y_th.data_ptr(), y_th.data_ptr() + 4 * hf]), ctx.c_ld, int(train), stream)
-        L.check(rc, h_pes[0], "lde_rnn_group_forward_ld", rnn=True)
+        L.call("lde_rnn_group_forward_ld", None, 3, ctx.c_pes, L.ptr_array([y_fe] * 3), T, B,
+               L.ptr_array([y_z0, y_th, L.ptr(y_th, 4 * hf).value]), ctx.c_ld, int(train), stream, err=h_pes[0])
         # 3. the four heads
         xs_li = (y_z0, y_th, y_z0, y_th)
         outs = [torch.empty((B, c.sizes[-1]), **f32) for c in lis]
-        sv_li = [torch.empty((int(lib.lde_chain_saved_floats(h, B)),), **f32) for h in h_lis] if train else None
-        arr4 = lambda ptrs: (C.c_void_p * 4)(*ptrs)
-        ctx.c_lis = arr4([h.value for h in h_lis])
+        sv_li = [c._new_saved(B, dev) for c in lis] if train else None
+        ctx.c_lis = L.ptr_array([h.value for h in h_lis])
         ctx.c_Ns = (C.c_int64 * 4)(B, B, B, B)
-        rc = lib.lde_chain_group_forward_save(4, ctx.c_lis, arr4([t.data_ptr() for t in xs_li]), ctx.c_Ns, arr4([o.data_ptr() for o in outs]),
-                                              arr4([t.data_ptr() for t in sv_li]) if train else None, stream)
-        L.check(rc, h_lis[0], "lde_chain_group_forward_save", chain=True)
+        L.call("lde_chain_group_forward_save", None, 4, ctx.c_lis, L.ptr_array(xs_li), ctx.c_Ns, L.ptr_array(outs),
+               L.ptr_array(sv_li) if train else None, stream, err=h_lis[0])
         ctx.mods, ctx.train, ctx.TB, ctx.need_dx = mods, train, (T, B), bool(ctx.needs_input_grad[1])
         if train:
             ctx.save_for_backward(x, y_fe, sv_fe, y_z0, y_th, *outs, *sv_li)
@@ -358,41 +285,28 @@ class _GokuEncoderFn(torch.autograd.Function):
         t = ctx.saved_tensors
         x, y_fe, sv_fe, y_z0, y_th = t[:5]
         outs, sv_li = t[5:9], t[9:13]
-        lib = fe._lib
         dev = x.device
         stream = L.raw_stream(dev.index)
-        f32 = dict(device=dev, dtype=torch.float32)
-        arr3 = lambda ptrs: (C.c_void_p * 3)(*ptrs)
-        arr4 = lambda ptrs: (C.c_void_p * 4)(*ptrs)
         douts = [d.contiguous().float() for d in douts]
         # 1. the heads: input gradients per head (two per stack output), weight gradients written (set_accumulate(0))
         xs_li = (y_z0, y_th, y_z0, y_th)
         d_li = [torch.empty_like(xi) for xi in xs_li]
-        dW_li = [torch.empty((c.num_weights,), **f32) for c in lis]
-        rc = lib.lde_chain_group_backward_saved(4, ctx.c_lis, arr4([t_.data_ptr() for t_ in xs_li]), arr4([o.data_ptr() for o in outs]),
-                                                arr4([d.data_ptr() for d in douts]), arr4([s_.data_ptr() for s_ in sv_li]), ctx.c_Ns,
-                                                arr4([d.data_ptr() for d in d_li]), arr4([d.data_ptr() for d in dW_li]), stream)
-        L.check(rc, lis[0]._native(), "lde_chain_group_backward_saved", chain=True)
+        dW_li = [L.new_weight_gradient(c, dev) for c in lis]
+        L.call("lde_chain_group_backward_saved", None, 4, ctx.c_lis, L.ptr_array(xs_li), L.ptr_array(outs), L.ptr_array(douts),
+               L.ptr_array(sv_li), ctx.c_Ns, L.ptr_array(d_li), L.ptr_array(dW_li), stream, err=lis[0]._native())
         # 2. the stacks: output gradient = μ head's + log σ² head's input gradient, the θ stacks' as column blocks of the (B, 2h) arrays
         hf = pes[1].sizes[-1]
         dz_a, dth_a, dz_b, dth_b = d_li
         dxs = [torch.empty_like(y_fe) for _ in pes]
-        dW_pe = [torch.empty((rec.num_weights,), **f32) for rec in pes]
-        rc = lib.lde_rnn_group_backward_ld(3, ctx.c_pes, arr3([y_fe.data_ptr()] * 3),
-                                           arr3([dz_a.data_ptr(), dth_a.data_ptr(), dth_a.data_ptr() + 4 * hf]),
-                                           arr3([dz_b.data_ptr(), dth_b.data_ptr(), dth_b.data_ptr() + 4 * hf]), ctx.c_ld, T, B,
-                                           arr3([d.data_ptr() for d in dxs]), arr3([d.data_ptr() for d in dW_pe]), stream)
-        L.check(rc, pes[0]._native(), "lde_rnn_group_backward_ld", rnn=True)
+        dW_pe = [L.new_weight_gradient(rec, dev) for rec in pes]
+        L.call("lde_rnn_group_backward_ld", None, 3, ctx.c_pes, L.ptr_array([y_fe] * 3),
+               L.ptr_array([dz_a, dth_a, L.ptr(dth_a, 4 * hf).value]), L.ptr_array([dz_b, dth_b, L.ptr(dth_b, 4 * hf).value]), ctx.c_ld, T, B,
+               L.ptr_array(dxs), L.ptr_array(dW_pe), stream, err=pes[0]._native())
         # 3. the feature extractor: output gradient = the three stacks' input gradients
         dx = torch.empty_like(x) if ctx.need_dx else None
-        dW_fe = torch.empty((fe.num_weights,), **f32)
-        if L.dw_stream is not None:
-            for dW in (dW_fe, *dW_li):
-                dW.record_stream(L.dw_stream)
-        rc = lib.lde_chain_backward_saved_sum(fe._native(), C.c_void_p(x.data_ptr()), C.c_void_p(y_fe.data_ptr()), 3, arr3([d.data_ptr() for d in dxs]),
-                                              C.c_void_p(sv_fe.data_ptr()), N, C.c_void_p(dx.data_ptr()) if dx is not None else C.c_void_p(),
-                                              C.c_void_p(dW_fe.data_ptr()), stream)
-        L.check(rc, fe._native(), "lde_chain_backward_saved_sum", chain=True)
+        dW_fe = L.new_weight_gradient(fe, dev)
+        L.call("lde_chain_backward_saved_sum", fe._native(), L.ptr(x), L.ptr(y_fe), 3, L.ptr_array(dxs), L.ptr(sv_fe), N, L.ptr(dx), L.ptr(dW_fe),
+               stream)
         return (None, dx, dW_fe, *dW_pe, *dW_li)
 
 
@@ -419,9 +333,11 @@ def _encode_goku_fused(encoder: Encoder, x):
     return (mu_z0.t(), mu_th.t()), (ls_z0.t(), ls_th.t())
 
 
-class Recurrent(torch.nn.Module):
+class Recurrent(L.NativeModule, torch.nn.Module):
     """A stack of cells of one kind applied to the frames of x [in, B, T] (reverse=True: frames T..1), returning the output
     after the last frame, [h_last, B] — `[pe(x) for x in frames][end]` followed by `Flux.reset!`  [REF GOKU.jl:40-47]."""
+
+    _create, _destroy, _is_recurrent = "lde_rnn_create", "lde_rnn_destroy", True
 
     def __init__(self, *cells, reverse: bool = False):
         super().__init__()
@@ -445,35 +361,16 @@ class Recurrent(torch.nn.Module):
         self.theta = torch.nn.Parameter(torch.cat(parts).float())
         for c in cells:
             c._owner, c._init = self, None
-        self._handle, self._lib = None, None
-        self._wkey = None          # set by _lib.refresh_weights: the parameter value the handle already holds
-        self._is_recurrent = True
 
-    def _native(self):
-        if self._handle is None:
-            self._lib = L.load()
-            d = L.RnnDesc()
-            d.abi_version, d.cell, d.n_layers, d.reverse = L.LDE_ABI_VERSION, self.code, len(self.cells), int(self.reverse)
-            for i, s in enumerate(self.sizes):
-                d.sizes[i] = s
-            h = C.c_void_p()
-            rc = self._lib.lde_rnn_create(C.byref(d), C.byref(h))
-            if rc != 0:
-                try:
-                    L.check(rc, h if h else None, "lde_rnn_create", rnn=True)
-                finally:
-                    if h:
-                        self._lib.lde_rnn_destroy(h)
-            L.check(self._lib.lde_rnn_set_accumulate(h, 0), h, "lde_rnn_set_accumulate", rnn=True)   # the pullback hands autograd a fresh gradient
-            self._handle = h
-        return self._handle
+    def _desc(self):
+        d = L.RnnDesc()
+        d.abi_version, d.cell, d.n_layers, d.reverse = L.LDE_ABI_VERSION, self.code, len(self.cells), int(self.reverse)
+        for i, s in enumerate(self.sizes):
+            d.sizes[i] = s
+        return d
 
-    def __del__(self):
-        try:
-            if self._handle is not None and self._lib is not None:
-                self._lib.lde_rnn_destroy(self._handle)
-        except Exception:
-            pass
+    def _created(self, h):
+        L.call("lde_rnn_set_accumulate", h, 0)            # the pullback hands autograd a fresh gradient
 
     def flat_weights(self) -> torch.Tensor:
         return self.theta

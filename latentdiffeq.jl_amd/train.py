@@ -17,7 +17,6 @@ no kernel of its own.
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Callable, Iterable, List, Optional, Sequence
 
@@ -203,7 +202,6 @@ class FluxADAMW(torch.optim.Adam):
 
     @torch.no_grad()
     def _native_step(self):
-        lib = L.load()
         if self.capturable:
             for g in self.param_groups:
                 ps = g["params"]
@@ -220,9 +218,8 @@ class FluxADAMW(torch.optim.Adam):
                         keep.append(gr)
                     t = tab[i]
                     t.p, t.g, t.m, t.v, t.n = p.data_ptr(), gr.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
-                L.check(lib.lde_adamw_flux_step_dev(len(ps), tab, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.decay,
-                                                    C.c_void_p(self._step_dev.data_ptr()), L.raw_stream(ps[0].device.index)), None,
-                        "lde_adamw_flux_step_dev")
+                L.call("lde_adamw_flux_step_dev", None, len(ps), tab, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.decay,
+                       L.ptr(self._step_dev), L.raw_stream(ps[0].device.index))
                 torch.autograd.graph.increment_version(ps)
             return
         for g in self.param_groups:
@@ -248,8 +245,8 @@ class FluxADAMW(torch.optim.Adam):
                         keep.append(gr)
                     t = tab[i]
                     t.p, t.g, t.m, t.v, t.n = p.data_ptr(), gr.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
-                L.check(lib.lde_adamw_flux_step(len(group), tab, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.decay, t_step,
-                                                L.raw_stream(group[0].device.index)), None, "lde_adamw_flux_step")
+                L.call("lde_adamw_flux_step", None, len(group), tab, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.decay, t_step,
+                       L.raw_stream(group[0].device.index))
                 # the kernel wrote through raw pointers: tell torch the parameters changed in place, so that `_lib.weights_key`
                 # (data_ptr, _version) — which lets a module skip its weight upload — and autograd's saved-tensor checks see it
                 torch.autograd.graph.increment_version(group)

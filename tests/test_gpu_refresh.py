@@ -10,13 +10,13 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _model(seed):
+def _model(seed, input_dim=64, hidden_dim_resnet=48):
     import torch
     import latentdiffeq_amd as la
     from latentdiffeq_amd import train as TR
     torch.manual_seed(seed)
     mt, diffeq = la.GOKU_basic(), la.Pendulum()
-    enc, dec = TR.default_layers(mt, 64, diffeq, device="cuda", hidden_dim_resnet=48)
+    enc, dec = TR.default_layers(mt, input_dim, diffeq, device="cuda", hidden_dim_resnet=hidden_dim_resnet)
     with torch.no_grad():
         dec[0][1]._dense[-1].bias.fill_(1.0)
     return TR.LatentDiffEqModel(mt, enc, dec)
@@ -123,3 +123,56 @@ def test_handover_in_bf16_mode_skips_the_f32_fragments_and_a_switch_back_rebuild
     with torch.no_grad():
         fresh.theta.copy_(c.theta)
     assert torch.equal(y_f, fresh(x))
+
+
+@pytest.mark.parametrize("branch_streams", [False, True])
+def test_a_training_step_uploads_exactly_the_weights_the_library_does_not_hold(branch_streams):
+    """Every call site hands its weights over through _lib.hand_over_weights: a training step (loss_batch + backward) after
+    refresh_weights() uploads nothing, and the step after an in-place parameter update without a refresh uploads once per module that
+    owns a handle (8 chains, 3 recurrent stacks) — through the fused encoder node (_BRANCH_STREAMS = False) and the per-module nodes on
+    branch streams (True). Shapes ragged against the 16-wide tiles."""
+    import torch
+    from latentdiffeq_amd import _lib as L
+    from latentdiffeq_amd import recurrent as R
+    from latentdiffeq_amd import train as TR
+    B, T = 20, 7
+    ts = np.arange(T) * 0.05
+    model = _model(5, input_dim=48, hidden_dim_resnet=40)
+    x = torch.rand(T, B, 48, device="cuda").permute(2, 1, 0)
+    lib = L.load()
+    names = ("lde_chain_set_weights_device", "lde_rnn_set_weights_device")
+    real = {n: getattr(lib, n) for n in names}
+    count = dict.fromkeys(names, 0)
+
+    def counting(n):
+        def shim(*args):
+            count[n] += 1
+            return real[n](*args)
+        return shim
+
+    def step():
+        for p in model.parameters():
+            p.grad = None
+        count.update(dict.fromkeys(names, 0))
+        TR.loss_batch(model, x, ts, 1e-3, True).backward()
+        torch.cuda.synchronize()
+        return count[names[0]], count[names[1]]
+
+    switch = R._BRANCH_STREAMS
+    try:
+        R._BRANCH_STREAMS = branch_streams
+        for n in names:
+            setattr(lib, n, counting(n))
+        assert step() == (8, 3)                                 # new handles hold nothing yet
+        assert model.refresh_weights() == 11
+        assert step() == (0, 0)
+        assert step() == (0, 0)                                 # … and the hand-over stays valid while the parameters do
+        with torch.no_grad():
+            for p in model.parameters():
+                p.add_(p.grad, alpha=-1e-3)
+        assert step() == (8, 3)
+        assert all(m._wkey is None for m in model.modules())
+    finally:
+        R._BRANCH_STREAMS = switch
+        for n in names:
+            setattr(lib, n, real[n])
