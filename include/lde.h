@@ -53,9 +53,13 @@ enum lde_rhs_kind {
   LDE_RHS_PENDULUM_FRICTION = 1,  /* ... - (b/m) y, b=0.7, m=1             [REF pendulum.jl:65-74] */
   LDE_RHS_MLP               = 2,  /* Chain(Dense(relu)...Dense)            [REF examples/pendulum_friction-less/nODE.jl:12-14] */
   LDE_RHS_PENDULUM_PLUS_MLP = 3,  /* pendulum(z,L) + MLP(z): BASELINE.json configs[2] */
-  LDE_RHS_SPENDULUM         = 4   /* the stochastic pendulum: dx = v dt + σ dW₁, dv = −(G/L) sin x dt + σ dW₂, G=10, L=p[1], σ=0.01 (diagonal,
+  LDE_RHS_SPENDULUM         = 4,  /* the stochastic pendulum: dx = v dt + σ dW₁, dv = −(G/L) sin x dt + σ dW₂, G=10, L=p[1], σ=0.01 (diagonal,
                                      additive, constant: Itô = Stratonovich)   [REF examples/pendulum_friction-less/pendulum.jl:93-140].
                                      Solvers LDE_SOLVER_EM / LDE_SOLVER_EULER_HEUN, LDE_SENSE_FORWARD_DUAL; see "the stochastic pendulum" below */
+  LDE_RHS_LOTKA_VOLTERRA    = 5   /* Lotka–Volterra: dx = αx − βxy, dy = −γy + δxy, θ = (α, β, γ, δ) = p[1:4] per trajectory (state_dim 2,
+                                     param_dim 4). The first right-hand side with more than one parameter — the reference's `diffeq` plug-in is
+                                     "any Julia function" [REF src/models/GOKU.jl:98-130]; this one has no file of its own there.
+                                     LDE_SENSE_FORWARD_DUAL only; see "the Lotka–Volterra system" below */
 };
 
 enum lde_solver {
@@ -112,7 +116,8 @@ enum lde_sensealg {
                                            LDE_BATCH_PER_TRAJECTORY, Tsit5 adaptive or fixed-step and RK4 fixed-step — and LDE_RHS_SPENDULUM with
                                            its two fixed-step schemes, whose only sensealg this is; any other description gives
                                            LDE_ERR_UNSUPPORTED (lde_desc_error names the missing piece). Opt-in: lde_problem_desc_default keeps
-                                           LDE_SENSE_DISCRETE. */
+                                           LDE_SENSE_DISCRETE. LDE_RHS_LOTKA_VOLTERRA runs the same solve with NP = 6 partials per component,
+                                           (x₀, y₀, α, β, γ, δ): "the Lotka–Volterra system" below. */
 };
 
 enum lde_activation { LDE_ACT_RELU = 0, LDE_ACT_TANH = 1 };
@@ -243,6 +248,22 @@ int lde_set_weights_device(lde_handle* h, const float* flat_dev, int64_t n, void
  * LDE_ERR_UNSUPPORTED on a handle of another right-hand side. */
 int lde_set_noise(lde_handle* h, uint64_t seed, uint64_t offset, uint64_t first_trajectory, const int64_t* epoch_dev);
 
+/* ---- the Lotka–Volterra system (LDE_RHS_LOTKA_VOLTERRA): dx = αx − βxy, dy = −γy + δxy ----
+ * The smallest system with more than one parameter: two states, θ = (α, β, γ, δ) per trajectory — theta [4×B], trajectory b's four values
+ * at theta[4b … 4b+3]; dtheta likewise. Polynomial: the right-hand side on dual numbers is plain f32 arithmetic,
+ *     ∂f/∂u = [[α − βy, −βx], [δy, −γ + δx]],   ∂f/∂θ = [[x, −xy, 0, 0], [0, 0, −y, xy]].
+ * Served: state_dim = 2, param_dim = 4, augment_dim = 0, n_layers = 0 (anything else: LDE_ERR_INVALID_ARG), LDE_BATCH_PER_TRAJECTORY,
+ * LDE_SOLVER_TSIT5 adaptive or fixed-step and LDE_SOLVER_RK4 fixed-step, sensealg LDE_SENSE_FORWARD_DUAL — the solve on dual numbers described
+ * at that enum value, with NP = D + P = 6 partials per component in the order (x₀, y₀, α, β, γ, δ) (seeds e₀, e₁, 0, 0, 0, 0) and all six
+ * in every norm of the step control. lde_num_weights = 0; dW must be NULL.
+ * Refused with LDE_ERR_UNSUPPORTED, lde_desc_error naming the missing piece: another sensealg ("… use LDE_SENSE_FORWARD_DUAL": the Nyström
+ * forward kernel, the discrete sweep and the continuous adjoints are written for the pendulum and do not exist for this system),
+ * LDE_BATCH_COUPLED, the stochastic steppers and adaptive RK4 (their own texts); lde_set_noise on such a handle. (LDE_BATCH_COUPLED_GLOBAL
+ * is LDE_ERR_INVALID_ARG for every right-hand side without an MLP.)
+ * The dual record has the layout below with NP = 6: J float [T][2][6][B] at A(4B), the step trace at A(4B) + A(48TB). Failure semantics,
+ * statistics, lde_step_record_* and option "step_trace" are those of the pendulum's dual solve. lde_last_kernel: "k_lv_forward_dual" /
+ * "k_lv_adjoint_dual". */
+
 /* Pre-size the handle's workspace for batches up to B and T save points (so that later
  * lde_forward/lde_adjoint calls allocate nothing and can be captured in a hipGraph). */
 int lde_reserve(lde_handle* h, int B, int T);
@@ -323,10 +344,12 @@ int lde_set_global_sum_peers(lde_handle* h, int rank, int nranks, void* const* m
  * Its size is fixed by (B, T) — it cannot overflow, and lde_step_record_status never reports an overflow for it (capacity = maxiters).
  * Layout (A(x) = x rounded up to a multiple of 256 bytes), from the 256-byte aligned base:
  *     n  int32 [B]                at 0                      accepted steps of trajectory b; −retcode when its solve failed
- *     J  float [T][2][3][B]       at A(4B)                  J[j][i][q][b] = ∂ẑ_i(t_j)/∂(x₀, v₀, L)_q of trajectory b (trajectory fastest)
- *     t  double [cap][B]          at A(4B) + A(24TB)        option "step_trace" = 1 only: start time of accepted step s of trajectory b at s·B + b
+ *     J  float [T][2][NP][B]      at A(4B)                  J[j][i][q][b] = ∂ẑ_i(t_j)/∂q of trajectory b (trajectory fastest); NP = D + P partials
+ *                                                           per component: 3, q ∈ (x₀, v₀, L), for the pendulums; 6, q ∈ (x₀, y₀, α, β, γ, δ), for
+ *                                                           LDE_RHS_LOTKA_VOLTERRA
+ *     t  double [cap][B]          at A(4B) + A(4·2·NP·TB)   option "step_trace" = 1 only: start time of accepted step s of trajectory b at s·B + b
  *     dt double [cap][B]          at … + A(8·cap·B)         … and its size; cap = lde_step_record_capacity(h, T)
- * J of a failed trajectory is zero. With "step_trace" = 1 lde_get_step_record(h, 0, …) returns the accepted steps (what a checker replays). */
+ * (Pendulums: J [T][2][3][B], the trace at A(4B) + A(24TB), as before.) J of a failed trajectory is zero. With "step_trace" = 1 lde_get_step_record(h, 0, …) returns the accepted steps (what a checker replays). */
 int64_t lde_step_record_bytes(const lde_handle* h, int B, int T);
 int lde_set_step_record(lde_handle* h, void* rec_dev, int64_t bytes);
 /* Did the record hold the solve? lde_step_record_capacity(h, T) = the accepted steps per sequence a record made now would hold;

@@ -9,6 +9,7 @@ include/lde.h. PyTorch is used only for device memory, streams and autograd plum
     Pendulum(; solver, sensalg, kwargs...)    [REF pendulum.jl:4-46]   Pendulum(solver=, sensalg=, **kwargs)
     Pendulum_friction(...)                    [REF pendulum.jl:50-91]  Pendulum_friction(...)
     SPendulum(; solver, sensalg, kwargs...)   [REF pendulum.jl:93-140] SPendulum(solver=EulerHeun(), sensalg=, dt=, seed=, **kwargs)
+    (a plug-in struct of one's own: "any Julia function")              LotkaVolterra(solver=Tsit5(), **kwargs)  — LDE_RHS_LOTKA_VOLTERRA
     NODE(latent_dim_in; hidden_dim, augment_dim, kwargs...) [REF nODE.jl:3-32]   NODE(latent_dim_in, hidden_dim=, augment_dim=, **kwargs)
     GOKU_basic(), LatentODE()                 [REF GOKU.jl:6-7], [REF LatentODE.jl:6]   same
     Decoder(model_type, (latent_out, diffeq, reconstructor)) [REF LatentDiffEqModel.jl:79-99]   same
@@ -100,7 +101,7 @@ class ForwardDiffSensitivity(DiscreteSensitivity):
 
     `dual_norm=True` (opt-in; LDE_SENSE_FORWARD_DUAL): the solve on dual numbers as upstream runs it during training — the error norm sees
     the partials, so the accepted steps are the reference's training-time ones, not the primal solve's. The forward pass carries the
-    Jacobians ∂ẑ(t_j)/∂(ẑ₀, θ̂) and the pullback contracts them. Analytic right-hand sides (Pendulum, Pendulum_friction) only."""
+    Jacobians ∂ẑ(t_j)/∂(ẑ₀, θ̂) and the pullback contracts them. Analytic right-hand sides (Pendulum, Pendulum_friction, LotkaVolterra) only."""
 
     def __init__(self, exact: bool = True, dual_norm: bool = False):
         self.dual_norm = bool(dual_norm)
@@ -270,6 +271,28 @@ class SPendulum(_PhysicsDiffEq):
         nz = (self.seed, self.offset, int(self.first_trajectory), self.epoch)
         self.offset += 1
         return nz
+
+
+class LotkaVolterra(_PhysicsDiffEq):
+    """Lotka–Volterra, du = [αx − βxy, −γy + δxy], p = (α, β, γ, δ) — LDE_RHS_LOTKA_VOLTERRA (include/lde.h: "the Lotka–Volterra system").
+    The first plug-in with more than one parameter: `prob.u0` has two entries and `prob.p` four, so `default_layers` builds a four-wide
+    `lo_θ` (softplus: θ̂ > 0); diffeq_layer takes θ̂ [4, B] and autograd returns dθ̂ [4, B].
+
+    Served on the dual-number path only: the struct carries `ForwardDiffSensitivity(dual_norm=True)` (LDE_SENSE_FORWARD_DUAL, what the
+    reference executes in training), Tsit5 adaptive or fixed-step and RK4 fixed-step. Another sensealg is refused by the library, with
+    its text ("… use LDE_SENSE_FORWARD_DUAL"): no discrete sweep and no continuous adjoint exist for this system."""
+    _rhs_kind = L.RHS_LOTKA_VOLTERRA
+
+    def __init__(self, solver=None, sensalg=None, sensealg=None, **kwargs):
+        sa = sensealg if sensealg is not None else sensalg
+        super().__init__(solver=solver, sensealg=sa if sa is not None else ForwardDiffSensitivity(dual_norm=True), **kwargs)
+        self.prob = _ODEProblemStub(np.array([1.0, 1.0], np.float32), np.array([1.0, 1.0, 1.0, 1.0], np.float32), (0.0, 1.0))
+
+    def _native(self) -> _Handle:
+        if self._handle is None:
+            d = _make_desc(self._rhs_kind, 2, 4, 0, (), self.solver, self.sensealg, L.BATCH_PER_TRAJECTORY, self.kwargs)
+            self._handle = _Handle(d)
+        return self._handle
 
 
 def _set_noise(handle: _Handle, nz):

@@ -36,6 +36,10 @@ int launch_pend_adjoint_dual(const DualRec& rec, const float* dz_out, int T, int
 int launch_pend_forward_sde(int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o, const DualRec& rec,
                             const SdeNoise& nz, bool over, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej,
                             int32_t* ret, hipStream_t stream);
+int launch_lv_forward_dual(int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o, const DualRec& rec,
+                           float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
+int launch_lv_adjoint_dual(const DualRec& rec, const float* dz_out, int T, int B, float* dz0, float* dtheta, int32_t* nfe, int32_t* nacc,
+                           int32_t* nrej, int32_t* ret, hipStream_t stream);
 struct MlpPlan;
 int mlp_plan_create(const lde_problem_desc& d, MlpPlan** out, std::string& err);
 void mlp_plan_destroy(MlpPlan* p);
@@ -96,7 +100,7 @@ struct lde_handle {
   std::string err = "";
 };
 
-using namespace lde_host;   // validate, has_mlp, has_pend, is_sde, sde_plan, rec_nseq, rec_capacity, rec_bytes, rec_view, align256, make_opts, num_weights, grid_ok, fixed_step_count
+using namespace lde_host;   // validate, has_mlp, has_pend, is_sde, is_lv, dual_partials, sde_plan, rec_nseq, rec_capacity, rec_bytes, rec_view, align256, make_opts, num_weights, grid_ok, fixed_step_count
 static int rec_capacity(const lde_handle* h, int T, int which);
 
 #define HIP_TRY(h, expr)                                                                   \
@@ -289,11 +293,12 @@ static int rec_prepare(lde_handle* h, int which, int B, int T, lde::StepRec* out
   return LDE_OK;
 }
 
-// LDE_SENSE_FORWARD_DUAL: the dual record of a call of shape (B, T) (lde_host.h: dual_rec_view) — the caller's block if one was handed over,
-// else the handle's own (rec_own[0]), grown here. `trace`: with the accepted steps (option "step_trace").
+// LDE_SENSE_FORWARD_DUAL: the dual record of a call of shape (B, T) (lde_host.h: dual_rec_view, with the right-hand side's partials per
+// component) — the caller's block if one was handed over, else the handle's own (rec_own[0]), grown here. `trace`: with the accepted steps
+// (option "step_trace").
 static int dual_prepare(lde_handle* h, int B, int T, bool trace, lde::DualRec* out) {
   const int cap = rec_capacity(h, T, 0);
-  const size_t need = dual_rec_bytes(B, T, cap, trace);
+  const size_t need = dual_rec_bytes(B, T, cap, trace, dual_partials(h->d));
   void* base = nullptr;
   if (h->rec_user) {
     if (h->rec_user_bytes < need) {
@@ -315,7 +320,7 @@ static int dual_prepare(lde_handle* h, int B, int T, bool trace, lde::DualRec* o
     }
     base = h->rec_own[0];
   }
-  *out = dual_rec_view(base, B, T, cap, trace);
+  *out = dual_rec_view(base, B, T, cap, trace, dual_partials(h->d));
   return LDE_OK;
 }
 
@@ -417,6 +422,9 @@ int lde_forward(lde_handle* h, const float* z0, const float* theta, const double
       rc = lde::launch_pend_forward_sde(h->d.solver, z0, theta, h->ts_dev, o, r, h->noise, sde_plan(h->d, ts, T).over, z_out, retcode, st[0],
                                         st[1], st[2], st[3], stream);
       h->last_kernel[0] = "k_pend_forward_sde";
+    } else if (is_lv(h->d)) {   // Lotka–Volterra: six partials per component, kernels and dispatch of its own (csrc/lde_lv_dual.hip)
+      rc = lde::launch_lv_forward_dual(h->d.solver, z0, theta, h->ts_dev, o, r, z_out, retcode, st[0], st[1], st[2], st[3], stream);
+      h->last_kernel[0] = "k_lv_forward_dual";
     } else {
       rc = lde::launch_pend_forward_dual(h->d.rhs_kind, h->d.solver, z0, theta, h->ts_dev, o, r, z_out, retcode, st[0], st[1], st[2], st[3],
                                          stream);
@@ -483,8 +491,13 @@ int lde_adjoint(lde_handle* h, const float* z_out, const float* theta, const dou
       }
       r = h->dual_last;
     }
-    rc = lde::launch_pend_adjoint_dual(r, dz_out, T, B, dz0, dtheta, st[0], st[1], st[2], st[3], stream);
-    h->last_kernel[1] = "k_pend_adjoint_dual";
+    if (is_lv(h->d)) {
+      rc = lde::launch_lv_adjoint_dual(r, dz_out, T, B, dz0, dtheta, st[0], st[1], st[2], st[3], stream);
+      h->last_kernel[1] = "k_lv_adjoint_dual";
+    } else {
+      rc = lde::launch_pend_adjoint_dual(r, dz_out, T, B, dz0, dtheta, st[0], st[1], st[2], st[3], stream);
+      h->last_kernel[1] = "k_pend_adjoint_dual";
+    }
     if (rc) h->err = "lde_adjoint: kernel launch failed";
     return rc;
   }
@@ -585,7 +598,7 @@ int lde_set_global_sum_peers(lde_handle* h, int rank, int nranks, void* const* m
 
 int64_t lde_step_record_bytes(const lde_handle* h, int B, int T) {
   if (!h || B < 1 || T < 1) return 0;
-  if (h->d.sensealg == LDE_SENSE_FORWARD_DUAL) return (int64_t)dual_rec_bytes(B, T, rec_capacity(h, T, 0), h->opt_step_trace != 0);
+  if (h->d.sensealg == LDE_SENSE_FORWARD_DUAL) return (int64_t)dual_rec_bytes(B, T, rec_capacity(h, T, 0), h->opt_step_trace != 0, dual_partials(h->d));
   return (int64_t)rec_bytes(h->d, B, rec_capacity(h, T, 0), true);
 }
 

@@ -22,7 +22,8 @@ using lde::DualRec;
 static bool has_mlp(const lde_problem_desc& d) {
   return d.rhs_kind == LDE_RHS_MLP || d.rhs_kind == LDE_RHS_PENDULUM_PLUS_MLP;
 }
-static bool has_pend(const lde_problem_desc& d) { return d.rhs_kind != LDE_RHS_MLP; }
+static bool is_lv(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_LOTKA_VOLTERRA; }
+static bool has_pend(const lde_problem_desc& d) { return d.rhs_kind != LDE_RHS_MLP && !is_lv(d); }
 static bool is_sde(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_SPENDULUM; }
 static bool sde_solver(int solver) { return solver == LDE_SOLVER_EM || solver == LDE_SOLVER_EULER_HEUN; }
 
@@ -33,10 +34,12 @@ static int validate(const lde_problem_desc* d, std::string* why) {
   };
   if (!d) return bad("desc is NULL");
   if (d->abi_version != LDE_ABI_VERSION) return bad("abi_version mismatch");
-  if (d->rhs_kind < 0 || d->rhs_kind > LDE_RHS_SPENDULUM) return bad("unknown rhs_kind");
+  if (d->rhs_kind < 0 || d->rhs_kind > LDE_RHS_LOTKA_VOLTERRA) return bad("unknown rhs_kind");
   if (d->state_dim < 1 || d->param_dim < 0 || d->augment_dim < 0) return bad("bad dims");
   if (has_pend(*d) && (d->state_dim != 2 || d->param_dim != 1 || d->augment_dim != 0))
     return bad("pendulum RHS needs state_dim=2, param_dim=1, augment_dim=0");
+  if (is_lv(*d) && (d->state_dim != 2 || d->param_dim != 4 || d->augment_dim != 0))
+    return bad("LDE_RHS_LOTKA_VOLTERRA needs state_dim=2, param_dim=4, augment_dim=0");
   if (d->rhs_kind == LDE_RHS_MLP && d->param_dim != 0) return bad("MLP RHS takes no per-trajectory parameters");
   if (has_mlp(*d)) {
     if (d->n_layers < 1 || d->n_layers > LDE_MAX_LAYERS) return bad("n_layers out of range");
@@ -47,6 +50,7 @@ static int validate(const lde_problem_desc* d, std::string* why) {
     if (d->activation != LDE_ACT_RELU && d->activation != LDE_ACT_TANH) return bad("unknown activation");
   }
   if (is_sde(*d) && d->n_layers != 0) return bad("LDE_RHS_SPENDULUM is analytic: n_layers must be 0");
+  if (is_lv(*d) && d->n_layers != 0) return bad("LDE_RHS_LOTKA_VOLTERRA is analytic: n_layers must be 0");
   if (d->solver != LDE_SOLVER_TSIT5 && d->solver != LDE_SOLVER_RK4 && !sde_solver(d->solver)) return bad("unknown solver");
   if (d->batching != LDE_BATCH_PER_TRAJECTORY && d->batching != LDE_BATCH_COUPLED && d->batching != LDE_BATCH_COUPLED_GLOBAL)
     return bad("unknown batching");
@@ -69,6 +73,13 @@ static int validate(const lde_problem_desc* d, std::string* why) {
     if (!(d->dt > 0) || !std::isfinite(d->dt)) return unsupported("LDE_RHS_SPENDULUM: fixed step only; pass a finite dt > 0");
     if (d->sensealg != LDE_SENSE_FORWARD_DUAL)
       return unsupported("LDE_RHS_SPENDULUM: the gradient is the scheme's exact derivative along the drawn path; use LDE_SENSE_FORWARD_DUAL");
+  }
+  // Lotka–Volterra is served on the dual-number path and nowhere else: the Nyström forward kernel, the discrete sweep and the continuous
+  // adjoints are written for the pendulum (include/lde.h: "the Lotka–Volterra system")
+  if (is_lv(*d)) {
+    if (d->batching != LDE_BATCH_PER_TRAJECTORY) return unsupported("LDE_RHS_LOTKA_VOLTERRA: no coupled solve; LDE_BATCH_PER_TRAJECTORY only");
+    if (d->sensealg != LDE_SENSE_FORWARD_DUAL)
+      return unsupported("LDE_RHS_LOTKA_VOLTERRA: only the solve on dual numbers exists for this system (no discrete sweep, no continuous adjoint); use LDE_SENSE_FORWARD_DUAL");
   }
   if (d->solver == LDE_SOLVER_RK4 && d->adaptive) {
     if (why) *why = "RK4 is fixed-step only here: pass adaptive=0, dt=h";
@@ -118,21 +129,25 @@ static StepRec rec_view(const lde_problem_desc& d, void* base, int B, int cap, b
   return r;
 }
 
-// LDE_SENSE_FORWARD_DUAL's record (include/lde.h: "the dual record"): n [B] | J [T][2][3][B] f32 | with the step trace t, dt [cap][B] f64.
+// LDE_SENSE_FORWARD_DUAL's record (include/lde.h: "the dual record"): n [B] | J [T][2][NP][B] f32 | with the step trace t, dt [cap][B] f64;
+// `np` = NP = D + P partials per component — 3 for the pendulums (the four-argument forms), 6 for Lotka–Volterra (dual_partials).
 // J first: its place depends on B alone, so the pullback (which reads n and J) finds it whether or not the forward traced its steps.
-static size_t dual_rec_bytes(int B, int T, int cap, bool trace) {
-  return align256((size_t)B * 4) + align256((size_t)T * 6 * B * 4) + (trace ? 2 * align256((size_t)cap * B * 8) : 0);
+static int dual_partials(const lde_problem_desc& d) { return is_lv(d) ? 6 : 3; }
+static size_t dual_rec_bytes(int B, int T, int cap, bool trace, int np) {
+  return align256((size_t)B * 4) + align256((size_t)T * 2 * np * B * 4) + (trace ? 2 * align256((size_t)cap * B * 8) : 0);
 }
-static DualRec dual_rec_view(void* base, int B, int T, int cap, bool trace) {
+static DualRec dual_rec_view(void* base, int B, int T, int cap, bool trace, int np) {
   DualRec r{};
   unsigned char* p = (unsigned char*)base;
   r.n = (int32_t*)p; p += align256((size_t)B * 4);
-  r.J = (float*)p; p += align256((size_t)T * 6 * B * 4);
+  r.J = (float*)p; p += align256((size_t)T * 2 * np * B * 4);
   r.t = trace ? (double*)p : nullptr; p += trace ? align256((size_t)cap * B * 8) : 0;
   r.dt = trace ? (double*)p : nullptr;
   r.cap = trace ? cap : 0;
   return r;
 }
+static size_t dual_rec_bytes(int B, int T, int cap, bool trace) { return dual_rec_bytes(B, T, cap, trace, 3); }
+static DualRec dual_rec_view(void* base, int B, int T, int cap, bool trace) { return dual_rec_view(base, B, T, cap, trace, 3); }
 
 // Number of floats in the flat weight vector implied by desc (0 for analytic right-hand sides; n_layers clamped to the struct's capacity)
 static int64_t num_weights(const lde_problem_desc* d) {
@@ -248,6 +263,17 @@ template <class F>
 static int pend_dispatch(int kind, int solver, bool adaptive, F&& f) {
   if (kind == LDE_RHS_PENDULUM) return pend_dispatch_solver<LDE_RHS_PENDULUM>(solver, adaptive, f);
   if (kind == LDE_RHS_PENDULUM_FRICTION) return pend_dispatch_solver<LDE_RHS_PENDULUM_FRICTION>(solver, adaptive, f);
+  return LDE_ERR_UNSUPPORTED;
+}
+
+// The template arguments of the Lotka–Volterra kernels (csrc/lde_lv_dual.hip): calls f(SOLVER) with a std::integral_constant for exactly the
+// three (solver, adaptive) combinations validate() admits for LDE_RHS_LOTKA_VOLTERRA — Tsit5 adaptive, Tsit5 fixed-step, RK4 fixed-step (the
+// kernel reads `adaptive` at run time) — and returns what f returns; anything else is LDE_ERR_UNSUPPORTED. A dispatch of its own:
+// pend_dispatch serves the pendulums' six combinations and nothing else.
+template <class F>
+static int lv_dispatch(int solver, bool adaptive, F&& f) {
+  if (solver == LDE_SOLVER_TSIT5) return f(std::integral_constant<int, LDE_SOLVER_TSIT5>{});
+  if (solver == LDE_SOLVER_RK4 && !adaptive) return f(std::integral_constant<int, LDE_SOLVER_RK4>{});
   return LDE_ERR_UNSUPPORTED;
 }
 

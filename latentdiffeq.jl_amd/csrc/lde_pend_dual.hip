@@ -10,83 +10,16 @@
 // slopes of it — every stage's sin x and cos x from ONE hw_sincos on the step's turn anchor (as PendBwd), ∂f/∂L = (G/L²)·sin x on the L column.
 // The stage sums, the solution weights and the interpolant are lde_device.h's (tsit5_attempt / rk4_step / tsit5_dense_* on an 8-vector); what
 // decides the steps — the dual norms, their squares, the RMS (accumulated in f64 as the oracle does) and the Hairer initial step — follows the
-// oracle's order of operations. ẑ goes to z_out [T×B×2] as lde_forward's other kernels write it; J_j = ∂ẑ(t_j)/∂(x₀, v₀, L) to the dual
+// oracle's order of operations (csrc/lde_dual.h, shared with the Lotka–Volterra kernel: NP = 3 partials per component here).
+// ẑ goes to z_out [T×B×2] as lde_forward's other kernels write it; J_j = ∂ẑ(t_j)/∂(x₀, v₀, L) to the dual
 // record, trajectory fastest (lde_types.h: DualRec), so that a wave's 64 lanes write — and the pullback's read — 256 consecutive bytes.
 // k_pend_adjoint_dual: dz0 = Σ_j J_j[:, 0:2]ᵀ dz_out_j, dθ = Σ_j J_j[:, 2]ᵀ dz_out_j, summed j outer, i inner in f32 (the oracle's order).
 #include "lde_device.h"
+#include "lde_dual.h"
 #include "lde_host.h"
 #include "lde_pend_dualrhs.h"
 
 namespace lde {
-
-namespace {
-
-// ‖u_i‖ of component i (0: x, 1: v) as ODE_DEFAULT_NORM takes it on a dual: sqrt(v² + Σ_q p_q²), the squares added in the oracle's order, unfused
-__device__ __forceinline__ float dual_abs(const float (&u)[DN], int i) {
-#pragma clang fp contract(off)
-  float s2 = u[i] * u[i];
-#pragma unroll
-  for (int q = 0; q < 3; q++) s2 += u[2 + 3 * i + q] * u[2 + 3 * i + q];
-  return sqrtf(s2);
-}
-
-// RMS over the two components of ‖e_i‖ / sk_i: each ratio and its square in f32, the sum of squares and the root in f64 (oracle: dual_rms)
-__device__ __forceinline__ double dual_rms(const float (&e)[DN], const float (&sk)[2]) {
-#pragma clang fp contract(off)
-  double s2 = 0.0;
-#pragma unroll
-  for (int i = 0; i < 2; i++) {
-    const float r = dual_abs(e, i) / sk[i];
-    s2 += (double)(r * r);
-  }
-  return sqrt(s2 / 2.0);
-}
-
-// Hairer–Nørsett–Wanner initial step with every norm the dual norm; f0 = f(y0) given (oracle: dual_solve's initial step)
-template <class F>
-__device__ __forceinline__ double dual_init_dt(F& f, const float (&y)[DN], const float (&f0)[DN], double dtmax, const KOpts& o) {
-  float sk[2];
-  {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int i = 0; i < 2; i++) sk[i] = o.abstol + dual_abs(y, i) * o.reltol;
-  }
-  const double d0 = dual_rms(y, sk), d1 = dual_rms(f0, sk);
-  double dt0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-  if (dt0 > dtmax) dt0 = dtmax;
-  const float h = (float)dt0;
-  float tmp[DN], f1[DN];
-#pragma unroll
-  for (int c = 0; c < DN; c++) tmp[c] = y[c] + h * f0[c];
-  f(tmp, f1);
-#pragma unroll
-  for (int c = 0; c < DN; c++) f1[c] -= f0[c];
-  const double d2 = dual_rms(f1, sk) / dt0, dm = d1 > d2 ? d1 : d2;
-  const double dt1 = (dm <= 1e-15) ? fmax(1e-6, dt0 * 1e-3) : pow(10.0, -(2.0 + log10(dm)) / 5.0);
-  const double dt = fmin(100.0 * dt0, dt1);
-  return dt > dtmax ? dtmax : dt;
-}
-
-// EEst of a Tsit5 attempt on duals: e = h·Σ_j b̃_j k_j per component, scale abstol + reltol·max(‖y_i‖, ‖y_new,i‖), RMS of ‖e_i‖ / scale
-__device__ __forceinline__ float dual_eest(float h, const float (&y)[DN], const float (&yn)[DN], const float (&k)[7][DN], const KOpts& o) {
-  float e[DN];
-#pragma unroll
-  for (int c = 0; c < DN; c++) {
-    float a = ts5::BT[0] * k[0][c];
-#pragma unroll
-    for (int j = 1; j < 7; j++) a += ts5::BT[j] * k[j][c];
-    e[c] = a * h;
-  }
-  float sk[2];
-  {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int i = 0; i < 2; i++) sk[i] = o.abstol + fmaxf(dual_abs(y, i), dual_abs(yn, i)) * o.reltol;
-  }
-  return (float)dual_rms(e, sk);
-}
-
-}  // namespace
 
 template <int KIND, int SOLVER, bool TS_LDS>
 __global__ void __launch_bounds__(256) k_pend_forward_dual(const float2* __restrict__ z0, const float* __restrict__ theta,
@@ -128,7 +61,7 @@ __global__ void __launch_bounds__(256) k_pend_forward_dual(const float2* __restr
     if (!o.adaptive) dt = o.dt_fixed;
     else if (o.dt_fixed > 0) dt = fmin(o.dt_fixed, dtmax);
     else {
-      dt = dual_init_dt(f, y, k[0], dtmax, o);
+      dt = dual_init_dt<3>(f, y, k[0], dtmax, o);
       nfe++;
     }
     float qold = 1e-4f;
@@ -145,7 +78,7 @@ __global__ void __launch_bounds__(256) k_pend_forward_dual(const float2* __restr
       f.anchor(y[0]);
       if (SOLVER == LDE_SOLVER_TSIT5) {
         tsit5_attempt<DN, PendDual<KIND>, false, 0>(f, h, y, k, yn, o);
-        if (o.adaptive) EEst = dual_eest(h, y, yn, k, o);
+        if (o.adaptive) EEst = dual_eest<3>(h, y, yn, k, o);
         nfe += 6;
       } else {
         rk4_step<DN>(f, h, y, k, yn);

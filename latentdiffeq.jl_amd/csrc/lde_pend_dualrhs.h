@@ -3,11 +3,11 @@
 // (csrc/lde_pend_sde.hip: the stochastic pendulum's drift; its additive noise has zero partials).
 #pragma once
 #include "lde_device.h"
+#include "lde_dual.h"   // DUAL_TS_LDS_MAX
 
 namespace lde {
 
 constexpr int DN = 8;                 // [x, v, ∂x/∂x₀, ∂x/∂v₀, ∂x/∂L, ∂v/∂x₀, ∂v/∂v₀, ∂v/∂L]
-constexpr int DUAL_TS_LDS_MAX = 6000;   // doubles of the save-time grid kept in LDS (48 KB)
 
 // du = [v, −(G/L) sin x (− (b/m) v)] on duals: ∂f/∂u = [[0, 1], [−(G/L) cos x, (−b/m)]], ∂f/∂L = [0, (G/L²) sin x]
 template <int KIND>

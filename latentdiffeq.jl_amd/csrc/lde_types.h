@@ -23,9 +23,11 @@ struct StepRec {
 
 // LDE_SENSE_FORWARD_DUAL's record in device memory (include/lde.h: lde_set_step_record): written by k_pend_forward_dual, read by
 // k_pend_adjoint_dual. J holds ∂ẑ(t_j)/∂(x₀, v₀, L) of every save time, trajectory fastest: element (j, i, q, b) at ((j·2 + i)·3 + q)·B + b.
+// The Lotka–Volterra kernels (csrc/lde_lv_dual.hip) use the same view with NP = 6 partials per component, a compile-time constant of
+// theirs: J [T][2][6][B], element (j, i, q, b) at ((j·2 + i)·6 + q)·B + b. No field says which: the pendulum kernels read none.
 struct DualRec {
   int32_t* n;    // [B] accepted steps; −retcode for a failed trajectory
-  float* J;      // [T][2][3][B]
+  float* J;      // [T][2][NP][B]
   double* t;     // [cap][B] start time of accepted step n (option "step_trace"; nullptr otherwise)
   double* dt;    // [cap][B] its size
   int cap;       // 0 without the trace
