@@ -696,6 +696,26 @@ int lde_adamw_flux_step(int n, const lde_adam_tensor* t, float lr, float beta1, 
  * [REF examples/pendulum_friction-less/model_train.jl:186-204: the loop the graph replaces]. */
 int lde_adamw_flux_step_dev(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps, float decay,
                             int64_t* step_dev, void* stream);
+/* The guarded step: lde_adamw_flux_step_dev behind a scan of every gradient. A captured training step cannot look at its solve from the
+ * host; a step record that overflows at some replay (lde_adjoint then returns all-NaN gradients, never a truncated sweep), a trajectory
+ * that fails at maxiters or an overflow in a bf16 chain would write NaN into every parameter and both moments, for ever. The call first
+ * scans every t[i].g and then does exactly what lde_adamw_flux_step_dev does, or nothing: if ANY gradient element of ANY array is
+ * non-finite (exponent bits all ones: NaN of any sign or payload, ±Inf; denormals, ±0 and ±FLT_MAX are finite) no p, m, v of any array is
+ * touched and *step_dev is not advanced; otherwise p, m, v and *step_dev end bit-identical to lde_adamw_flux_step_dev on the same
+ * arguments. Two phases with a kernel boundary between them (all scan launches, then all update launches); no launch waits for another
+ * workgroup. The step count doubles as the noise epoch of a captured step's ε (loss.set_noise_epoch): a withheld step leaves the epoch
+ * where it was — the replay after it draws the ε the withheld one drew.
+ * guard_dev: LDE_GUARD_WORDS device int64, owned by the caller, initialised once by lde_guard_init:
+ *   [0] in flight: lowest index (in the caller's t[] order) of an array whose gradient holds a non-finite value in the step being taken;
+ *       −1 = clean. Always −1 between steps: the step's last kernel puts it back, so a hipGraph replay needs no reset from the host.
+ *   [1] skipped: updates withheld so far            [2] streak: consecutive withheld updates (0 after an applied one)
+ *   [3] last_bad_array: [0]'s value at the most recent withheld update; −1 = never
+ * Both calls return LDE_ERR_INVALID_ARG for a NULL step_dev / guard_dev and for what lde_adamw_flux_step_dev refuses, before any device
+ * call. A clean step over empty arrays only ticks the count, as the unguarded call does. */
+#define LDE_GUARD_WORDS 4
+int lde_guard_init(int64_t* guard_dev, void* stream);
+int lde_adamw_flux_step_guarded(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps, float decay,
+                                int64_t* step_dev, int64_t* guard_dev, void* stream);
 
 /* ====================================================================================================================
  * The one collective of the path. The reference's only parallelism is `EnsembleThreads()` over the

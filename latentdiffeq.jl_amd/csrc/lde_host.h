@@ -752,6 +752,49 @@ static int rnn_dispatch(int cell, int mode, F&& f) {
   return LDE_ERR_UNSUPPORTED;
 }
 
+// ---- the parameter update (csrc/lde_optim.hip's launch code asks this): which arrays of the caller's t[] travel in which
+// launch. A launch carries at most OPT_MAXT NON-EMPTY arrays (its kernel-argument table) and at most 2³⁰ − 1 workgroups; a workgroup owns
+// `per_wg` consecutive elements of one array. The update (OPT_PER_WG) and the gradient scan of the guarded step (GUARD_PER_WG: it moves
+// 4 bytes per element where the update moves 28) both walk t[] with this function, each with its own slice.
+constexpr int OPT_WG = 256;
+constexpr int OPT_PER_WG = 8 * OPT_WG;      // the update: two 16-byte accesses per lane and array
+constexpr int GUARD_PER_WG = 32 * OPT_WG;   // the scan: eight 16-byte loads per lane, 32 KiB per workgroup — the default GOKU model (2 MB of
+                                            // gradients) is 70 workgroups where the update has 252. Measured (abl/guard_time.py):
+                                            // at that size a larger slice only lengthens the one workgroup everything waits for — the scan adds
+                                            // 3.4 µs at 8 192, 3.7 at 16 384, 4.2 at 32 768, 5.2 at 65 536; at 2²⁶ floats the slice does not matter
+constexpr int OPT_MAXT = 48;                // arrays per launch (kernel-argument table: 48 × 40 B)
+constexpr int OPT_MAX_BLOCKS = 0x3fffffff;
+struct OptLaunch {
+  int n;                     // non-empty arrays in this launch (0: nothing left to launch)
+  int idx[OPT_MAXT];         // their indices in the caller's t[]
+  int blk0[OPT_MAXT + 1];    // first workgroup of each; blk0[n] = the grid
+  int next;                  // where the following launch starts in t[]
+  bool last;                 // no array after `next` has elements: the step's last launch
+  bool too_large;            // n == 0 because t[next] alone needs more than OPT_MAX_BLOCKS workgroups (the caller refuses the call)
+};
+static OptLaunch opt_next_launch(int n, const lde_adam_tensor* t, int first, int per_wg) {
+  OptLaunch L{};
+  int blk = 0;
+  while (first < n && L.n < OPT_MAXT) {
+    if (t[first].n > 0) {
+      const int64_t nb = (t[first].n - 1) / per_wg + 1;
+      if (nb > OPT_MAX_BLOCKS - blk) break;   // next launch
+      L.idx[L.n] = first;
+      L.blk0[L.n] = blk;
+      blk += (int)nb;
+      L.n++;
+    }
+    first++;
+  }
+  L.blk0[L.n] = blk;
+  L.next = first;
+  L.too_large = L.n == 0 && first < n;
+  bool more = false;   // another launch follows? (only the step's last one advances the count)
+  for (int j = first; j < n; j++) more = more || t[j].n > 0;
+  L.last = !more;
+  return L;
+}
+
 static KOpts make_opts(const lde_problem_desc& d, const double* ts, int T, int B) {
   KOpts o;
   o.abstol = (float)d.abstol;

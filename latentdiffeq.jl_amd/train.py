@@ -17,6 +17,7 @@ no kernel of its own.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Callable, Iterable, List, Optional, Sequence
 
@@ -146,10 +147,17 @@ class FluxADAMW(torch.optim.Adam):
     point (same arithmetic up to rounding; tests/test_gpu_optim.py compares the two). The native path bumps the parameters'
     version counters after its launch (it writes through raw pointers), so `refresh_weights()` is optional after it too. Its
     optimiser state keeps `step` as a Python int (a tensor step from a torch checkpoint is converted on entry); a native
-    state_dict is therefore not resumable by torch's FUSED Adam, which expects tensor steps."""
+    state_dict is therefore not resumable by torch's FUSED Adam, which expects tensor steps.
+    `guard=True` (needs `capturable=True`): the step is lde_adamw_flux_step_guarded — every gradient is scanned on the device first, and
+    if any element of any array is NaN or ±Inf the whole update is withheld: no parameter, no moment and not the step count change (the
+    count is also the noise epoch of a captured step: the next replay draws the ε the withheld one drew). Otherwise the update is the
+    unguarded one bit for bit. `guard_state()` reads the counters. Several GPUs: the gradient all-reduce sits before the optimiser half,
+    and a sum with a NaN is NaN on every rank — all ranks withhold the same step; nothing is exchanged for it."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), decay: float = 0.0, eps: float = 1e-8, fused=None, native=None,
-                 capturable: bool = False):
+                 capturable: bool = False, guard: bool = False):
+        if guard and not capturable:
+            raise ValueError("FluxADAMW(guard=True) needs capturable=True (the guard is part of the device-counted step)")
         groups = list(params)
         params = [p for g in groups for p in (g["params"] if isinstance(g, dict) else [g])]     # (arrays, or torch's group dicts)
         on_gpu = bool(params) and all(p.is_cuda for p in params)
@@ -175,6 +183,37 @@ class FluxADAMW(torch.optim.Adam):
                 raise ValueError("FluxADAMW(capturable=True) takes ONE parameter group")
             from .loss import set_noise_epoch
             set_noise_epoch(self._step_dev)     # a captured step's ε is keyed by this counter: fresh noise at every replay (loss.randn)
+        # guard: LDE_GUARD_WORDS device words (in flight, skipped, streak, last_bad_array), initialised once; the kernels keep them
+        self.guard = bool(guard)
+        self._guard_dev = None
+        if self.guard:
+            self._guard_dev = torch.empty(L.GUARD_WORDS, dtype=torch.int64, device=params[0].device)
+            L.call("lde_guard_init", None, L.ptr(self._guard_dev), L.raw_stream(params[0].device.index))
+
+    def guard_state(self) -> dict:
+        """dict(skipped, streak, last_bad_array) of the guarded step (include/lde.h: "the guarded step"): updates withheld so far,
+        consecutive ones up to now, and the index — in the parameter group's order — of the lowest array with a non-finite gradient at the
+        most recent withheld update (−1: never). Read-only. ONE device→host copy: a synchronisation with the device; not for every step
+        (GraphedStep looks every `check_every` replays). The counters are not part of `state_dict()`."""
+        if not self.guard:
+            raise ValueError("FluxADAMW.guard_state() needs guard=True")
+        w = self._guard_dev.tolist()
+        return dict(skipped=int(w[1]), streak=int(w[2]), last_bad_array=int(w[3]))
+
+    @contextlib.contextmanager
+    def withheld(self):
+        """Inside the block ONE `step()` of the guarded form is withheld whatever its gradients hold, and the counters are put back at the
+        end: a whole training step can be run for what it does to the workspaces (GraphedStep.recover: the step record regrows) while the
+        parameters, the moments, the step count and `guard_state()` stay what they were. Word [0] is raised by hand — the kernels see a
+        scan that found something — and is −1 again after the step, as always."""
+        if not self.guard:
+            raise ValueError("FluxADAMW.withheld() needs guard=True")
+        keep = self._guard_dev.clone()
+        self._guard_dev[0:1].fill_(0)
+        try:
+            yield
+        finally:
+            self._guard_dev.copy_(keep)
 
     def add_param_group(self, param_group):
         if getattr(self, "capturable", False) and self.param_groups:
@@ -218,8 +257,12 @@ class FluxADAMW(torch.optim.Adam):
                         keep.append(gr)
                     t = tab[i]
                     t.p, t.g, t.m, t.v, t.n = p.data_ptr(), gr.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
-                L.call("lde_adamw_flux_step_dev", None, len(ps), tab, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.decay,
-                       L.ptr(self._step_dev), L.raw_stream(ps[0].device.index))
+                if self.guard:
+                    L.call("lde_adamw_flux_step_guarded", None, len(ps), tab, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.decay,
+                           L.ptr(self._step_dev), L.ptr(self._guard_dev), L.raw_stream(ps[0].device.index))
+                else:
+                    L.call("lde_adamw_flux_step_dev", None, len(ps), tab, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.decay,
+                           L.ptr(self._step_dev), L.raw_stream(ps[0].device.index))
                 torch.autograd.graph.increment_version(ps)
             return
         for g in self.param_groups:
@@ -285,26 +328,50 @@ class GraphedStep:
     Several GPUs: the collective stays OUTSIDE the graphs — pass the step in two halves: `fn` = zero_grad, forward, loss, backward;
     `between` = the gradient all-reduce (dist.FlatGradAllReduce: eager, on the gradients' fixed addresses); `fn2` = the optimiser step and
     the weight hand-over, a second graph. A replay is then graph · all-reduce · graph (capture in `thread_local` error mode: torch's
-    collective watchdog thread may query its events meanwhile)."""
+    collective watchdog thread may query its events meanwhile).
+    `guard` = the step's `FluxADAMW(capturable=True, guard=True)`: a captured step cannot look at its solve from the host (the eager
+    step's look at the step record, api._SolveFn._record_that_holds, needs a synchronisation), so a replay whose minibatch is stiffer
+    than the warm-up's can overflow the record and come back with NaN gradients — which the guarded update withholds on the device, at
+    the cost of that step's own time. Every `check_every` replays `replay` reads `guard.guard_state()` (one synchronisation) and, if
+    updates were withheld since its last look, calls `recover()`: ONE eager pass of the whole step on the current static inputs — outside
+    capture, so the look at the record happens and the handle keeps the larger "record_capacity"; its own update is withheld
+    (`FluxADAMW.withheld`), so the parameters, the step count and the counters are what the replays left — then the old graphs are
+    dropped and the step is captured again as in the constructor. `recoveries` counts the calls. A cause that an eager pass does not
+    cure (a trajectory that fails at maxiters, an overflow in a bf16 chain) keeps its steps withheld and costs a recovery per look that
+    finds new ones: watch `guard_state()["streak"]`. Several GPUs: a sum with a NaN is NaN on every rank, so after the all-reduce every
+    rank withholds the same step, looks at the same count and recovers at the same replay. `guard=None`: the class as it was."""
 
     def __init__(self, fn: Callable[[], torch.Tensor], static_inputs: Sequence[torch.Tensor] = (), warmup: int = 3,
-                 between: Optional[Callable[[], None]] = None, fn2: Optional[Callable[[], None]] = None):
+                 between: Optional[Callable[[], None]] = None, fn2: Optional[Callable[[], None]] = None, guard=None,
+                 check_every: int = 50):
         self.fn, self.static_inputs, self.between, self.fn2 = fn, list(static_inputs), between, fn2
-
-        def whole():
-            out = fn()
-            if between is not None:
-                between()
-            if fn2 is not None:
-                fn2()
-            return out
+        if guard is not None and not getattr(guard, "guard", False):
+            raise ValueError("GraphedStep(guard=...) takes the step's FluxADAMW(capturable=True, guard=True)")
+        if check_every < 1:
+            raise ValueError("check_every must be at least 1")
+        self.guard, self.check_every, self.recoveries = guard, int(check_every), 0
+        self._replays, self._skipped_seen = 0, 0
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(warmup):
-                whole()
+                self._whole()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
+        if guard is not None:
+            self._skipped_seen = guard.guard_state()["skipped"]
+        self._capture()
+
+    def _whole(self):
+        out = self.fn()
+        if self.between is not None:
+            self.between()
+        if self.fn2 is not None:
+            self.fn2()
+        return out
+
+    def _capture(self):
+        fn, between, fn2 = self.fn, self.between, self.fn2
         mode = dict(capture_error_mode="thread_local") if (between is not None or fn2 is not None) else {}
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, **mode):
@@ -328,7 +395,29 @@ class GraphedStep:
             self.between()
         if self.graph2 is not None:
             self.graph2.replay()
+        if self.guard is not None:
+            self._replays += 1
+            if self._replays % self.check_every == 0:
+                skipped = self.guard.guard_state()["skipped"]
+                if skipped > self._skipped_seen:
+                    self._skipped_seen = skipped
+                    loss = self.loss.clone() if self.loss is not None else None   # this replay's loss: the new capture has a new tensor
+                    self.recover()
+                    return loss
         return self.loss
+
+    def recover(self):
+        """One eager pass of the whole step on the current static inputs with its update withheld (the workspaces — the step record —
+        regrow; nothing the training run has computed changes), then a new capture in place of the old graphs. See the class docstring."""
+        if self.guard is None:
+            raise ValueError("GraphedStep.recover() needs guard=")
+        self.recoveries += 1
+        torch.cuda.synchronize()
+        with self.guard.withheld():
+            self._whole()
+        torch.cuda.synchronize()
+        self.graph = self.graph2 = None      # the old graphs and their memory pool go before the new capture
+        self._capture()
 
 
 def train(model: LatentDiffEqModel, loader_train: Iterable, val_set, dt: float, epochs: int, seq_len: int, full_seq_len: int,
