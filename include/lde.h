@@ -716,6 +716,32 @@ int lde_adamw_flux_step_dev(int n, const lde_adam_tensor* t, float lr, float bet
 int lde_guard_init(int64_t* guard_dev, void* stream);
 int lde_adamw_flux_step_guarded(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps, float decay,
                                 int64_t* step_dev, int64_t* guard_dev, void* stream);
+/* The clipped step: the guarded step with gradient clipping by norm between its scan and its update — Flux's
+ * `Optimiser(ClipNorm(c), ADAMW(...))`, torch's `clip_grad_norm_` in front of the optimiser — without a launch per array and without a norm
+ * the host has to look at, so that it can sit inside a captured step. Three phases, each a kernel boundary; no launch waits for another
+ * workgroup, nothing is read by the host, no floating-point atomic is used: the result does not depend on the order in which workgroups run.
+ *   1. the scan reads every t[i].g once, makes the guarded step's non-finite test and forms Σg²: in f32 within a lane (at most 32 elements),
+ *      in f64 above (wave, workgroup); one f64 partial per workgroup goes to a slot of its own in ws_dev;
+ *   2. one workgroup sums each array's partials in a fixed order and writes norms_dev[i] = (float)√Σᵢ (0 for an empty array),
+ *      norms_dev[n] = (float)√ΣΣ and the scale of every array, computed in f32 from the f32 norm:
+ *        LDE_CLIP_GLOBAL     s = min(1, c / (‖g‖ + 1e-6))    for every array, ‖g‖ = norms_dev[n]            (torch.nn.utils.clip_grad_norm_)
+ *        LDE_CLIP_PER_ARRAY  sᵢ = ‖gᵢ‖ > c ? c / ‖gᵢ‖ : 1                                                  (Flux.Optimise.ClipNorm)
+ *      A norm that is not finite counts as a non-finite gradient — a NaN or ±Inf element, and also finite elements beyond ≈ 1.8e19, whose
+ *      squares overflow f32: guard word [0] is lowered to the lowest such array's index. (LDE_CLIP_GLOBAL only: should ‖g‖ alone
+ *      overflow f32 with every ‖gᵢ‖ finite, the step is withheld in the name of the first non-empty array.)
+ *   3. the update is the guarded step's with g ← sᵢ·g in front of the moments. Withholding, the counters, the reset of word [0] and the step
+ *      count are the guarded step's. Gradients are not modified in memory. With every scale equal to 1, p, m, v and *step_dev end
+ *      bit-identical to lde_adamw_flux_step_guarded on the same arguments.
+ * ws_dev: lde_clip_ws_bytes(n, t) bytes of device memory, 8-byte aligned, owned by the caller, contents of no meaning between calls; the
+ * size depends on the array sizes only (host arithmetic, no device call; 0 for n == 0 or only empty arrays, and ws_dev may then be NULL).
+ * norms_dev: n + 1 device floats. Returns LDE_ERR_INVALID_ARG before any device call for a NULL step_dev, guard_dev or norms_dev, a NULL
+ * ws_dev with any non-empty array, a clip_norm that is not finite or not > 0, an unknown mode, and what lde_adamw_flux_step_dev refuses.
+ * A step over empty arrays only ticks the count and writes zeros to norms_dev. */
+enum { LDE_CLIP_GLOBAL = 0, LDE_CLIP_PER_ARRAY = 1 };
+size_t lde_clip_ws_bytes(int n, const lde_adam_tensor* t);
+int lde_adamw_flux_step_clipped(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps, float decay,
+                                float clip_norm, int clip_mode, int64_t* step_dev, int64_t* guard_dev,
+                                void* ws_dev, float* norms_dev, void* stream);
 
 /* ====================================================================================================================
  * The one collective of the path. The reference's only parallelism is `EnsembleThreads()` over the

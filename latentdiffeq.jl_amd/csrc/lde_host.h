@@ -795,6 +795,66 @@ static OptLaunch opt_next_launch(int n, const lde_adam_tensor* t, int first, int
   return L;
 }
 
+// ---- the workspace of the clipped step (lde_adamw_flux_step_clipped, include/lde.h: "the clipped step"): what the norm scan leaves for
+// the finalising kernel and the finalising kernel for the update. The scan walks t[] with opt_next_launch at GUARD_PER_WG, so its workgroups
+// — launch after launch, workgroup after workgroup — meet the non-empty arrays in the caller's order, each array's slices side by side.
+// One f64 partial per scan workgroup in THAT order: array L.idx[i] of a launch with slot base s owns slots [s + L.blk0[i], s + L.blk0[i+1]).
+// The non-empty arrays are numbered 0 … nne − 1 in the caller's order ("ordinals": the update's launches, whose packing may differ from the
+// scan's, meet them in the same order); per ordinal the workspace holds the array's Σg² (f64, the finalising kernel's), its descriptor
+// (written by the scan workgroup that owns the array's first slice: the table of a launch travels in kernel arguments, the finalising
+// kernel sees every launch's arrays) and its scale (f32).
+//     [0, 8·slots) partials | [off_sums, +8·nne) | [off_desc, +16·nne) | [off_scale, +4·nne)              (ws_dev: 8-byte aligned)
+// `on_launch(L, slot0, ord0)` is called once per scan launch; lde_clip_ws_bytes passes one that does nothing.
+struct ClipDesc {
+  int64_t slot0;    // the array's first partial
+  int32_t nslots;   // its scan workgroups
+  int32_t idx;      // its index in the caller's t[]
+};
+struct ClipWs {
+  int64_t slots;    // scan workgroups of the whole call = f64 partials
+  int64_t nne;      // non-empty arrays
+  size_t off_sums, off_desc, off_scale, bytes;
+};
+template <class F>
+static ClipWs clip_plan(int n, const lde_adam_tensor* t, F&& on_launch) {
+  ClipWs w{};
+  for (int first = 0; first < n;) {
+    const OptLaunch L = opt_next_launch(n, t, first, GUARD_PER_WG);
+    if (L.n == 0) break;   // nothing left (or an array no launch holds: the update's plan, with the smaller slice, has refused the call)
+    on_launch(L, w.slots, w.nne);
+    first = L.next;
+    w.slots += L.blk0[L.n];
+    w.nne += L.n;
+  }
+  w.off_sums = sizeof(double) * (size_t)w.slots;
+  w.off_desc = w.off_sums + sizeof(double) * (size_t)w.nne;
+  w.off_scale = w.off_desc + sizeof(ClipDesc) * (size_t)w.nne;
+  w.bytes = w.off_scale + sizeof(float) * (size_t)w.nne;
+  return w;
+}
+// what every form of the update refuses, and what the clipped step refuses on top of it — all of it before any device call
+static bool opt_args_ok(int n, const lde_adam_tensor* t, float beta1, float beta2, int64_t step, const void* step_dev) {
+  if (n < 0 || (n > 0 && !t) || (!step_dev && step < 1) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return false;
+  for (int i = 0; i < n; i++)
+    if (t[i].n < 0 || (t[i].n > 0 && (!t[i].p || !t[i].g || !t[i].m || !t[i].v))) return false;
+  return true;
+}
+static bool clip_args_ok(int n, const lde_adam_tensor* t, float beta1, float beta2, float clip_norm, int clip_mode, const void* step_dev,
+                         const void* guard_dev, const void* ws_dev, const void* norms_dev) {
+  if (!step_dev || !guard_dev || !norms_dev || !(clip_norm > 0.f) || !std::isfinite(clip_norm)) return false;
+  if (clip_mode != LDE_CLIP_GLOBAL && clip_mode != LDE_CLIP_PER_ARRAY) return false;
+  if (!opt_args_ok(n, t, beta1, beta2, 0, step_dev)) return false;
+  for (int first = 0; first < n;) {   // the update's plan: an array no launch holds
+    const OptLaunch L = opt_next_launch(n, t, first, OPT_PER_WG);
+    if (L.too_large) return false;
+    if (L.n == 0) break;
+    first = L.next;
+  }
+  bool any = false;
+  for (int i = 0; i < n; i++) any = any || t[i].n > 0;
+  return !any || (ws_dev && (reinterpret_cast<uintptr_t>(ws_dev) & 7) == 0);
+}
+
 static KOpts make_opts(const lde_problem_desc& d, const double* ts, int T, int B) {
   KOpts o;
   o.abstol = (float)d.abstol;

@@ -132,6 +132,52 @@ __global__ void __launch_bounds__(OPT_WG) k_adamw_flux(OptTable tab, OptCoef c, 
     for (int q = 0; q < 4 && e + q < hi; q++) adam1(t.p[e + q], t.g[e + q], t.m[e + q], t.v[e + q], c);
 }
 
+// The update of the clipped step (lde_adamw_flux_step_clipped): k_adamw_flux<true> with g ← s·g in front of adam1, s = scale[i] = what
+// k_clip_finalise left for the launch's array i (memory keeps the raw g; s = 1: s·g is g bit for bit and the step is the guarded one). A
+// kernel of its own and not a third instantiation: sharing the body through an inlined function changed the register assignment of the two
+// existing instantiations, and they are to stay the code they were.
+__global__ void __launch_bounds__(OPT_WG) k_adamw_flux_clipped(OptTable tab, OptCoef c, int64_t* __restrict__ step_dev, int bump, GuardArg<true> ga,
+                                                               const float* __restrict__ scale) {
+  __shared__ int64_t s_bad;
+  if (threadIdx.x == 0) s_bad = __hip_atomic_load(ga.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int64_t ti = *step_dev + 1;
+  const double td = (double)ti;
+  c.inv_bc1 = (float)(1.0 / (1.0 - pow((double)c.b1, td)));
+  c.inv_bc2 = (float)(1.0 / (1.0 - pow((double)c.b2, td)));
+  __syncthreads();
+  const int64_t bad = s_bad;
+  if (bump && threadIdx.x == 0 && atomicAdd(&g_guard_seen, 1u) == gridDim.x - 1) {
+    guard_bookkeeping(ga.w, bad, step_dev, ti);
+    g_guard_seen = 0;
+  }
+  if (bad != -1) return;
+  int i = 0;
+  while (i + 1 < tab.n && (int)blockIdx.x >= tab.blk0[i + 1]) i++;
+  const lde_adam_tensor t = tab.t[i];
+  const float s = scale[i];
+  const int64_t lo = (int64_t)((int)blockIdx.x - tab.blk0[i]) * OPT_PER_WG;
+  const int64_t hi = lo + OPT_PER_WG < t.n ? lo + OPT_PER_WG : t.n;
+  const bool al = ((((uintptr_t)t.p) | ((uintptr_t)t.g) | ((uintptr_t)t.m) | ((uintptr_t)t.v)) & 15) == 0;
+  int64_t e = lo + 4 * (int64_t)threadIdx.x;
+  if (al) {
+    for (; e + 4 <= hi; e += 4 * OPT_WG) {
+      f4 x = *reinterpret_cast<f4*>(t.p + e), m = *reinterpret_cast<f4*>(t.m + e), v = *reinterpret_cast<f4*>(t.v + e);
+      const f4 g = *reinterpret_cast<const f4*>(t.g + e);
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        float xq = x[q], mq = m[q], vq = v[q];
+        adam1(xq, s * g[q], mq, vq, c);
+        x[q] = xq; m[q] = mq; v[q] = vq;
+      }
+      *reinterpret_cast<f4*>(t.p + e) = x;
+      *reinterpret_cast<f4*>(t.m + e) = m;
+      *reinterpret_cast<f4*>(t.v + e) = v;
+    }
+  }
+  for (; e < hi; e += 4 * OPT_WG)   // unaligned arrays, and the ragged end
+    for (int q = 0; q < 4 && e + q < hi; q++) adam1(t.p[e + q], s * t.g[e + q], t.m[e + q], t.v[e + q], c);
+}
+
 // The scan of the guarded step: a workgroup owns GUARD_PER_WG consecutive elements of one array's GRADIENT (the same table, packed with the
 // larger slice: 4 bytes per element are read where the update moves 28). Non-finite = exponent bits all ones — NaN of any sign and payload,
 // ±Inf — as an integer test, OR-ed over a lane's elements; one ballot per wave; only a wave that saw one issues a global atomicMin of the
@@ -163,6 +209,123 @@ __global__ void __launch_bounds__(OPT_WG) k_grad_guard(OptTable tab, OptIdx ix, 
   if (__ballot(bad != 0) != 0 && (threadIdx.x & 63) == 0) atomicMin(word0, (unsigned long long)ix.idx[i]);
 }
 
+// The scan of the clipped step (lde_adamw_flux_step_clipped, include/lde.h: "the clipped step"): k_grad_guard's walk and test, and Σg² on
+// the same loads. A lane adds the squares of its (at most GUARD_PER_WG / OPT_WG = 32) elements in f32; everything above the lane is f64:
+// a butterfly over the wave (every lane ends with the same sum, whatever the order the waves ran in), the workgroup's waves in wave order.
+// One f64 per workgroup goes to the workgroup's own slot `part[blockIdx.x]` (`part` = the launch's slot base, lde_host::clip_plan) — no
+// floating-point atomic, nothing that depends on arrival order. The workgroup that owns an array's first slice also leaves the array's
+// descriptor (`desc` = the launch's first ordinal) for the finalising kernel, which sees no launch's table.
+using lde_host::ClipDesc;
+__device__ __forceinline__ double wave_sum(double s) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  return s;
+}
+__device__ __forceinline__ float sq4(float acc, u4 b) {
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const float g = __uint_as_float(b[q]);
+    acc += g * g;
+  }
+  return acc;
+}
+__global__ void __launch_bounds__(OPT_WG) k_grad_norm_guard(OptTable tab, OptIdx ix, unsigned long long* __restrict__ word0, double* __restrict__ part,
+                                                            ClipDesc* __restrict__ desc, int64_t slot0) {
+  __shared__ double s_wave[OPT_WG / 64];
+  int i = 0;
+  while (i + 1 < tab.n && (int)blockIdx.x >= tab.blk0[i + 1]) i++;
+  const unsigned* g = reinterpret_cast<const unsigned*>(tab.t[i].g);
+  const int64_t n = tab.t[i].n;
+  const int64_t lo = (int64_t)((int)blockIdx.x - tab.blk0[i]) * GUARD_PER_WG;
+  const int64_t hi = lo + GUARD_PER_WG < n ? lo + GUARD_PER_WG : n;
+  unsigned bad = 0;
+  float acc = 0.0f;
+  int64_t e = lo + 4 * (int64_t)threadIdx.x;
+  if ((((uintptr_t)g) & 15) == 0) {
+    constexpr int64_t S = 4 * OPT_WG;
+    for (; e + (GUARD_LOADS - 1) * S + 4 <= hi; e += GUARD_LOADS * S) {   // GUARD_LOADS independent 16-byte loads in flight per lane
+      u4 x[GUARD_LOADS];
+#pragma unroll
+      for (int k = 0; k < GUARD_LOADS; k++) x[k] = *reinterpret_cast<const u4*>(g + e + k * S);
+#pragma unroll
+      for (int k = 0; k < GUARD_LOADS; k++) {
+        bad |= nonfinite4(x[k]);
+        acc = sq4(acc, x[k]);
+      }
+    }
+    for (; e + 4 <= hi; e += S) {
+      const u4 x = *reinterpret_cast<const u4*>(g + e);
+      bad |= nonfinite4(x);
+      acc = sq4(acc, x);
+    }
+  }
+  for (; e < hi; e += 4 * OPT_WG)   // unaligned arrays, and the ragged end
+    for (int q = 0; q < 4 && e + q < hi; q++) {
+      const unsigned b = g[e + q];
+      const float gq = __uint_as_float(b);
+      bad |= nonfinite(b);
+      acc += gq * gq;
+    }
+  if (__ballot(bad != 0) != 0 && (threadIdx.x & 63) == 0) atomicMin(word0, (unsigned long long)ix.idx[i]);
+  const double w = wave_sum((double)acc);
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = s_wave[0];
+#pragma unroll
+    for (int k = 1; k < OPT_WG / 64; k++) s += s_wave[k];
+    part[blockIdx.x] = s;
+    if ((int)blockIdx.x == tab.blk0[i]) {
+      ClipDesc d;
+      d.slot0 = slot0 + tab.blk0[i];
+      d.nslots = tab.blk0[i + 1] - tab.blk0[i];
+      d.idx = ix.idx[i];
+      desc[i] = d;
+    }
+  }
+}
+
+// The finalising kernel of the clipped step: ONE workgroup, after every scan launch. A wave takes the arrays wave, wave + 4, … (ordinals:
+// lde_host::clip_plan): its lanes add the array's partials lane, lane + 64, … in that order, the butterfly adds the lanes — a fixed order
+// for a given table. Σ of every array goes to `sums` (f64); behind a barrier every wave adds them all in the same order (every thread
+// then holds the same ΣΣ), and the threads write norms[idx] = (float)√Σ, the scale (f32, from the f32 norm: the contract of include/lde.h)
+// and, for a norm that is not finite, the array's index into guard word [0] (atomicMin: the lowest wins, as in the scan).
+struct ClipArg { float c; int mode; };
+__global__ void __launch_bounds__(OPT_WG) k_clip_finalise(const double* __restrict__ part, double* sums, const ClipDesc* __restrict__ desc,
+                                                          float* __restrict__ scale, int64_t nne, int n, float* __restrict__ norms, ClipArg a,
+                                                          unsigned long long* __restrict__ word0) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = threadIdx.x; i < n; i += OPT_WG) norms[i] = 0.0f;   // (the empty arrays keep this)
+  for (int64_t k = wave; k < nne; k += OPT_WG / 64) {
+    const ClipDesc d = desc[k];
+    double s = 0.0;
+    for (int j = lane; j < d.nslots; j += 64) s += part[d.slot0 + j];
+    s = wave_sum(s);
+    if (lane == 0) sums[k] = s;
+  }
+  __syncthreads();
+  double tot = 0.0;
+  for (int64_t k = lane; k < nne; k += 64) tot += sums[k];
+  tot = wave_sum(tot);
+  const float gn = (float)sqrt(tot);
+  int any_bad = 0;
+  for (int64_t k = threadIdx.x; k < nne; k += OPT_WG) {
+    const float ni = (float)sqrt(sums[k]);
+    const int idx = desc[k].idx;
+    norms[idx] = ni;
+    scale[k] = a.mode == LDE_CLIP_GLOBAL ? fminf(1.0f, a.c / (gn + 1e-6f)) : (ni > a.c ? a.c / ni : 1.0f);
+    if (!isfinite(ni)) {
+      any_bad = 1;
+      atomicMin(word0, (unsigned long long)idx);
+    }
+  }
+  any_bad = __syncthreads_or(any_bad);
+  if (threadIdx.x == 0) {
+    norms[n] = gn;
+    if (a.mode == LDE_CLIP_GLOBAL && !any_bad && !isfinite(gn)) atomicMin(word0, (unsigned long long)desc[0].idx);   // (ΣΣ alone beyond f32)
+  }
+}
+
 }  // namespace lde
 
 using namespace lde;
@@ -175,16 +338,19 @@ static OptTable opt_table(const lde_adam_tensor* t, const lde_host::OptLaunch& L
   return tab;
 }
 
-template <bool GUARD>
-static int adamw_impl(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps, float decay, int64_t step,
-                      int64_t* step_dev, int64_t* guard_dev, void* stream) {
-  if (n < 0 || (n > 0 && !t) || (!step_dev && step < 1) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return LDE_ERR_INVALID_ARG;
-  for (int i = 0; i < n; i++)
-    if (t[i].n < 0 || (t[i].n > 0 && (!t[i].p || !t[i].g || !t[i].m || !t[i].v))) return LDE_ERR_INVALID_ARG;
+static OptCoef opt_coef(float lr, float beta1, float beta2, float eps, float decay, int64_t step, const int64_t* step_dev) {
   OptCoef c;
   c.b1 = beta1; c.b2 = beta2; c.omb1 = 1.0f - beta1; c.omb2 = 1.0f - beta2; c.eps = eps; c.lr = lr; c.decay = decay;
   c.inv_bc1 = (float)(1.0 / (1.0 - __builtin_pow((double)beta1, (double)(step_dev ? 1 : step))));   // Flux carries β₁ᵗ, β₂ᵗ as a running product
   c.inv_bc2 = (float)(1.0 / (1.0 - __builtin_pow((double)beta2, (double)(step_dev ? 1 : step))));
+  return c;
+}
+
+template <bool GUARD>
+static int adamw_impl(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps, float decay, int64_t step,
+                      int64_t* step_dev, int64_t* guard_dev, void* stream) {
+  if (!lde_host::opt_args_ok(n, t, beta1, beta2, step, step_dev)) return LDE_ERR_INVALID_ARG;
+  const OptCoef c = opt_coef(lr, beta1, beta2, eps, decay, step, step_dev);
   GuardArg<GUARD> ga;
   if constexpr (GUARD) {
     ga.w = guard_dev;
@@ -223,6 +389,61 @@ static int adamw_impl(int n, const lde_adam_tensor* t, float lr, float beta1, fl
     if (hipGetLastError() != hipSuccess) return LDE_ERR_HIP;
   }
   return LDE_OK;
+}
+
+// The clipped step: every scan launch, the finalising kernel, every update launch — in that order on one stream (lde_host::clip_plan says
+// where each scan launch's partials and descriptors go; the update's launches meet the non-empty arrays in the same order, so launch
+// by launch they take the next L.n scales).
+static int adamw_clipped(int n, const lde_adam_tensor* t, const OptCoef& c, float clip_norm, int clip_mode, int64_t* step_dev, int64_t* guard_dev,
+                         void* ws_dev, float* norms_dev, hipStream_t stream) {
+  const lde_host::ClipWs w = lde_host::clip_plan(n, t, [](const lde_host::OptLaunch&, int64_t, int64_t) {});
+  char* const ws = static_cast<char*>(ws_dev);
+  double* const part = w.nne ? reinterpret_cast<double*>(ws) : nullptr;
+  double* const sums = w.nne ? reinterpret_cast<double*>(ws + w.off_sums) : nullptr;
+  ClipDesc* const desc = w.nne ? reinterpret_cast<ClipDesc*>(ws + w.off_desc) : nullptr;
+  float* const scale = w.nne ? reinterpret_cast<float*>(ws + w.off_scale) : nullptr;
+  unsigned long long* const word0 = reinterpret_cast<unsigned long long*>(guard_dev);
+  int rc = LDE_OK;
+  lde_host::clip_plan(n, t, [&](const lde_host::OptLaunch& L, int64_t slot0, int64_t ord0) {
+    if (rc != LDE_OK) return;
+    OptIdx ix;
+    for (int i = 0; i < L.n; i++) ix.idx[i] = L.idx[i];
+    hipLaunchKernelGGL(k_grad_norm_guard, dim3(L.blk0[L.n]), dim3(OPT_WG), 0, stream, opt_table(t, L), ix, word0, part + slot0, desc + ord0, slot0);
+    if (hipGetLastError() != hipSuccess) rc = LDE_ERR_HIP;
+  });
+  if (rc != LDE_OK) return rc;
+  ClipArg a;
+  a.c = clip_norm; a.mode = clip_mode;
+  hipLaunchKernelGGL(k_clip_finalise, dim3(1), dim3(OPT_WG), 0, stream, part, sums, desc, scale, w.nne, n, norms_dev, a, word0);
+  if (hipGetLastError() != hipSuccess) return LDE_ERR_HIP;
+  GuardArg<true> ga;
+  ga.w = guard_dev;
+  int64_t ord0 = 0;
+  for (int first = 0; first < n;) {
+    const lde_host::OptLaunch L = lde_host::opt_next_launch(n, t, first, OPT_PER_WG);
+    first = L.next;
+    if (L.n == 0) break;
+    hipLaunchKernelGGL(k_adamw_flux_clipped, dim3(L.blk0[L.n]), dim3(OPT_WG), 0, stream, opt_table(t, L), c, step_dev, L.last ? 1 : 0, ga, scale + ord0);
+    if (hipGetLastError() != hipSuccess) return LDE_ERR_HIP;
+    ord0 += L.n;
+  }
+  if (w.nne == 0) {
+    hipLaunchKernelGGL(k_adam_tick_guarded, dim3(1), dim3(1), 0, stream, step_dev, guard_dev);
+    if (hipGetLastError() != hipSuccess) return LDE_ERR_HIP;
+  }
+  return LDE_OK;
+}
+
+extern "C" size_t lde_clip_ws_bytes(int n, const lde_adam_tensor* t) {
+  if (n <= 0 || !t) return 0;
+  return lde_host::clip_plan(n, t, [](const lde_host::OptLaunch&, int64_t, int64_t) {}).bytes;
+}
+extern "C" int lde_adamw_flux_step_clipped(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps, float decay,
+                                           float clip_norm, int clip_mode, int64_t* step_dev, int64_t* guard_dev, void* ws_dev,
+                                           float* norms_dev, void* stream) {
+  if (!lde_host::clip_args_ok(n, t, beta1, beta2, clip_norm, clip_mode, step_dev, guard_dev, ws_dev, norms_dev)) return LDE_ERR_INVALID_ARG;
+  return adamw_clipped(n, t, opt_coef(lr, beta1, beta2, eps, decay, 0, step_dev), clip_norm, clip_mode, step_dev, guard_dev, ws_dev, norms_dev,
+                       (hipStream_t)stream);
 }
 
 extern "C" int lde_adamw_flux_step(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps, float decay,

@@ -18,6 +18,7 @@ no kernel of its own.
 from __future__ import annotations
 
 import contextlib
+import math
 import os
 from typing import Callable, Iterable, List, Optional, Sequence
 
@@ -152,12 +153,24 @@ class FluxADAMW(torch.optim.Adam):
     if any element of any array is NaN or ±Inf the whole update is withheld: no parameter, no moment and not the step count change (the
     count is also the noise epoch of a captured step: the next replay draws the ε the withheld one drew). Otherwise the update is the
     unguarded one bit for bit. `guard_state()` reads the counters. Several GPUs: the gradient all-reduce sits before the optimiser half,
-    and a sum with a NaN is NaN on every rank — all ranks withhold the same step; nothing is exchanged for it."""
+    and a sum with a NaN is NaN on every rank — all ranks withhold the same step; nothing is exchanged for it.
+    `clip_norm=c` clips the gradients by norm in front of the update: `clip_mode="global"` is torch's `clip_grad_norm_` — one scale
+    min(1, c/(‖g‖ + 1e-6)) from the norm of all gradients together; `"per_array"` is Flux's `Optimiser(ClipNorm(c), ADAMW(...))` — every
+    array whose own norm exceeds c is scaled to norm c. On the native path it needs `capturable=True, guard=True`: the step is
+    lde_adamw_flux_step_clipped (include/lde.h: "the clipped step") — the guard's scan also forms Σg², one small kernel turns the sums into
+    norms and scales, the update scales g as it loads it; no launch per array, nothing read by the host, the gradients in memory stay as
+    they were, and a norm that is not finite withholds the step like a NaN. Its workspace and the norms live at fixed addresses from
+    construction on, so the step can be captured. Off the native path (CPU tensors, `native=False`) the same two rules are applied with
+    torch ops in front of the step, to `p.grad` IN PLACE, as `clip_grad_norm_` does. `grad_norms()` reads the last step's norms."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), decay: float = 0.0, eps: float = 1e-8, fused=None, native=None,
-                 capturable: bool = False, guard: bool = False):
+                 capturable: bool = False, guard: bool = False, clip_norm: Optional[float] = None, clip_mode: str = "global"):
         if guard and not capturable:
             raise ValueError("FluxADAMW(guard=True) needs capturable=True (the guard is part of the device-counted step)")
+        if clip_mode not in L.CLIP_MODES:
+            raise ValueError(f"FluxADAMW(clip_mode={clip_mode!r}): one of {sorted(L.CLIP_MODES)}")
+        if clip_norm is not None and not (math.isfinite(float(clip_norm)) and float(clip_norm) > 0.0):
+            raise ValueError("FluxADAMW(clip_norm=...) takes a finite threshold > 0 (None: no clipping)")
         groups = list(params)
         params = [p for g in groups for p in (g["params"] if isinstance(g, dict) else [g])]     # (arrays, or torch's group dicts)
         on_gpu = bool(params) and all(p.is_cuda for p in params)
@@ -189,6 +202,55 @@ class FluxADAMW(torch.optim.Adam):
         if self.guard:
             self._guard_dev = torch.empty(L.GUARD_WORDS, dtype=torch.int64, device=params[0].device)
             L.call("lde_guard_init", None, L.ptr(self._guard_dev), L.raw_stream(params[0].device.index))
+        # clip: the workspace of the clipped step and its n + 1 norms, allocated ONCE — a captured step replays these addresses
+        self.clip_norm = None if clip_norm is None else float(clip_norm)
+        self.clip_mode = clip_mode
+        self._clip_ws = self._norms_dev = self._norms_host = None
+        if self.clip_norm is not None and self.native:
+            if not (self.capturable and self.guard):
+                raise ValueError("FluxADAMW(clip_norm=...) on the native path needs capturable=True, guard=True "
+                                 "(the clipped step is the guarded, device-counted step with a scale in front of it)")
+            tab = (L.AdamTensor * len(params))()
+            for i, p in enumerate(params):
+                tab[i].n = p.numel()
+            nbytes = int(L.load().lde_clip_ws_bytes(len(params), tab))
+            self._clip_ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=params[0].device)
+            self._norms_dev = torch.zeros(len(params) + 1, dtype=torch.float32, device=params[0].device)
+
+    def grad_norms(self):
+        """(per-array list, total) — the gradient norms of the most recent `step()`, before clipping, in the parameter group's order: what
+        the clipped step measured (include/lde.h: "the clipped step"; an empty array reads 0, the total is the norm of all gradients
+        together in either mode). ONE device→host copy: a synchronisation with the device; not for every step of a captured run."""
+        if self.clip_norm is None:
+            raise ValueError("FluxADAMW.grad_norms() needs clip_norm=")
+        if self._norms_dev is not None:
+            w = self._norms_dev.tolist()
+        elif self._norms_host is not None:
+            w = self._norms_host
+        else:
+            w = [0.0] * (sum(len(g["params"]) for g in self.param_groups) + 1)
+        return [float(x) for x in w[:-1]], float(w[-1])
+
+    @torch.no_grad()
+    def _clip_with_torch(self):
+        """Off the native path: the two rules of the clipped step with torch ops, on `p.grad` in place — norms in f64, rounded to f32, the
+        scale formed in f32 (tests/clip_ref.py states the same). Arrays without a gradient count as empty."""
+        ps = [p for g in self.param_groups for p in g["params"]]
+        sq = [p.grad.detach().double().pow(2).sum() if p.grad is not None else torch.zeros((), dtype=torch.float64, device=p.device) for p in ps]
+        per = [s.sqrt().float() for s in sq]
+        total = torch.stack([s.cpu() for s in sq]).sum().sqrt().float() if sq else torch.zeros(())
+        c = torch.tensor(self.clip_norm, dtype=torch.float32)
+        one = torch.ones((), dtype=torch.float32)
+        for p, ni in zip(ps, per):
+            if p.grad is None:
+                continue
+            if self.clip_mode == "global":
+                s = torch.minimum(one, c / (total + torch.tensor(1e-6, dtype=torch.float32)))
+            else:
+                s = c / ni.cpu() if float(ni) > float(c) else one
+            if float(s) != 1.0:
+                p.grad.mul_(s.to(p.grad.device, p.grad.dtype))
+        self._norms_host = [float(x) for x in per] + [float(total)]
 
     def guard_state(self) -> dict:
         """dict(skipped, streak, last_bad_array) of the guarded step (include/lde.h: "the guarded step"): updates withheld so far,
@@ -257,7 +319,11 @@ class FluxADAMW(torch.optim.Adam):
                         keep.append(gr)
                     t = tab[i]
                     t.p, t.g, t.m, t.v, t.n = p.data_ptr(), gr.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
-                if self.guard:
+                if self.clip_norm is not None:
+                    L.call("lde_adamw_flux_step_clipped", None, len(ps), tab, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.decay,
+                           self.clip_norm, L.CLIP_MODES[self.clip_mode], L.ptr(self._step_dev), L.ptr(self._guard_dev),
+                           L.ptr(self._clip_ws), L.ptr(self._norms_dev), L.raw_stream(ps[0].device.index))
+                elif self.guard:
                     L.call("lde_adamw_flux_step_guarded", None, len(ps), tab, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.decay,
                            L.ptr(self._step_dev), L.ptr(self._guard_dev), L.raw_stream(ps[0].device.index))
                 else:
@@ -307,6 +373,8 @@ class FluxADAMW(torch.optim.Adam):
         if closure is not None:             # gradients at the UN-decayed point, as Flux's Optimiser(ADAM, WeightDecay) and the native path
             with torch.enable_grad():
                 loss = closure()
+        if self.clip_norm is not None:
+            self._clip_with_torch()
         if self.decay:
             for g in self.param_groups:
                 ps = [p for p in g["params"] if p.grad is not None]
@@ -423,13 +491,22 @@ class GraphedStep:
 def train(model: LatentDiffEqModel, loader_train: Iterable, val_set, dt: float, epochs: int, seq_len: int, full_seq_len: int,
           lr: float = 1e-3, decay: float = 1e-10, start_beta: float = 0.0, end_beta: float = 1.0, n_cycle: int = 3, ratio: float = 0.9,
           progressive_training: bool = False, prog_training_duration: int = 0, start_seq_len: int = 0, variational: bool = True,
-          rng: Optional[np.random.Generator] = None, on_epoch: Optional[Callable] = None, grad_sync: Optional[Callable] = None):
+          rng: Optional[np.random.Generator] = None, on_epoch: Optional[Callable] = None, grad_sync: Optional[Callable] = None,
+          clip_norm: Optional[float] = None, clip_mode: str = "global"):
     """The epoch loop of the example script  [REF examples/pendulum_friction-less/model_train.jl:138-218]: cyclical β, optional
     progressive sequence length, Flux-flavour ADAMW, validation loss after every minibatch, best weights kept. `loader_train` yields
     x [pixels, B, full_seq_len] tensors on the model's device; `grad_sync` is called between backward and the optimiser step
-    (dist.FlatGradAllReduce for multi-GPU). Returns (history, best_state)."""
+    (dist.FlatGradAllReduce for multi-GPU). `clip_norm` (with `clip_mode`, see FluxADAMW): the gradients are clipped by norm in front of
+    every update — on the GPU the optimiser is then built in its capturable, guarded, clipped form (one submission per step, a step with
+    non-finite gradients or norms is withheld) and is left in `model.optimizer`, where `grad_norms()` and `guard_state()` can be read;
+    None: the loop as it was. Returns (history, best_state)."""
     params = model.parameters()
-    opt = FluxADAMW(params, lr=lr, betas=(0.9, 0.999), decay=decay)      # ADAMW(η, (0.9, 0.999), decay), Flux flavour
+    if clip_norm is None:
+        opt = FluxADAMW(params, lr=lr, betas=(0.9, 0.999), decay=decay)      # ADAMW(η, (0.9, 0.999), decay), Flux flavour
+    else:
+        on_gpu = bool(params) and all(p.is_cuda for p in params)
+        opt = FluxADAMW(params, lr=lr, betas=(0.9, 0.999), decay=decay, capturable=on_gpu, guard=on_gpu, clip_norm=clip_norm, clip_mode=clip_mode)
+        model.optimizer = opt
     schedule = frange_cycle_linear(epochs, start_beta, end_beta, n_cycle, ratio)
     if progressive_training:
         prog = np.rint(np.linspace(start_seq_len, seq_len, prog_training_duration)).astype(int)
