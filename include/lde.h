@@ -742,6 +742,34 @@ size_t lde_clip_ws_bytes(int n, const lde_adam_tensor* t);
 int lde_adamw_flux_step_clipped(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps, float decay,
                                 float clip_norm, int clip_mode, int64_t* step_dev, int64_t* guard_dev,
                                 void* ws_dev, float* norms_dev, void* stream);
+/* The AdaBelief step: the optimiser the reference's three training scripts name as the alternative, `AdaBelief(η)`
+ * [REF examples/pendulum_friction-less/model_train.jl:136-138], [REF model_train_LatentODE.jl:133-135], [REF model_train_original_data.jl:115-118]
+ * — as `Optimiser(AdaBelief(η, (β₁, β₂)), WeightDecay(decay))`, in the four forms of the ADAMW step above. Per element, with the caller's
+ * state arrays m and s (`v` of lde_adam_tensor holds s; zero before the first step) and t ≥ 1:
+ *     m ← β₁·m + (1 − β₁)·g
+ *     s ← β₂·s + (1 − β₂)·(g − m)² + ε_var                         (m is the NEW m)
+ *     Δ = η·(m/(1 − β₁ᵗ)) / (√(s/(1 − β₂ᵗ)) + ε_den) + decay·x     (the decay is not scaled by η, as in the ADAMW step)
+ *     x ← x − Δ
+ * in f32, a·b + c·d as one fused multiply-add (m, s and Δ), every other operation rounded on its own; 1/(1 − βᵗ) is formed in f64 from the
+ * f32 β and rounded to f32. eps_var and eps_den are separate arguments because the published forms differ in where ε goes and how large
+ * it is: the paper (Zhuang et al. 2020) has ε_var = ε_den = ε; Flux 0.13.6's `AdaBelief` [REF Manifest.toml:452] is — AS RECALLED, Flux's
+ * source is not available to this project, so this is UNPINNED — ε_var = ε_den = ε² with ε = 1e-8, which is what the Python layer
+ * (train.FluxAdaBelief) passes by default. The other placement is the same call with other arguments.
+ * ONE update launch for all n arrays, the table, the stream, *step_dev, guard_dev (lde_guard_init, LDE_GUARD_WORDS), ws_dev
+ * (lde_clip_ws_bytes), norms_dev and LDE_CLIP_* exactly as in lde_adamw_flux_step / _dev / _guarded / _clipped: the guarded and clipped
+ * forms run the SAME scan and finalising kernels in front of the update, so norms_dev, the guard words and what withholds a step are the
+ * ADAMW step's bit for bit. A clean guarded step equals the device-counted one bit for bit; a clipped one with every scale 1 the guarded.
+ * Every form returns LDE_ERR_INVALID_ARG, before any device call, for what its ADAMW twin refuses and for an eps_var or eps_den that is
+ * negative or not finite (0 is accepted). */
+int lde_adabelief_flux_step(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps_var, float eps_den, float decay,
+                            int64_t step, void* stream);
+int lde_adabelief_flux_step_dev(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps_var, float eps_den,
+                                float decay, int64_t* step_dev, void* stream);
+int lde_adabelief_flux_step_guarded(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps_var, float eps_den,
+                                    float decay, int64_t* step_dev, int64_t* guard_dev, void* stream);
+int lde_adabelief_flux_step_clipped(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps_var, float eps_den,
+                                    float decay, float clip_norm, int clip_mode, int64_t* step_dev, int64_t* guard_dev,
+                                    void* ws_dev, float* norms_dev, void* stream);
 
 /* ====================================================================================================================
  * The one collective of the path. The reference's only parallelism is `EnsembleThreads()` over the

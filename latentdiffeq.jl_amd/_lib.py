@@ -35,7 +35,8 @@ EXPORTS = ["lde_abi_version", "lde_problem_desc_default", "lde_desc_error", "lde
            "lde_rnn_num_weights", "lde_rnn_create", "lde_rnn_destroy", "lde_rnn_set_weights", "lde_rnn_set_weights_device",
            "lde_rnn_reserve", "lde_rnn_forward", "lde_rnn_backward", "lde_rnn_last_error", "lde_rnn_backward_dx", "lde_rnn_backward_dw", "lde_refresh_weights",
            "lde_sample_forward", "lde_sample_backward", "lde_kl_forward", "lde_kl_backward", "lde_mse_forward",
-           "lde_mse_backward", "lde_sample_kl_forward", "lde_sample_kl_backward", "lde_mse_forward_add", "lde_adamw_flux_step", "lde_adamw_flux_step_dev", "lde_guard_init", "lde_adamw_flux_step_guarded", "lde_clip_ws_bytes", "lde_adamw_flux_step_clipped", "lde_set_dw_stream", "lde_join_dw",
+           "lde_mse_backward", "lde_sample_kl_forward", "lde_sample_kl_backward", "lde_mse_forward_add", "lde_adamw_flux_step", "lde_adamw_flux_step_dev", "lde_guard_init", "lde_adamw_flux_step_guarded", "lde_clip_ws_bytes", "lde_adamw_flux_step_clipped",
+           "lde_adabelief_flux_step", "lde_adabelief_flux_step_dev", "lde_adabelief_flux_step_guarded", "lde_adabelief_flux_step_clipped", "lde_set_dw_stream", "lde_join_dw",
            "lde_comm_unique_id", "lde_comm_init", "lde_comm_allreduce_f32", "lde_comm_nranks", "lde_comm_rank",
            "lde_comm_destroy", "lde_comm_last_error"]
 # lde_sum_hook: int hook(void* user, double* vals, int n) — vals[0..n) ← Σ over ranks, in place
@@ -221,6 +222,11 @@ def load():
     lib.lde_clip_ws_bytes.argtypes = [i32, C.POINTER(AdamTensor)]
     lib.lde_clip_ws_bytes.restype = C.c_size_t
     lib.lde_adamw_flux_step_clipped.argtypes = [i32, C.POINTER(AdamTensor), f32, f32, f32, f32, f32, f32, i32, vp, vp, vp, vp, vp]
+    # the AdaBelief step: the same four forms with (eps_var, eps_den) where ADAMW has eps
+    lib.lde_adabelief_flux_step.argtypes = [i32, C.POINTER(AdamTensor), f32, f32, f32, f32, f32, f32, i64, vp]
+    lib.lde_adabelief_flux_step_dev.argtypes = [i32, C.POINTER(AdamTensor), f32, f32, f32, f32, f32, f32, vp, vp]
+    lib.lde_adabelief_flux_step_guarded.argtypes = [i32, C.POINTER(AdamTensor), f32, f32, f32, f32, f32, f32, vp, vp, vp]
+    lib.lde_adabelief_flux_step_clipped.argtypes = [i32, C.POINTER(AdamTensor), f32, f32, f32, f32, f32, f32, f32, i32, vp, vp, vp, vp, vp]
     lib.lde_comm_unique_id.argtypes = [C.c_char_p]
     lib.lde_comm_init.argtypes = [C.POINTER(vp), i32, i32, C.c_char_p]
     lib.lde_comm_allreduce_f32.argtypes = [vp, vp, i64, vp]

@@ -854,6 +854,11 @@ static bool clip_args_ok(int n, const lde_adam_tensor* t, float beta1, float bet
   for (int i = 0; i < n; i++) any = any || t[i].n > 0;
   return !any || (ws_dev && (reinterpret_cast<uintptr_t>(ws_dev) & 7) == 0);
 }
+// what the AdaBelief step (lde_adabelief_flux_step*, include/lde.h: "the AdaBelief step") refuses on top of its ADAMW twin: an ε that is
+// negative or not finite (0 is allowed: the rule without the term)
+static bool belief_eps_ok(float eps_var, float eps_den) {
+  return eps_var >= 0.f && eps_den >= 0.f && std::isfinite(eps_var) && std::isfinite(eps_den);
+}
 
 static KOpts make_opts(const lde_problem_desc& d, const double* ts, int T, int B) {
   KOpts o;

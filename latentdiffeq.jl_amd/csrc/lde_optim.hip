@@ -326,6 +326,89 @@ __global__ void __launch_bounds__(OPT_WG) k_clip_finalise(const double* __restri
   }
 }
 
+// ---- the AdaBelief step (lde_adabelief_flux_step*, include/lde.h: "the AdaBelief step"): Flux's `Optimiser(AdaBelief(η, β), WeightDecay(decay))`,
+// the optimiser the reference's scripts name as the alternative [REF examples/pendulum_friction-less/model_train.jl:136-138]:
+//     m ← β₁·m + (1 − β₁)·g;   s ← β₂·s + (1 − β₂)·(g − m)² + ε_var  (the NEW m);   Δ = η·(m/(1 − β₁ᵗ))/(√(s/(1 − β₂ᵗ)) + ε_den) + decay·x;   x ← x − Δ
+// k_adamw_flux's geometry — the same table, a workgroup owns 2048 consecutive elements of one array, 16-byte accesses when all four
+// pointers are aligned, the scalar path for unaligned arrays and the ragged end, 28 bytes per element (`v` of the table holds s) — and
+// its three forms as ONE template (these kernels are new: they may share a body, see the comment above k_adamw_flux_clipped):
+// BELIEF_PLAIN (step_dev == nullptr: the coefficients arrive complete; otherwise the device-counted form), BELIEF_GUARDED (word [0] read
+// once per workgroup, the last workgroup of the last launch does guard_bookkeeping), BELIEF_CLIPPED (guarded, with g ← scale[i]·g as it
+// is loaded). The scans in front of the guarded and clipped forms are k_grad_guard / k_grad_norm_guard / k_clip_finalise themselves.
+// The counting-in has counters of its own, one per form: a step of this rule and an ADAMW step on another stream do not meet in one.
+// The arithmetic is written out operation by operation (two fused multiply-adds where the rule has a·b + c·d, nothing else contracted),
+// so that the three forms round alike: a clean guarded step is the device-counted one bit for bit, a clipped one with s = 1 the guarded.
+enum { BELIEF_PLAIN = 0, BELIEF_GUARDED = 1, BELIEF_CLIPPED = 2 };
+struct BeliefCoef { float b1, b2, omb1, omb2, inv_bc1, inv_bc2, eps_var, eps_den, lr, decay; };
+
+__device__ __forceinline__ void belief1(float& x, float g, float& m, float& s, const BeliefCoef& c) {
+#pragma clang fp contract(off)
+  m = __builtin_fmaf(c.b1, m, c.omb1 * g);
+  const float d = g - m;
+  s = __builtin_fmaf(c.b2, s, c.omb2 * d * d) + c.eps_var;
+  const float q = (m * c.inv_bc1) / (__builtin_sqrtf(s * c.inv_bc2) + c.eps_den);
+  x -= __builtin_fmaf(q, c.lr, c.decay * x);
+}
+
+__device__ unsigned g_belief_seen[3] = {0, 0, 0};
+template <int FORM>
+__global__ void __launch_bounds__(OPT_WG) k_adabelief_flux(OptTable tab, BeliefCoef c, int64_t* __restrict__ step_dev, int bump, int64_t* gw,
+                                                           const float* __restrict__ scale) {
+  if constexpr (FORM != BELIEF_PLAIN) {
+    __shared__ int64_t s_bad;
+    if (threadIdx.x == 0) s_bad = __hip_atomic_load(gw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int64_t ti = *step_dev + 1;
+    const double td = (double)ti;
+    c.inv_bc1 = (float)(1.0 / (1.0 - pow((double)c.b1, td)));
+    c.inv_bc2 = (float)(1.0 / (1.0 - pow((double)c.b2, td)));
+    __syncthreads();
+    const int64_t bad = s_bad;
+    if (bump && threadIdx.x == 0 && atomicAdd(&g_belief_seen[FORM], 1u) == gridDim.x - 1) {
+      guard_bookkeeping(gw, bad, step_dev, ti);
+      g_belief_seen[FORM] = 0;
+    }
+    if (bad != -1) return;
+  } else if (step_dev) {
+    const int64_t ti = *step_dev + 1;
+    const double td = (double)ti;
+    c.inv_bc1 = (float)(1.0 / (1.0 - pow((double)c.b1, td)));
+    c.inv_bc2 = (float)(1.0 / (1.0 - pow((double)c.b2, td)));
+    if (bump) {
+      __syncthreads();
+      if (threadIdx.x == 0 && atomicAdd(&g_belief_seen[FORM], 1u) == gridDim.x - 1) {
+        *step_dev = ti;
+        g_belief_seen[FORM] = 0;
+      }
+    }
+  }
+  int i = 0;
+  while (i + 1 < tab.n && (int)blockIdx.x >= tab.blk0[i + 1]) i++;
+  const lde_adam_tensor t = tab.t[i];
+  float sc = 1.0f;
+  if constexpr (FORM == BELIEF_CLIPPED) sc = scale[i];
+  const int64_t lo = (int64_t)((int)blockIdx.x - tab.blk0[i]) * OPT_PER_WG;
+  const int64_t hi = lo + OPT_PER_WG < t.n ? lo + OPT_PER_WG : t.n;
+  const bool al = ((((uintptr_t)t.p) | ((uintptr_t)t.g) | ((uintptr_t)t.m) | ((uintptr_t)t.v)) & 15) == 0;
+  int64_t e = lo + 4 * (int64_t)threadIdx.x;
+  if (al) {
+    for (; e + 4 <= hi; e += 4 * OPT_WG) {
+      f4 x = *reinterpret_cast<f4*>(t.p + e), m = *reinterpret_cast<f4*>(t.m + e), v = *reinterpret_cast<f4*>(t.v + e);
+      const f4 g = *reinterpret_cast<const f4*>(t.g + e);
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        float xq = x[q], mq = m[q], vq = v[q];
+        belief1(xq, FORM == BELIEF_CLIPPED ? sc * g[q] : g[q], mq, vq, c);
+        x[q] = xq; m[q] = mq; v[q] = vq;
+      }
+      *reinterpret_cast<f4*>(t.p + e) = x;
+      *reinterpret_cast<f4*>(t.m + e) = m;
+      *reinterpret_cast<f4*>(t.v + e) = v;
+    }
+  }
+  for (; e < hi; e += 4 * OPT_WG)   // unaligned arrays, and the ragged end
+    for (int q = 0; q < 4 && e + q < hi; q++) belief1(t.p[e + q], FORM == BELIEF_CLIPPED ? sc * t.g[e + q] : t.g[e + q], t.m[e + q], t.v[e + q], c);
+}
+
 }  // namespace lde
 
 using namespace lde;
@@ -346,14 +429,13 @@ static OptCoef opt_coef(float lr, float beta1, float beta2, float eps, float dec
   return c;
 }
 
-template <bool GUARD>
-static int adamw_impl(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps, float decay, int64_t step,
-                      int64_t* step_dev, int64_t* guard_dev, void* stream) {
+// The plan of the host-counted, device-counted and guarded forms, for either rule: `update(L, bump)` enqueues the rule's update kernel for
+// the launch L (`bump`: the step's last launch of a device-counted form — its last workgroup advances the count).
+template <bool GUARD, class Update>
+static int opt_impl(int n, const lde_adam_tensor* t, float beta1, float beta2, int64_t step, int64_t* step_dev, int64_t* guard_dev, void* stream,
+                    Update&& update) {
   if (!lde_host::opt_args_ok(n, t, beta1, beta2, step, step_dev)) return LDE_ERR_INVALID_ARG;
-  const OptCoef c = opt_coef(lr, beta1, beta2, eps, decay, step, step_dev);
-  GuardArg<GUARD> ga;
   if constexpr (GUARD) {
-    ga.w = guard_dev;
     // ALL scan launches go first — after a look at the update's plan: a call that will be refused launches nothing
     for (int first = 0; first < n;) {
       const lde_host::OptLaunch L = lde_host::opt_next_launch(n, t, first, OPT_PER_WG);
@@ -380,7 +462,7 @@ static int adamw_impl(int n, const lde_adam_tensor* t, float lr, float beta1, fl
       break;
     }
     launched = true;
-    hipLaunchKernelGGL(k_adamw_flux<GUARD>, dim3(L.blk0[L.n]), dim3(OPT_WG), 0, (hipStream_t)stream, opt_table(t, L), c, step_dev, (step_dev && L.last) ? 1 : 0, ga);
+    update(L, (step_dev && L.last) ? 1 : 0);
     if (hipGetLastError() != hipSuccess) return LDE_ERR_HIP;
   }
   if (step_dev && !launched) {
@@ -390,12 +472,24 @@ static int adamw_impl(int n, const lde_adam_tensor* t, float lr, float beta1, fl
   }
   return LDE_OK;
 }
+template <bool GUARD>
+static int adamw_impl(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps, float decay, int64_t step,
+                      int64_t* step_dev, int64_t* guard_dev, void* stream) {
+  const OptCoef c = opt_coef(lr, beta1, beta2, eps, decay, step, step_dev);
+  GuardArg<GUARD> ga;
+  if constexpr (GUARD) ga.w = guard_dev;
+  return opt_impl<GUARD>(n, t, beta1, beta2, step, step_dev, guard_dev, stream, [&](const lde_host::OptLaunch& L, int bump) {
+    hipLaunchKernelGGL(k_adamw_flux<GUARD>, dim3(L.blk0[L.n]), dim3(OPT_WG), 0, (hipStream_t)stream, opt_table(t, L), c, step_dev, bump, ga);
+  });
+}
 
 // The clipped step: every scan launch, the finalising kernel, every update launch — in that order on one stream (lde_host::clip_plan says
 // where each scan launch's partials and descriptors go; the update's launches meet the non-empty arrays in the same order, so launch
 // by launch they take the next L.n scales).
-static int adamw_clipped(int n, const lde_adam_tensor* t, const OptCoef& c, float clip_norm, int clip_mode, int64_t* step_dev, int64_t* guard_dev,
-                         void* ws_dev, float* norms_dev, hipStream_t stream) {
+// `update(L, bump, scale)` enqueues the rule's clipped update kernel for the launch L, `scale` = the scales of ITS arrays.
+template <class Update>
+static int opt_clipped(int n, const lde_adam_tensor* t, float clip_norm, int clip_mode, int64_t* step_dev, int64_t* guard_dev, void* ws_dev,
+                       float* norms_dev, hipStream_t stream, Update&& update) {
   const lde_host::ClipWs w = lde_host::clip_plan(n, t, [](const lde_host::OptLaunch&, int64_t, int64_t) {});
   char* const ws = static_cast<char*>(ws_dev);
   double* const part = w.nne ? reinterpret_cast<double*>(ws) : nullptr;
@@ -416,14 +510,12 @@ static int adamw_clipped(int n, const lde_adam_tensor* t, const OptCoef& c, floa
   a.c = clip_norm; a.mode = clip_mode;
   hipLaunchKernelGGL(k_clip_finalise, dim3(1), dim3(OPT_WG), 0, stream, part, sums, desc, scale, w.nne, n, norms_dev, a, word0);
   if (hipGetLastError() != hipSuccess) return LDE_ERR_HIP;
-  GuardArg<true> ga;
-  ga.w = guard_dev;
   int64_t ord0 = 0;
   for (int first = 0; first < n;) {
     const lde_host::OptLaunch L = lde_host::opt_next_launch(n, t, first, OPT_PER_WG);
     first = L.next;
     if (L.n == 0) break;
-    hipLaunchKernelGGL(k_adamw_flux_clipped, dim3(L.blk0[L.n]), dim3(OPT_WG), 0, stream, opt_table(t, L), c, step_dev, L.last ? 1 : 0, ga, scale + ord0);
+    update(L, L.last ? 1 : 0, scale + ord0);
     if (hipGetLastError() != hipSuccess) return LDE_ERR_HIP;
     ord0 += L.n;
   }
@@ -442,8 +534,13 @@ extern "C" int lde_adamw_flux_step_clipped(int n, const lde_adam_tensor* t, floa
                                            float clip_norm, int clip_mode, int64_t* step_dev, int64_t* guard_dev, void* ws_dev,
                                            float* norms_dev, void* stream) {
   if (!lde_host::clip_args_ok(n, t, beta1, beta2, clip_norm, clip_mode, step_dev, guard_dev, ws_dev, norms_dev)) return LDE_ERR_INVALID_ARG;
-  return adamw_clipped(n, t, opt_coef(lr, beta1, beta2, eps, decay, 0, step_dev), clip_norm, clip_mode, step_dev, guard_dev, ws_dev, norms_dev,
-                       (hipStream_t)stream);
+  const OptCoef c = opt_coef(lr, beta1, beta2, eps, decay, 0, step_dev);
+  GuardArg<true> ga;
+  ga.w = guard_dev;
+  return opt_clipped(n, t, clip_norm, clip_mode, step_dev, guard_dev, ws_dev, norms_dev, (hipStream_t)stream,
+                     [&](const lde_host::OptLaunch& L, int bump, const float* scale) {
+                       hipLaunchKernelGGL(k_adamw_flux_clipped, dim3(L.blk0[L.n]), dim3(OPT_WG), 0, (hipStream_t)stream, opt_table(t, L), c, step_dev, bump, ga, scale);
+                     });
 }
 
 extern "C" int lde_adamw_flux_step(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps, float decay,
@@ -464,4 +561,49 @@ extern "C" int lde_adamw_flux_step_guarded(int n, const lde_adam_tensor* t, floa
                                            int64_t* step_dev, int64_t* guard_dev, void* stream) {
   if (!step_dev || !guard_dev) return LDE_ERR_INVALID_ARG;
   return adamw_impl<true>(n, t, lr, beta1, beta2, eps, decay, 0, step_dev, guard_dev, stream);
+}
+
+// ---- the AdaBelief step: the four forms of the ADAMW step, through the same plans
+static BeliefCoef belief_coef(float lr, float beta1, float beta2, float eps_var, float eps_den, float decay, int64_t step, const int64_t* step_dev) {
+  BeliefCoef c;
+  c.b1 = beta1; c.b2 = beta2; c.omb1 = 1.0f - beta1; c.omb2 = 1.0f - beta2; c.eps_var = eps_var; c.eps_den = eps_den; c.lr = lr; c.decay = decay;
+  c.inv_bc1 = (float)(1.0 / (1.0 - __builtin_pow((double)beta1, (double)(step_dev ? 1 : step))));
+  c.inv_bc2 = (float)(1.0 / (1.0 - __builtin_pow((double)beta2, (double)(step_dev ? 1 : step))));
+  return c;
+}
+template <bool GUARD>
+static int belief_impl(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps_var, float eps_den, float decay, int64_t step,
+                       int64_t* step_dev, int64_t* guard_dev, void* stream) {
+  if (!lde_host::belief_eps_ok(eps_var, eps_den)) return LDE_ERR_INVALID_ARG;
+  const BeliefCoef c = belief_coef(lr, beta1, beta2, eps_var, eps_den, decay, step, step_dev);
+  return opt_impl<GUARD>(n, t, beta1, beta2, step, step_dev, guard_dev, stream, [&](const lde_host::OptLaunch& L, int bump) {
+    hipLaunchKernelGGL(k_adabelief_flux<GUARD ? BELIEF_GUARDED : BELIEF_PLAIN>, dim3(L.blk0[L.n]), dim3(OPT_WG), 0, (hipStream_t)stream, opt_table(t, L), c,
+                       step_dev, bump, guard_dev, (const float*)nullptr);
+  });
+}
+extern "C" int lde_adabelief_flux_step(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps_var, float eps_den, float decay,
+                                       int64_t step, void* stream) {
+  return belief_impl<false>(n, t, lr, beta1, beta2, eps_var, eps_den, decay, step, nullptr, nullptr, stream);
+}
+extern "C" int lde_adabelief_flux_step_dev(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps_var, float eps_den,
+                                           float decay, int64_t* step_dev, void* stream) {
+  if (!step_dev) return LDE_ERR_INVALID_ARG;
+  return belief_impl<false>(n, t, lr, beta1, beta2, eps_var, eps_den, decay, 0, step_dev, nullptr, stream);
+}
+extern "C" int lde_adabelief_flux_step_guarded(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps_var, float eps_den,
+                                               float decay, int64_t* step_dev, int64_t* guard_dev, void* stream) {
+  if (!step_dev || !guard_dev) return LDE_ERR_INVALID_ARG;
+  return belief_impl<true>(n, t, lr, beta1, beta2, eps_var, eps_den, decay, 0, step_dev, guard_dev, stream);
+}
+extern "C" int lde_adabelief_flux_step_clipped(int n, const lde_adam_tensor* t, float lr, float beta1, float beta2, float eps_var, float eps_den,
+                                               float decay, float clip_norm, int clip_mode, int64_t* step_dev, int64_t* guard_dev, void* ws_dev,
+                                               float* norms_dev, void* stream) {
+  if (!lde_host::belief_eps_ok(eps_var, eps_den)) return LDE_ERR_INVALID_ARG;
+  if (!lde_host::clip_args_ok(n, t, beta1, beta2, clip_norm, clip_mode, step_dev, guard_dev, ws_dev, norms_dev)) return LDE_ERR_INVALID_ARG;
+  const BeliefCoef c = belief_coef(lr, beta1, beta2, eps_var, eps_den, decay, 0, step_dev);
+  return opt_clipped(n, t, clip_norm, clip_mode, step_dev, guard_dev, ws_dev, norms_dev, (hipStream_t)stream,
+                     [&](const lde_host::OptLaunch& L, int bump, const float* scale) {
+                       hipLaunchKernelGGL(k_adabelief_flux<BELIEF_CLIPPED>, dim3(L.blk0[L.n]), dim3(OPT_WG), 0, (hipStream_t)stream, opt_table(t, L), c,
+                                          step_dev, bump, guard_dev, scale);
+                     });
 }

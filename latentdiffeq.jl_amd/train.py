@@ -137,65 +137,47 @@ def time_loader(x, full_seq_len: int, seq_len: int, rng: Optional[np.random.Gene
     return x[:, :, rand_time(full_seq_len, seq_len, rng)]
 
 
-class FluxADAMW(torch.optim.Adam):
-    """`ADAMW(η, (β₁, β₂), decay)` of the pinned Flux 0.13.6 [REF Manifest.toml:452] = `Optimiser(ADAM(η, β), WeightDecay(decay))`
-    [REF examples/pendulum_friction-less/model_train.jl:138]: Δ = η·m̂/(√v̂ + ε), then Δ += decay·x, then x −= Δ, i.e.
-    x ← (1 − decay)·x − ADAM step — the decay is NOT multiplied by η (torch.optim.AdamW applies lr·weight_decay·x: 1000× weaker at
-    the example's η = decay = 1e-3). ε = 1e-8 and the bias correction are Flux's = torch's.
-    On the GPU (`native`, the default when every parameter is a contiguous f32 HIP tensor) the whole update is ONE liblde.so launch
-    for all parameter arrays (lde_adamw_flux_step) — no per-step tensor grouping, step-counter kernels or separate decay pass;
-    otherwise one multi-tensor scale of the parameters followed by torch's Adam update with the gradients taken at the un-decayed
-    point (same arithmetic up to rounding; tests/test_gpu_optim.py compares the two). The native path bumps the parameters'
-    version counters after its launch (it writes through raw pointers), so `refresh_weights()` is optional after it too. Its
-    optimiser state keeps `step` as a Python int (a tensor step from a torch checkpoint is converted on entry); a native
-    state_dict is therefore not resumable by torch's FUSED Adam, which expects tensor steps.
-    `guard=True` (needs `capturable=True`): the step is lde_adamw_flux_step_guarded — every gradient is scanned on the device first, and
-    if any element of any array is NaN or ±Inf the whole update is withheld: no parameter, no moment and not the step count change (the
-    count is also the noise epoch of a captured step: the next replay draws the ε the withheld one drew). Otherwise the update is the
-    unguarded one bit for bit. `guard_state()` reads the counters. Several GPUs: the gradient all-reduce sits before the optimiser half,
-    and a sum with a NaN is NaN on every rank — all ranks withhold the same step; nothing is exchanged for it.
-    `clip_norm=c` clips the gradients by norm in front of the update: `clip_mode="global"` is torch's `clip_grad_norm_` — one scale
-    min(1, c/(‖g‖ + 1e-6)) from the norm of all gradients together; `"per_array"` is Flux's `Optimiser(ClipNorm(c), ADAMW(...))` — every
-    array whose own norm exceeds c is scaled to norm c. On the native path it needs `capturable=True, guard=True`: the step is
-    lde_adamw_flux_step_clipped (include/lde.h: "the clipped step") — the guard's scan also forms Σg², one small kernel turns the sums into
-    norms and scales, the update scales g as it loads it; no launch per array, nothing read by the host, the gradients in memory stay as
-    they were, and a norm that is not finite withholds the step like a NaN. Its workspace and the norms live at fixed addresses from
-    construction on, so the step can be captured. Off the native path (CPU tensors, `native=False`) the same two rules are applied with
-    torch ops in front of the step, to `p.grad` IN PLACE, as `clip_grad_norm_` does. `grad_norms()` reads the last step's norms."""
+class _FluxNativeStep:
+    """What FluxADAMW and FluxAdaBelief share: the one-launch native step in its four forms (host-counted, device-counted, guarded, clipped),
+    the device words that go with them, and the surface around them — `grad_norms()`, `guard_state()`, `withheld()`, the `state_dict` round
+    trip of the device step count. A mixin in front of a torch optimiser class; the rule's class says which entry points (`_ABI`), which
+    state key holds the second state array (`_SECOND`), what goes between β₂ and the decay in the call (`_eps_args`) and its name in
+    messages (`_NAME`)."""
+    _NAME = "FluxADAMW"
+    _ABI = "lde_adamw_flux_step"
+    _SECOND = "exp_avg_sq"
 
-    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), decay: float = 0.0, eps: float = 1e-8, fused=None, native=None,
-                 capturable: bool = False, guard: bool = False, clip_norm: Optional[float] = None, clip_mode: str = "global"):
+    def _eps_args(self, group):
+        return (group["eps"],)
+
+    @classmethod
+    def _check_options(cls, capturable, guard, clip_norm, clip_mode):
         if guard and not capturable:
-            raise ValueError("FluxADAMW(guard=True) needs capturable=True (the guard is part of the device-counted step)")
+            raise ValueError(f"{cls._NAME}(guard=True) needs capturable=True (the guard is part of the device-counted step)")
         if clip_mode not in L.CLIP_MODES:
-            raise ValueError(f"FluxADAMW(clip_mode={clip_mode!r}): one of {sorted(L.CLIP_MODES)}")
+            raise ValueError(f"{cls._NAME}(clip_mode={clip_mode!r}): one of {sorted(L.CLIP_MODES)}")
         if clip_norm is not None and not (math.isfinite(float(clip_norm)) and float(clip_norm) > 0.0):
-            raise ValueError("FluxADAMW(clip_norm=...) takes a finite threshold > 0 (None: no clipping)")
-        groups = list(params)
-        params = [p for g in groups for p in (g["params"] if isinstance(g, dict) else [g])]     # (arrays, or torch's group dicts)
-        on_gpu = bool(params) and all(p.is_cuda for p in params)
-        if fused is None:
-            fused = on_gpu
-        self.capturable = False             # (add_param_group runs inside the base constructor)
-        super().__init__(groups, lr=lr, betas=betas, eps=eps, weight_decay=0.0, fused=fused or None)
+            raise ValueError(f"{cls._NAME}(clip_norm=...) takes a finite threshold > 0 (None: no clipping)")
+
+    def _setup_native(self, params, on_gpu, decay, native, capturable, guard, clip_norm, clip_mode):
+        """Everything behind the base constructor: which path, and the device words of the capturable, guarded and clipped forms."""
         self.decay = float(decay)
         ok = on_gpu and all(p.dtype == torch.float32 and p.is_contiguous() for p in params)
         if native is None:
             native = ok and _NATIVE_ADAM
         if native and not ok:
-            raise ValueError("FluxADAMW(native=True) needs contiguous float32 HIP parameters")
+            raise ValueError(f"{self._NAME}(native=True) needs contiguous float32 HIP parameters")
         self.native = bool(native)
         # capturable (native only): the step count lives in ONE device int64 shared by all arrays (lde_adamw_flux_step_dev), so that the
         # update can sit inside a captured hipGraph (train.GraphedStep); every array must then have a gradient at every step
         self.capturable = bool(capturable)
         if self.capturable and not self.native:
-            raise ValueError("FluxADAMW(capturable=True) needs the native path")
+            raise ValueError(f"{self._NAME}(capturable=True) needs the native path")
         self._step_dev = torch.zeros((), dtype=torch.int64, device=params[0].device) if self.capturable else None
         if self.capturable:
             if len(self.param_groups) != 1:     # one device counter, bumped by every lde_adamw_flux_step_dev launch: one launch per step
-                raise ValueError("FluxADAMW(capturable=True) takes ONE parameter group")
-            from .loss import set_noise_epoch
-            set_noise_epoch(self._step_dev)     # a captured step's ε is keyed by this counter: fresh noise at every replay (loss.randn)
+                raise ValueError(f"{self._NAME}(capturable=True) takes ONE parameter group")
+            self.set_noise_epoch()              # a captured step's ε is keyed by this counter: fresh noise at every replay (loss.randn)
         # guard: LDE_GUARD_WORDS device words (in flight, skipped, streak, last_bad_array), initialised once; the kernels keep them
         self.guard = bool(guard)
         self._guard_dev = None
@@ -208,7 +190,7 @@ class FluxADAMW(torch.optim.Adam):
         self._clip_ws = self._norms_dev = self._norms_host = None
         if self.clip_norm is not None and self.native:
             if not (self.capturable and self.guard):
-                raise ValueError("FluxADAMW(clip_norm=...) on the native path needs capturable=True, guard=True "
+                raise ValueError(f"{self._NAME}(clip_norm=...) on the native path needs capturable=True, guard=True "
                                  "(the clipped step is the guarded, device-counted step with a scale in front of it)")
             tab = (L.AdamTensor * len(params))()
             for i, p in enumerate(params):
@@ -217,12 +199,20 @@ class FluxADAMW(torch.optim.Adam):
             self._clip_ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=params[0].device)
             self._norms_dev = torch.zeros(len(params) + 1, dtype=torch.float32, device=params[0].device)
 
+    def set_noise_epoch(self):
+        """Make this optimiser's device step count the noise epoch of a captured step's ε (loss.set_noise_epoch): the capturable form does
+        it at construction; call it again after another optimiser took the role."""
+        if not getattr(self, "capturable", False):
+            raise ValueError(f"{self._NAME}.set_noise_epoch() needs capturable=True")
+        from .loss import set_noise_epoch
+        set_noise_epoch(self._step_dev)
+
     def grad_norms(self):
         """(per-array list, total) — the gradient norms of the most recent `step()`, before clipping, in the parameter group's order: what
         the clipped step measured (include/lde.h: "the clipped step"; an empty array reads 0, the total is the norm of all gradients
         together in either mode). ONE device→host copy: a synchronisation with the device; not for every step of a captured run."""
         if self.clip_norm is None:
-            raise ValueError("FluxADAMW.grad_norms() needs clip_norm=")
+            raise ValueError(f"{self._NAME}.grad_norms() needs clip_norm=")
         if self._norms_dev is not None:
             w = self._norms_dev.tolist()
         elif self._norms_host is not None:
@@ -258,7 +248,7 @@ class FluxADAMW(torch.optim.Adam):
         most recent withheld update (−1: never). Read-only. ONE device→host copy: a synchronisation with the device; not for every step
         (GraphedStep looks every `check_every` replays). The counters are not part of `state_dict()`."""
         if not self.guard:
-            raise ValueError("FluxADAMW.guard_state() needs guard=True")
+            raise ValueError(f"{self._NAME}.guard_state() needs guard=True")
         w = self._guard_dev.tolist()
         return dict(skipped=int(w[1]), streak=int(w[2]), last_bad_array=int(w[3]))
 
@@ -269,7 +259,7 @@ class FluxADAMW(torch.optim.Adam):
         parameters, the moments, the step count and `guard_state()` stay what they were. Word [0] is raised by hand — the kernels see a
         scan that found something — and is −1 again after the step, as always."""
         if not self.guard:
-            raise ValueError("FluxADAMW.withheld() needs guard=True")
+            raise ValueError(f"{self._NAME}.withheld() needs guard=True")
         keep = self._guard_dev.clone()
         self._guard_dev[0:1].fill_(0)
         try:
@@ -279,7 +269,7 @@ class FluxADAMW(torch.optim.Adam):
 
     def add_param_group(self, param_group):
         if getattr(self, "capturable", False) and self.param_groups:
-            raise ValueError("FluxADAMW(capturable=True) takes ONE parameter group")
+            raise ValueError(f"{self._NAME}(capturable=True) takes ONE parameter group")
         super().add_param_group(param_group)
 
     def state_dict(self):
@@ -296,7 +286,7 @@ class FluxADAMW(torch.optim.Adam):
         if self.capturable:
             steps = [int(st["step"]) for st in self.state.values() if "step" in st]
             if steps and min(steps) != max(steps):
-                raise ValueError("FluxADAMW(capturable=True): the checkpoint's arrays have been updated unequally often")
+                raise ValueError(f"{self._NAME}(capturable=True): the checkpoint's arrays have been updated unequally often")
             self._step_dev.fill_(steps[0] if steps else 0)
             for st in self.state.values():
                 st.pop("step", None)
@@ -307,27 +297,27 @@ class FluxADAMW(torch.optim.Adam):
             for g in self.param_groups:
                 ps = g["params"]
                 if any(p.grad is None for p in ps):
-                    raise RuntimeError("FluxADAMW(capturable=True): every parameter needs a gradient at every step")
+                    raise RuntimeError(f"{self._NAME}(capturable=True): every parameter needs a gradient at every step")
                 keep = []
                 tab = (L.AdamTensor * len(ps))()
                 for i, p in enumerate(ps):
                     st, gr = self.state[p], p.grad
                     if not st:
-                        st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(p), torch.zeros_like(p)
+                        st["exp_avg"], st[self._SECOND] = torch.zeros_like(p), torch.zeros_like(p)
                     if gr.dtype != torch.float32 or not gr.is_contiguous():
                         gr = gr.float().contiguous()
                         keep.append(gr)
                     t = tab[i]
-                    t.p, t.g, t.m, t.v, t.n = p.data_ptr(), gr.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
+                    t.p, t.g, t.m, t.v, t.n = p.data_ptr(), gr.data_ptr(), st["exp_avg"].data_ptr(), st[self._SECOND].data_ptr(), p.numel()
                 if self.clip_norm is not None:
-                    L.call("lde_adamw_flux_step_clipped", None, len(ps), tab, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.decay,
+                    L.call(self._ABI + "_clipped", None, len(ps), tab, g["lr"], g["betas"][0], g["betas"][1], *self._eps_args(g), self.decay,
                            self.clip_norm, L.CLIP_MODES[self.clip_mode], L.ptr(self._step_dev), L.ptr(self._guard_dev),
                            L.ptr(self._clip_ws), L.ptr(self._norms_dev), L.raw_stream(ps[0].device.index))
                 elif self.guard:
-                    L.call("lde_adamw_flux_step_guarded", None, len(ps), tab, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.decay,
+                    L.call(self._ABI + "_guarded", None, len(ps), tab, g["lr"], g["betas"][0], g["betas"][1], *self._eps_args(g), self.decay,
                            L.ptr(self._step_dev), L.ptr(self._guard_dev), L.raw_stream(ps[0].device.index))
                 else:
-                    L.call("lde_adamw_flux_step_dev", None, len(ps), tab, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.decay,
+                    L.call(self._ABI + "_dev", None, len(ps), tab, g["lr"], g["betas"][0], g["betas"][1], *self._eps_args(g), self.decay,
                            L.ptr(self._step_dev), L.raw_stream(ps[0].device.index))
                 torch.autograd.graph.increment_version(ps)
             return
@@ -339,7 +329,7 @@ class FluxADAMW(torch.optim.Adam):
             for p in ps:
                 st = self.state[p]
                 if not st:
-                    st["step"], st["exp_avg"], st["exp_avg_sq"] = 0, torch.zeros_like(p), torch.zeros_like(p)
+                    st["step"], st["exp_avg"], st[self._SECOND] = 0, torch.zeros_like(p), torch.zeros_like(p)
                 # a state loaded from a torch / fused Adam checkpoint carries `step` as a tensor: normalise to a Python int (the
                 # native state is not resumable by torch's fused Adam, which wants tensor steps — documented in the class docstring)
                 st["step"] = int(st["step"]) + 1
@@ -353,12 +343,51 @@ class FluxADAMW(torch.optim.Adam):
                         gr = gr.float().contiguous()
                         keep.append(gr)
                     t = tab[i]
-                    t.p, t.g, t.m, t.v, t.n = p.data_ptr(), gr.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
-                L.call("lde_adamw_flux_step", None, len(group), tab, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.decay, t_step,
+                    t.p, t.g, t.m, t.v, t.n = p.data_ptr(), gr.data_ptr(), st["exp_avg"].data_ptr(), st[self._SECOND].data_ptr(), p.numel()
+                L.call(self._ABI, None, len(group), tab, g["lr"], g["betas"][0], g["betas"][1], *self._eps_args(g), self.decay, t_step,
                        L.raw_stream(group[0].device.index))
                 # the kernel wrote through raw pointers: tell torch the parameters changed in place, so that `_lib.weights_key`
                 # (data_ptr, _version) — which lets a module skip its weight upload — and autograd's saved-tensor checks see it
                 torch.autograd.graph.increment_version(group)
+
+
+class FluxADAMW(_FluxNativeStep, torch.optim.Adam):
+    """`ADAMW(η, (β₁, β₂), decay)` of the pinned Flux 0.13.6 [REF Manifest.toml:452] = `Optimiser(ADAM(η, β), WeightDecay(decay))`
+    [REF examples/pendulum_friction-less/model_train.jl:138]: Δ = η·m̂/(√v̂ + ε), then Δ += decay·x, then x −= Δ, i.e.
+    x ← (1 − decay)·x − ADAM step — the decay is NOT multiplied by η (torch.optim.AdamW applies lr·weight_decay·x: 1000× weaker at
+    the example's η = decay = 1e-3). ε = 1e-8 and the bias correction are Flux's = torch's.
+    On the GPU (`native`, the default when every parameter is a contiguous f32 HIP tensor) the whole update is ONE liblde.so launch
+    for all parameter arrays (lde_adamw_flux_step) — no per-step tensor grouping, step-counter kernels or separate decay pass;
+    otherwise one multi-tensor scale of the parameters followed by torch's Adam update with the gradients taken at the un-decayed
+    point (same arithmetic up to rounding; tests/test_gpu_optim.py compares the two). The native path bumps the parameters'
+    version counters after its launch (it writes through raw pointers), so `refresh_weights()` is optional after it too. Its
+    optimiser state keeps `step` as a Python int (a tensor step from a torch checkpoint is converted on entry); a native
+    state_dict is therefore not resumable by torch's FUSED Adam, which expects tensor steps.
+    `guard=True` (needs `capturable=True`): the step is lde_adamw_flux_step_guarded — every gradient is scanned on the device first, and
+    if any element of any array is NaN or ±Inf the whole update is withheld: no parameter, no moment and not the step count change (the
+    count is also the noise epoch of a captured step: the next replay draws the ε the withheld one drew). Otherwise the update is the
+    unguarded one bit for bit. `guard_state()` reads the counters. Several GPUs: the gradient all-reduce sits before the optimiser half,
+    and a sum with a NaN is NaN on every rank — all ranks withhold the same step; nothing is exchanged for it.
+    `clip_norm=c` clips the gradients by norm in front of the update: `clip_mode="global"` is torch's `clip_grad_norm_` — one scale
+    min(1, c/(‖g‖ + 1e-6)) from the norm of all gradients together; `"per_array"` is Flux's `Optimiser(ClipNorm(c), ADAMW(...))` — every
+    array whose own norm exceeds c is scaled to norm c. On the native path it needs `capturable=True, guard=True`: the step is
+    lde_adamw_flux_step_clipped (include/lde.h: "the clipped step") — the guard's scan also forms Σg², one small kernel turns the sums into
+    norms and scales, the update scales g as it loads it; no launch per array, nothing read by the host, the gradients in memory stay as
+    they were, and a norm that is not finite withholds the step like a NaN. Its workspace and the norms live at fixed addresses from
+    construction on, so the step can be captured. Off the native path (CPU tensors, `native=False`) the same two rules are applied with
+    torch ops in front of the step, to `p.grad` IN PLACE, as `clip_grad_norm_` does. `grad_norms()` reads the last step's norms."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), decay: float = 0.0, eps: float = 1e-8, fused=None, native=None,
+                 capturable: bool = False, guard: bool = False, clip_norm: Optional[float] = None, clip_mode: str = "global"):
+        self._check_options(capturable, guard, clip_norm, clip_mode)
+        groups = list(params)
+        params = [p for g in groups for p in (g["params"] if isinstance(g, dict) else [g])]     # (arrays, or torch's group dicts)
+        on_gpu = bool(params) and all(p.is_cuda for p in params)
+        if fused is None:
+            fused = on_gpu
+        self.capturable = False             # (add_param_group runs inside the base constructor)
+        super().__init__(groups, lr=lr, betas=betas, eps=eps, weight_decay=0.0, fused=fused or None)
+        self._setup_native(params, on_gpu, decay, native, capturable, guard, clip_norm, clip_mode)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -382,6 +411,96 @@ class FluxADAMW(torch.optim.Adam):
                     torch._foreach_mul_(ps, 1.0 - self.decay)
         super().step()
         return loss
+
+
+class FluxAdaBelief(_FluxNativeStep, torch.optim.Optimizer):
+    """`AdaBelief(η, (β₁, β₂))` — the optimiser the reference's training scripts name as the alternative to ADAMW
+    [REF examples/pendulum_friction-less/model_train.jl:136-138] — as `Optimiser(AdaBelief(η, β), WeightDecay(decay))`:
+    m ← β₁m + (1−β₁)g; s ← β₂s + (1−β₂)(g − m)² + ε_var (the new m); Δ = η·m̂/(√ŝ + ε_den) + decay·x; x ← x − Δ (include/lde.h: "the
+    AdaBelief step"; the decay is not scaled by η, as in FluxADAMW). `eps`: a number ε means ε_var = ε_den = ε² — Flux 0.13.6's placement
+    AS RECALLED (its source is not available to this project: UNPINNED); a pair is (ε_var, ε_den) as given — the paper's placement is
+    `eps=(1e-8, 1e-8)`, or whatever ε it is run with.
+    Everything else is FluxADAMW's, with the same rules and messages under this class's name: `native` (the default when every parameter
+    is a contiguous f32 HIP tensor) makes the whole update ONE liblde.so launch (lde_adabelief_flux_step); `capturable=True` keeps the step
+    count on the device (…_step_dev) so that the update can sit in a captured step (GraphedStep); `guard=True` scans the gradients first
+    and withholds the update when one is not finite (…_step_guarded; `guard_state()`, `withheld()`, and `GraphedStep(guard=opt)` takes
+    it); `clip_norm=c` with `clip_mode` clips by norm in front of the update (…_step_clipped; `grad_norms()`). The scans are the ADAMW
+    step's own kernels. State keys: `exp_avg`, `exp_avg_var`, `step`. Off the native path (CPU tensors, `native=False`) the rule is applied
+    with torch ops — torch.optim has no AdaBelief — in the arithmetic of the parameters' dtype, the constants rounded to f32 the way the C
+    ABI receives them; clipping then happens in front, on `p.grad` in place, as in FluxADAMW."""
+    _NAME = "FluxAdaBelief"
+    _ABI = "lde_adabelief_flux_step"
+    _SECOND = "exp_avg_var"
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps=1e-8, decay: float = 0.0, native=None, capturable: bool = False,
+                 guard: bool = False, clip_norm: Optional[float] = None, clip_mode: str = "global"):
+        self._check_options(capturable, guard, clip_norm, clip_mode)
+        if not (float(lr) >= 0.0 and math.isfinite(float(lr))):
+            raise ValueError(f"FluxAdaBelief(lr={lr!r}): a finite learning rate >= 0")
+        if not (len(betas) == 2 and all(0.0 <= float(b) < 1.0 for b in betas)):
+            raise ValueError(f"FluxAdaBelief(betas={betas!r}): two numbers in [0, 1)")
+        self._split_eps(eps)
+        groups = list(params)
+        params = [p for g in groups for p in (g["params"] if isinstance(g, dict) else [g])]     # (arrays, or torch's group dicts)
+        on_gpu = bool(params) and all(p.is_cuda for p in params)
+        self.capturable = False             # (add_param_group runs inside the base constructor)
+        super().__init__(groups, dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=eps))
+        self._setup_native(params, on_gpu, decay, native, capturable, guard, clip_norm, clip_mode)
+
+    @staticmethod
+    def _split_eps(eps):
+        """(ε_var, ε_den) of `eps`: a number ε → (ε², ε²); a pair as given. Both finite and ≥ 0."""
+        try:
+            pair = tuple(float(e) for e in eps) if isinstance(eps, (tuple, list)) else (float(eps) ** 2,) * 2
+            ok = len(pair) == 2 and all(math.isfinite(e) and e >= 0.0 for e in pair) and (isinstance(eps, (tuple, list)) or float(eps) >= 0.0)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"FluxAdaBelief(eps={eps!r}): a finite number >= 0, or a pair (eps_var, eps_den) of them")
+        return pair
+
+    def _eps_args(self, group):
+        return self._split_eps(group["eps"])
+
+    @torch.no_grad()
+    def _torch_step(self):
+        """The rule with torch ops, operation for operation what tests/belief_ref.py states (without the kernel's fused multiply-adds)."""
+        f32 = np.float32
+        for g in self.param_groups:
+            b1, b2 = f32(g["betas"][0]), f32(g["betas"][1])
+            omb1, omb2 = float(f32(1.0) - b1), float(f32(1.0) - b2)
+            eps_var, eps_den = (float(f32(e)) for e in self._split_eps(g["eps"]))
+            lr, decay = float(f32(g["lr"])), float(f32(self.decay))
+            for p in g["params"]:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                if not st:
+                    st["step"], st["exp_avg"], st["exp_avg_var"] = 0, torch.zeros_like(p), torch.zeros_like(p)
+                st["step"] = t = int(st["step"]) + 1
+                inv_bc1 = float(f32(1.0 / (1.0 - float(b1) ** t)))
+                inv_bc2 = float(f32(1.0 / (1.0 - float(b2) ** t)))
+                m, s, gr = st["exp_avg"], st["exp_avg_var"], p.grad.to(p.dtype)
+                m.mul_(float(b1)).add_(gr * omb1)
+                d = gr - m
+                s.mul_(float(b2)).add_(d * omb2 * d).add_(eps_var)
+                q = (m * inv_bc1) / ((s * inv_bc2).sqrt() + eps_den)
+                p.sub_(q * lr + p * decay)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self.native:
+            self._native_step()
+            return loss
+        if self.clip_norm is not None:
+            self._clip_with_torch()
+        self._torch_step()
+        return loss
+
 
 
 class GraphedStep:
@@ -492,20 +611,24 @@ def train(model: LatentDiffEqModel, loader_train: Iterable, val_set, dt: float, 
           lr: float = 1e-3, decay: float = 1e-10, start_beta: float = 0.0, end_beta: float = 1.0, n_cycle: int = 3, ratio: float = 0.9,
           progressive_training: bool = False, prog_training_duration: int = 0, start_seq_len: int = 0, variational: bool = True,
           rng: Optional[np.random.Generator] = None, on_epoch: Optional[Callable] = None, grad_sync: Optional[Callable] = None,
-          clip_norm: Optional[float] = None, clip_mode: str = "global"):
+          clip_norm: Optional[float] = None, clip_mode: str = "global", optimiser: str = "adamw"):
     """The epoch loop of the example script  [REF examples/pendulum_friction-less/model_train.jl:138-218]: cyclical β, optional
     progressive sequence length, Flux-flavour ADAMW, validation loss after every minibatch, best weights kept. `loader_train` yields
     x [pixels, B, full_seq_len] tensors on the model's device; `grad_sync` is called between backward and the optimiser step
     (dist.FlatGradAllReduce for multi-GPU). `clip_norm` (with `clip_mode`, see FluxADAMW): the gradients are clipped by norm in front of
     every update — on the GPU the optimiser is then built in its capturable, guarded, clipped form (one submission per step, a step with
     non-finite gradients or norms is withheld) and is left in `model.optimizer`, where `grad_norms()` and `guard_state()` can be read;
-    None: the loop as it was. Returns (history, best_state)."""
+    None: the loop as it was. `optimiser`: "adamw" (the scripts' choice) or "adabelief" — FluxAdaBelief, the alternative they name
+    [REF model_train.jl:136-138], with the same η, β and decay. Returns (history, best_state)."""
+    if optimiser not in ("adamw", "adabelief"):
+        raise ValueError(f"train(optimiser={optimiser!r}): 'adamw' or 'adabelief'")
+    Opt = FluxADAMW if optimiser == "adamw" else FluxAdaBelief
     params = model.parameters()
     if clip_norm is None:
-        opt = FluxADAMW(params, lr=lr, betas=(0.9, 0.999), decay=decay)      # ADAMW(η, (0.9, 0.999), decay), Flux flavour
+        opt = Opt(params, lr=lr, betas=(0.9, 0.999), decay=decay)      # ADAMW(η, (0.9, 0.999), decay), Flux flavour
     else:
         on_gpu = bool(params) and all(p.is_cuda for p in params)
-        opt = FluxADAMW(params, lr=lr, betas=(0.9, 0.999), decay=decay, capturable=on_gpu, guard=on_gpu, clip_norm=clip_norm, clip_mode=clip_mode)
+        opt = Opt(params, lr=lr, betas=(0.9, 0.999), decay=decay, capturable=on_gpu, guard=on_gpu, clip_norm=clip_norm, clip_mode=clip_mode)
         model.optimizer = opt
     schedule = frange_cycle_linear(epochs, start_beta, end_beta, n_cycle, ratio)
     if progressive_training:
