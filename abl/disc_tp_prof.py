@@ -13,7 +13,17 @@ to the sweep's end, 4.5 per launch back to back. What was tried on the way (each
   the sweep as a chain of 21 map applications — value passed by v_readlane → scalar → VALU: 92 cycles per step; by DPP wave_shl:1: 100; by DPP
   row_shl:1 within rows: 110 (one wave per SIMD: every dependent instruction's latency is exposed) — as a suffix scan of the maps: 530 cycles;
   the save times of a step walked by every one of its three lanes: 2700 cycles (the longest step of the trajectory decides: 3 round trips
-  of 4) — shared between the three lanes and added up in LDS: 2000."""
+  of 4) — shared between the three lanes and added up in LDS: 2000.
+
+Round 7 (profiles/r7_disc_tp_stamps.txt: the commit before and this one on one box, cycles): the kernel arguments read at entry and the first
+round's nine global loads issued unconditionally at clamped indices: loads 1948 → 873–934; the save-time phase as straight-line code (one
+batch of LDS reads, & / | instead of && / ||, selects; the ragged-grid walk and further trips behind wave votes): save times 2011 → 1572;
+entry → sweep done 7484 → 5773 (3.22 → 2.50 µs), 4.49 → 4.06 µs per launch back to back in the prof build. What the compiler makes of
+k_pend_adjoint_disc_tp<0, 0> (hipcc -O3 --offload-arch=gfx950 -S; before → after): 1147 → 1243 instructions, s_and_saveexec_b64 23 → 11,
+s_cbranch_execz 21 → 15, v_mov_b64 30 → 7; s_load 11 in eight groups with seven s_waitcnt lgkmcnt(0) in series in front of the round loop
+→ 9, all in front of the first global_load with one wait; no exec-masked block around a first-round load (the nine global_load follow
+each other, one s_waitcnt vmcnt(0)); on the one-trip path of the save-time phase ten ds_read_b64 and one s_waitcnt lgkmcnt(0) in front
+of the four bodies and no s_and_saveexec_b64 inside them."""
 import ctypes as C
 import os
 import subprocess

@@ -5,7 +5,12 @@ stepping wave and of the three dense-output waves from a -DLDE_PEND_PROF=1 build
 
 Stamps (workgroup 0; shader clock = __builtin_readcyclecounter, wall = 100 MHz): 8 stepper entry, 9 stepping loop starts (inputs loaded,
 k₁ = f(y₀) and the Hairer initial step — two evaluations, two pow — done), 10 loop ended, 11 stepper done; 12–14 dense-output wave i has
-stored its last save. DESIGN.md §9 prices the metric's floor with these numbers."""
+stored its last save. DESIGN.md §9 prices the metric's floor with these numbers.
+
+Round 7 (profiles/r7_metric_floor.txt: the commit before and this one on one box): the kernel arguments the stepping wave uses are read at
+kernel entry, in front of the first barrier — prologue 1154 → 1069 cycles, exit 2265 → 2185, the loop unchanged (585 → 586 per step). What
+the compiler makes of k_pend_forward_lp<true, 4> (hipcc -O3 --offload-arch=gfx950 -S; before → after): 1043 → 1033 instructions, s_load
+15 → 12, of them behind the first global_load (the stepper's path after the barrier, the record's replay) 7 → 0."""
 import ctypes as C
 import os
 import subprocess

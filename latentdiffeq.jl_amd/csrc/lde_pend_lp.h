@@ -144,6 +144,24 @@ __global__ void __launch_bounds__(64 * (1 + NH)) k_pend_forward_lp(const float2*
   const bool valid = b < B;
   const int bc = valid ? b : B - 1;
   const double t_first = o.t_first, tend = o.t_last;
+  // Every kernel argument the stepping wave uses, read HERE (inputs of one empty asm: requested back to back, waited for once, under the
+  // loads of z₀ and L and the barrier below): left to the compiler, the controller's constants and the record's pointers are fetched
+  // where they are first needed — scalar loads with a wait each on the stepper's own path between the barrier and the first step, and
+  // again between the last step and the record's stores. Stepper prologue 1 154 → 1 069 cycles, exit 2 265 → 2 185 (abl/metric_floor.py);
+  // the kernel alone 7.24 → 7.10 µs (rocprofv3 averages); on the pipelined step of the metric this is inside the run-to-run spread
+  // (the launch's tail is the dense-output waves', not the stepper's exit).
+  const float o_abstol = o.abstol, o_reltol = o.reltol, o_beta1 = o.beta1, o_beta2 = o.beta2, o_inv_gamma = o.inv_gamma, o_q_lo = o.q_lo,
+              o_q_hi = o.q_hi, o_qmin = o.qmin;
+  const double o_dtmin = o.dtmin, o_dt_fixed = o.dt_fixed;
+  const long long o_maxiters = o.maxiters;
+  const int rec_cap = o.rec.cap;
+  int32_t* const rec_n = o.rec.n;
+  double *const rec_t = o.rec.t, *const rec_dt = o.rec.dt;
+  float2* const rec_y = reinterpret_cast<float2*>(o.rec.y);
+  asm volatile("" ::"s"(o_abstol), "s"(o_reltol), "s"(o_beta1), "s"(o_beta2), "s"(o_inv_gamma), "s"(o_q_lo), "s"(o_q_hi), "s"(o_qmin), "s"(o_dtmin),
+               "s"(o_dt_fixed), "s"(o_maxiters), "s"(T), "s"(B), "s"(chunk), "s"(t_first), "s"(tend), "s"(z0), "s"(theta), "s"(ts_g), "s"(z_out),
+               "s"(retcode), "s"(st_nfe), "s"(st_nacc), "s"(st_nrej), "s"(st_ret));
+  if (REC) asm volatile("" ::"s"(rec_cap), "s"(rec_n), "s"(rec_t), "s"(rec_dt), "s"(rec_y));
   const float2 zi = z0[bc];
   PendFwd<0> f(theta[bc]);
   const float ngl = f.ngl;
@@ -178,9 +196,9 @@ __global__ void __launch_bounds__(64 * (1 + NH)) k_pend_forward_lp(const float2*
     const float glt = ngl * INV_2PI;   // −g/L per turn: the stepper's state is in TURNS — ξ = x/2π (even lanes), ω = v/2π (odd lanes)
     // the controller works on 1/q = γ·2^(β₂·l_old − β₁·l), l = log₂ EEst = ½·log₂ m2 − ½, clamped to [qmin, qmax]: in terms of lg = log₂ m2,
     // 1/q = 2^(cb·lg_old − ca·lg + c0) with ca = β₁/2, cb = β₂/2, c0 = log₂ γ + (β₁ − β₂)/2 — one fma, one v_exp_f32, one v_med3_f32 (no reciprocal)
-    const float ca = 0.5f * o.beta1, cb = 0.5f * o.beta2, c0 = 0.5f * (o.beta1 - o.beta2) - log2f(o.inv_gamma);
-    const float iq_lo = o.qmin, iq_hi = 1.0f / o.q_lo;
-    float abst = o.abstol * INV_2PI, relt = o.reltol;   // (the scaled error is a ratio: abstol in the state's unit)
+    const float ca = 0.5f * o_beta1, cb = 0.5f * o_beta2, c0 = 0.5f * (o_beta1 - o_beta2) - log2f(o_inv_gamma);
+    const float iq_lo = o_qmin, iq_hi = 1.0f / o_q_lo;
+    float abst = o_abstol * INV_2PI, relt = o_reltol;   // (the scaled error is a ratio: abstol in the state's unit)
     asm volatile("" : "+v"(abst), "+v"(relt));   // (kept in registers: as kernel-argument scalars two of them in one v_fma need a copy per step)
 
     int ret = LDE_RET_SUCCESS, nfe = 0, nacc = 0, nrej = 0;
@@ -189,14 +207,14 @@ __global__ void __launch_bounds__(64 * (1 + NH)) k_pend_forward_lp(const float2*
     constexpr float LQ_MIN = -13.287712379549449f;   // log₂ of qoldinit = 1e-4
     constexpr float LG_MIN = 2.0f * LQ_MIN + 1.0f;   // the same bound on lg = log₂ m2 = 2·l + 1
     float lgold = LG_MIN;
-    const int maxit = o.maxiters > 0x7fffffffLL ? 0x7fffffff : (int)o.maxiters;
-    const float dtmin = (float)o.dtmin;
+    const int maxit = o_maxiters > 0x7fffffffLL ? 0x7fffffff : (int)o_maxiters;
+    const float dtmin = (float)o_dtmin;
     if (valid && lane == 0) z_out[b] = zi;  // ts[0] is saved as ẑ₀ itself
     const double dtmax_d = tend - t;
     const float dtmax = (float)dtmax_d;
     float s1 = hw_sin(zi.x, turn_anchor(zi.x));   // σ₁ = sin x₀ (uniform)
     nfe = 1;
-    if (o.dt_fixed > 0) dt = (float)fmin(o.dt_fixed, dtmax_d);
+    if (o_dt_fixed > 0) dt = (float)fmin(o_dt_fixed, dtmax_d);
     else {
       f.anchor(zi.x);
       const float ya[2] = {zi.x, zi.y}, fa[2] = {zi.y, ngl * s1};
@@ -272,10 +290,10 @@ __global__ void __launch_bounds__(64 * (1 + NH)) k_pend_forward_lp(const float2*
           nrej++;
           lim--;
           if (!fin) {
-            if (__any(h > dtmin)) dt = h * o.qmin;
+            if (__any(h > dtmin)) dt = h * o_qmin;
             else { ret = LDE_RET_NONFINITE; active = false; nrej--; }
           } else {
-            dt = h * fast_rcp(fminf(o.q_hi, __builtin_amdgcn_exp2f(o.beta1 * fmaf(0.5f, lg, -0.5f)) * o.inv_gamma));
+            dt = h * fast_rcp(fminf(o_q_hi, __builtin_amdgcn_exp2f(o_beta1 * fmaf(0.5f, lg, -0.5f)) * o_inv_gamma));
             if (__any(dt < dtmin)) { ret = LDE_RET_DTMIN; active = false; }
           }
           last = __any(dt >= rem * 0.99999988f);   // (t has not moved)
@@ -325,10 +343,10 @@ __global__ void __launch_bounds__(64 * (1 + NH)) k_pend_forward_lp(const float2*
           if (lane == i) ti = tacc;
           tacc += (double)__int_as_float(__builtin_amdgcn_readlane(hbits, i));
         }
-        if (valid && mine && i0 + lane < o.rec.cap) {
-          o.rec.t[(size_t)(i0 + lane) * B + b] = ti;
-          o.rec.dt[(size_t)(i0 + lane) * B + b] = (double)hi;
-          reinterpret_cast<float2*>(o.rec.y)[(size_t)(i0 + lane) * B + b] = ys;
+        if (valid && mine && i0 + lane < rec_cap) {
+          rec_t[(size_t)(i0 + lane) * B + b] = ti;
+          rec_dt[(size_t)(i0 + lane) * B + b] = (double)hi;
+          rec_y[(size_t)(i0 + lane) * B + b] = ys;
         }
       }
       if (!active) break;
@@ -350,7 +368,7 @@ __global__ void __launch_bounds__(64 * (1 + NH)) k_pend_forward_lp(const float2*
       st_nfe[b] = nfe + NS * (nacc + nrej);
       st_nacc[b] = nacc;
       st_nrej[b] = nrej;
-      if (REC) o.rec.n[b] = ret == LDE_RET_SUCCESS ? nacc : 0;
+      if (REC) rec_n[b] = ret == LDE_RET_SUCCESS ? nacc : 0;
     }
     LPPROF(11);
     return;

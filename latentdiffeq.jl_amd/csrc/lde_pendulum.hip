@@ -1929,10 +1929,19 @@ __global__ void __launch_bounds__(64) k_pend_adjoint_disc_tp(const float2* __res
                                                              int32_t* __restrict__ st_nacc, int32_t* __restrict__ st_nrej,
                                                              int32_t* __restrict__ st_ret) {
   extern __shared__ __attribute__((aligned(16))) double s_lds[];   // the save grid [T] | this trajectory's Δẑ [T] | partial sums [66][12]
-  const int T = o.T, B = o.B, lane = threadIdx.x;
+  // ---- the kernel arguments, every one the kernel uses, read HERE: left to the compiler each is fetched where it is first needed — eight
+  // groups of scalar loads, seven waits in series, the vector loads spread between them (the 228-byte block spans four cache lines). As
+  // inputs of one empty asm they are all requested back to back and waited for once (nine s_load, one wait, in front of the first
+  // global load). Together with the unconditional loads below: entry → loads landed 1 948 → ≈ 900 cycles (abl/disc_tp_prof.py).
+  const int T = o.T, B = o.B, cap = o.rec.cap, lane = threadIdx.x, nwg = gridDim.x;
+  const int32_t* const rec_n = o.rec.n;
+  const double *const rec_t = o.rec.t, *const rec_dt = o.rec.dt;
+  const float2* const rec_y = reinterpret_cast<const float2*>(o.rec.y);
+  asm volatile("" ::"s"(z_out), "s"(theta), "s"(ts_g), "s"(dz_out), "s"(dz0), "s"(dtheta), "s"(st_nfe), "s"(st_nacc), "s"(st_nrej), "s"(st_ret),
+               "s"(rec_n), "s"(rec_t), "s"(rec_dt), "s"(rec_y), "s"(T), "s"(B), "s"(cap), "s"(nwg));
   // trajectory ↔ workgroup as in k_pend_forward_sh (the grid is a multiple of 8): the workgroup lands on the XCD whose L2 holds the
   // record and the ẑ the forward launch wrote for this trajectory
-  const int b = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const int b = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
   if (b >= B) return;
   double* s_t = s_lds;
   float2* s_d = reinterpret_cast<float2*>(s_lds + T);
@@ -1941,25 +1950,24 @@ __global__ void __launch_bounds__(64) k_pend_adjoint_disc_tp(const float2* __res
   constexpr float RK[5][4] = {{0.f, 0.f, 0.f, 0.f}, {0.5f, 0.f, 0.f, 0.f}, {0.f, 0.5f, 0.f, 0.f}, {0.f, 0.f, 1.f, 0.f},
                               {1.0f / 6.0f, 1.0f / 3.0f, 1.0f / 3.0f, 1.0f / 6.0f}};
   auto A = [&](int i, int q) -> float { return SOLVER == LDE_SOLVER_TSIT5 ? ts5::A[i][q] : RK[i][q]; };
-  const StepRec& R = o.rec;
   const int sl = (lane * 43) >> 7, tau = lane - 3 * sl;   // lane = 3·(step of the round) + tangent
   PPROF(0);
-  // ---- everything whose address is known now: the save grid, Δẑ, the record's first round, the step count
+  // ---- everything whose address is known now: the save grid, Δẑ, the record's first round, the step count — nine loads, every one
+  // UNCONDITIONAL from a clamped index (B, T, cap ≥ 1: inside the buffers of this call) and opaque to the compiler once loaded: a load
+  // under its lane condition is an exec-masked block of its own with a wait in front of the next (csrc/lde_mlp64.h: the c3 prologue).
+  // What a lane without a save time or without a step of the first round loads is never used: the LDS fill is guarded, and t, tnew of
+  // a lane enter the save-time phase under `act` only (h and y of such a lane are zeroed in the round).
   const bool j0ok = lane < T;
-  const double tsv = j0ok ? ts_g[lane] : 0.0;
-  const float2 dv = j0ok ? dz_out[(size_t)lane * B + b] : make_float2(0.f, 0.f);
-  const int spec_ok = sl < DTP_STEPS && sl < R.cap;
-  double t0r = 0.0, dt0r = 0.0, tn0r = 0.0;
-  float2 y0r = make_float2(0.f, 0.f);
-  if (spec_ok) {
-    t0r = R.t[(size_t)sl * B + b];
-    dt0r = R.dt[(size_t)sl * B + b];
-    y0r = reinterpret_cast<const float2*>(R.y)[(size_t)sl * B + b];
-    if (sl + 1 < R.cap) tn0r = R.t[(size_t)(sl + 1) * B + b];
-  }
-  const int ns = __builtin_amdgcn_readfirstlane(R.n[b]);
-  const float L = theta[b];
-  const float2 y0 = z_out[b];
+  const int jl = min(lane, T - 1), sl0 = min(sl, cap - 1), sl1 = min(sl + 1, cap - 1);
+  double tsv = ts_g[jl];
+  float2 dv = dz_out[(size_t)jl * B + b];
+  double t0r = rec_t[(size_t)sl0 * B + b], dt0r = rec_dt[(size_t)sl0 * B + b], tn0r = rec_t[(size_t)sl1 * B + b];
+  float2 y0r = rec_y[(size_t)sl0 * B + b];
+  int nsv = rec_n[b];
+  float L = theta[b];
+  float2 y0 = z_out[b];
+  asm volatile("" : "+v"(tsv), "+v"(dv.x), "+v"(dv.y), "+v"(t0r), "+v"(dt0r), "+v"(tn0r), "+v"(y0r.x), "+v"(y0r.y), "+v"(nsv), "+v"(L), "+v"(y0.x), "+v"(y0.y));
+  const int ns = __builtin_amdgcn_readfirstlane(nsv);
   if (j0ok) {
     s_t[lane] = tsv;
     s_d[lane] = dv;
@@ -1973,7 +1981,7 @@ __global__ void __launch_bounds__(64) k_pend_adjoint_disc_tp(const float2* __res
   const float ngl = -10.0f / L, gl2 = 10.0f / (L * L);
   int ret = LDE_RET_SUCCESS;
   if (!isfinite(y0.x) || !isfinite(y0.y)) ret = LDE_RET_NONFINITE;      // a failed forward trajectory: zero gradient [REF GOKU.jl:114]
-  else if (T > 1 && (ns < 1 || ns > R.cap)) ret = LDE_RET_MAXITERS;      // no usable record: NaN gradient (never a truncated sweep)
+  else if (T > 1 && (ns < 1 || ns > cap)) ret = LDE_RET_MAXITERS;      // no usable record: NaN gradient (never a truncated sweep)
   float ax = 0.f, ay = 0.f, gth = 0.f;   // wave-uniform: the cotangent below the steps done so far, dθ
   if (ret == LDE_RET_SUCCESS && T > 1) {
     const double tbeg = s_t[0], tend = s_t[T - 1];
@@ -1985,10 +1993,10 @@ __global__ void __launch_bounds__(64) k_pend_adjoint_disc_tp(const float2* __res
       double t = t0r, dt = dt0r, tnew = tn0r;
       float2 yv = y0r;
       if (r > 0 && act) {
-        t = R.t[(size_t)s * B + b];
-        dt = R.dt[(size_t)s * B + b];
-        yv = reinterpret_cast<const float2*>(R.y)[(size_t)s * B + b];
-        if (s + 1 < ns) tnew = R.t[(size_t)(s + 1) * B + b];
+        t = rec_t[(size_t)s * B + b];
+        dt = rec_dt[(size_t)s * B + b];
+        yv = rec_y[(size_t)s * B + b];
+        if (s + 1 < ns) tnew = rec_t[(size_t)(s + 1) * B + b];
       }
       const bool last = s == ns - 1;
       if (last) tnew = tend;
@@ -2048,14 +2056,20 @@ __global__ void __launch_bounds__(64) k_pend_adjoint_disc_tp(const float2* __res
       }
       PPROF(2);
       // ---- the save times in (t, tnew]: on the step's end → e_s; inside → the interpolant's weights
-      // (One wave per SIMD: nothing hides a dependent instruction's latency but the wave's own independent instructions. So the four save
-      //  times of a round trip are four independent, branch-free bodies — a save time outside the step enters with weight zero — on
-      //  register pairs (x, y); only the ten running sums chain from body to body.)
+      // (One wave per SIMD: nothing hides a dependent instruction's latency but the wave's own independent instructions, and a branch on a
+      //  fresh vector compare is ≈ 48 cycles of it (abl/valu_lat2.hip). So EVERY lane runs one trip of four save times as straight-line code:
+      //  the grid check's two entries and the four (time, Δẑ) pairs below the guess come in ONE batch of LDS reads with one wait; the tests
+      //  are compares combined with & and | (no short-circuit: && and || on fresh compares become exec-mask blocks), their results
+      //  selects — a save time outside the step, or a lane without a step, enters with weight zero on a Θ made finite (h = 0: 1/h = ∞) —
+      //  and the four bodies are independent on register pairs (x, y); only the ten running sums chain from body to body. What is rare
+      //  sits behind wave votes, out of the way: a grid the guess is wrong on, and steps with more than four save times per lane.
+      //  The phase at the metric's shape: 2 011 → ≈ 1 575 cycles, abl/disc_tp_prof.py; same sums in the same order: bit-identical results.)
       f32x2 ev = {0.f, 0.f}, ynv = {0.f, 0.f}, c1 = {0.f, 0.f}, c2 = {0.f, 0.f}, c3 = {0.f, 0.f}, c4 = {0.f, 0.f};   // Tsit5: moments of Θ; RK4: the four Hermite sums
-      if (act) {
+      {
         // the last save time ≤ tnew: where a uniform grid has it (exact there: the index in f64 with a margin far below a grid spacing),
         // checked against the grid itself in the round trip that also fetches the first four save times below it
-        int j = (int)((tnew - tbeg) * jscale + 1e-6);
+        const double tgs = act ? tnew : tbeg;   // (a lane without a step: a finite guess)
+        int j = (int)((tgs - tbeg) * jscale + 1e-6);
         j = j < 0 ? 0 : (j > T - 1 ? T - 1 : j);
         const float rh = fast_rcp(h);
         double tq[4];
@@ -2068,29 +2082,16 @@ __global__ void __launch_bounds__(64) k_pend_adjoint_disc_tp(const float2* __res
             dq[u] = *reinterpret_cast<const f32x2*>(&s_d[jj]);
           }
         };
-        {
-          const double ttop = s_t[j], tup = s_t[j < T - 1 ? j + 1 : j];
-          const bool ragged = !(ttop <= tnew && (j == T - 1 || tup > tnew));
-          j -= tau;   // the step's three lanes share its save times: lane τ takes the τ-th, (τ + 3)-th, … from the last one down
-          fetch();
-          if (__builtin_expect(ragged, 0)) {   // (a ragged grid: walk to it)
-            j += tau;
-            while (j < T - 1 && s_t[j + 1] <= tnew) j++;
-            while (j > 0 && s_t[j] > tnew) j--;
-            j -= tau;
-            fetch();
-          }
-        }
-        for (;;) {
+        auto trip = [&]() -> bool {   // four save times from j down in steps of three; true: the fourth was inside the step, there may be more
           bool in = false;
 #pragma unroll
           for (int u = 0; u < 4; u++) {
             const double tj = tq[u];
-            in = j - 3 * u >= 1 && tj > t;                   // (the grid ascends: once false, false for every save time below)
-            const bool end = tj >= tnew || (j - 3 * u == T - 1 && last);
+            in = act & (j - 3 * u >= 1) & (tj > t);          // (the grid ascends: once false, false for every save time below)
+            const bool end = (tj >= tnew) | ((j - 3 * u == T - 1) & last);
             const f32x2 zero = {0.f, 0.f};
-            const f32x2 de = in && end ? dq[u] : zero, di = in && !end ? dq[u] : zero;
-            const float th = (float)(tj - t) * rh;
+            const f32x2 de = (in & end) ? dq[u] : zero, di = (in & !end) ? dq[u] : zero;
+            const float th = in ? (float)(tj - t) * rh : 0.f;
             ev += de;
             if (SOLVER == LDE_SOLVER_TSIT5) {
               const float t2 = th * th, t3 = t2 * th, t4 = t2 * t2;
@@ -2109,9 +2110,30 @@ __global__ void __launch_bounds__(64) k_pend_adjoint_disc_tp(const float2* __res
               c3 += (h11 * h) * di;
             }
           }
-          if (!in) break;
-          j -= 12;
-          fetch();
+          return in;
+        };
+        const int jg = j;
+        double ttop = s_t[j], tup = s_t[j < T - 1 ? j + 1 : j];
+        j -= tau;   // the step's three lanes share its save times: lane τ takes the τ-th, (τ + 3)-th, … from the last one down
+        fetch();
+        asm volatile("" : "+v"(ttop), "+v"(tup), "+v"(tq[0]), "+v"(tq[1]), "+v"(tq[2]), "+v"(tq[3]), "+v"(dq[0]), "+v"(dq[1]), "+v"(dq[2]), "+v"(dq[3]));   // (all six reads issued, one wait)
+        const bool ragged = act & !((ttop <= tnew) & ((jg == T - 1) | (tup > tnew)));
+        if (__builtin_expect(__any(ragged), 0)) {   // (a ragged grid: walk to it)
+          if (ragged) {
+            j = jg;
+            while (j < T - 1 && s_t[j + 1] <= tnew) j++;
+            while (j > 0 && s_t[j] > tnew) j--;
+            j -= tau;
+            fetch();
+          }
+        }
+        bool more = trip();
+        if (__builtin_expect(__any(more), 0)) {   // (more than four save times of the step for one of its lanes)
+          while (more) {
+            j -= 12;
+            fetch();
+            more = trip();
+          }
         }
       }
       {   // the three lanes' partial sums meet in LDS (a wave's LDS operations execute in order) and are added in the order τ = 0, 1, 2
