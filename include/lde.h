@@ -666,6 +666,33 @@ int lde_sample_kl_backward(const float* mu, const float* logvar, const float* ep
 int lde_mse_forward_add(const float* x, const float* xhat, int64_t n, float scale, const float* base, float* out, float* scratch,
                         void* stream);
 
+/* The KL-carrying terms with the KL weight β in DEVICE memory — what a captured training step needs when β changes between replays
+ * (the reference's cyclical schedule changes it every epoch [REF examples/pendulum_friction-less/model_train.jl:150, :175]): the host
+ * rewrites one float, the graph stays. Each entry point is its twin above with `const float* beta_dev` (one device float, read by the
+ * kernel at run time) and `float divisor` (the batch size the term is divided by) where the twin has `float scale`:
+ *   s = *beta_dev ⊘ divisor      — ONE IEEE round-to-nearest f32 division, not a reciprocal-multiply —
+ * and from there exactly the twin with scale = s: the same per-element formulas, the same fixed-order sums, the same separately rounded
+ * base + s·Σ. Results are bit for bit the twin's called with the f32 quotient β/divisor. lde_kl_forward_dev also takes a `base` (NULL: 0),
+ * so that `reconstruction + β·kl` of the non-variational loss chains through it. The pair forms carry one beta_dev and a divisor per part,
+ * and keep the twin's LDE_ERR_UNSUPPORTED beyond 8192 entries per part. Every form returns LDE_ERR_INVALID_ARG, before any device call,
+ * for a NULL beta_dev, a divisor that is not finite or not > 0, and whatever its twin refuses. β itself gets no gradient. */
+int lde_kl_forward_dev(const float* mu, const float* logvar, int64_t n, const float* beta_dev, float divisor, const float* base, float* out,
+                       float* scratch, void* stream);
+int lde_kl_backward_dev(const float* mu, const float* logvar, int64_t n, const float* beta_dev, float divisor, const float* dout, float* dmu,
+                        float* dlogvar, void* stream);
+int lde_sample_kl_forward_dev(const float* mu, const float* logvar, const float* eps, int64_t n, const float* beta_dev, float divisor,
+                              const float* base, float* l, float* out, float* scratch, void* stream);
+int lde_sample_kl_backward_dev(const float* mu, const float* logvar, const float* eps, const float* dl, const float* dout, const float* beta_dev,
+                               float divisor, int64_t n, float* dmu, float* dlogvar, void* stream);
+int lde_sample_kl_pair_forward_dev(const float* mu_a, const float* logvar_a, int64_t n_a, float divisor_a, const float* mu_b, const float* logvar_b,
+                                   int64_t n_b, float divisor_b, const float* beta_dev, const float* base, uint64_t seed, uint64_t offset_a,
+                                   uint64_t offset_b, uint32_t call_a, uint32_t call_b, const int64_t* epoch_dev, float* eps_a, float* eps_b,
+                                   float* l_a, float* l_b, float* out, float* scratch, void* stream);
+int lde_sample_kl_pair_backward_dev(const float* mu_a, const float* logvar_a, const float* eps_a, const float* dl_a, int64_t n_a, float divisor_a,
+                                    const float* mu_b, const float* logvar_b, const float* eps_b, const float* dl_b, int64_t n_b, float divisor_b,
+                                    const float* beta_dev, const float* dout, float* dmu_a, float* dlogvar_a, float* dmu_b, float* dlogvar_b,
+                                    void* stream);
+
 /* Where the chain / recurrent pullbacks enqueue their WEIGHT-GRADIENT kernels. Default (NULL): on the caller's stream, after
  * the pullback kernel — `dW` is complete in stream order like every other output. With a stream set, lde_chain_backward[_saved]
  * and lde_rnn_backward enqueue only the input-gradient kernel on the caller's stream and the kernels that produce `dW` on this

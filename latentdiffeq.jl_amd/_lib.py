@@ -35,7 +35,8 @@ EXPORTS = ["lde_abi_version", "lde_problem_desc_default", "lde_desc_error", "lde
            "lde_rnn_num_weights", "lde_rnn_create", "lde_rnn_destroy", "lde_rnn_set_weights", "lde_rnn_set_weights_device",
            "lde_rnn_reserve", "lde_rnn_forward", "lde_rnn_backward", "lde_rnn_last_error", "lde_rnn_backward_dx", "lde_rnn_backward_dw", "lde_refresh_weights",
            "lde_sample_forward", "lde_sample_backward", "lde_kl_forward", "lde_kl_backward", "lde_mse_forward",
-           "lde_mse_backward", "lde_sample_kl_forward", "lde_sample_kl_backward", "lde_mse_forward_add", "lde_adamw_flux_step", "lde_adamw_flux_step_dev", "lde_guard_init", "lde_adamw_flux_step_guarded", "lde_clip_ws_bytes", "lde_adamw_flux_step_clipped",
+           "lde_mse_backward", "lde_sample_kl_forward", "lde_sample_kl_backward", "lde_mse_forward_add", "lde_kl_forward_dev", "lde_kl_backward_dev", "lde_sample_kl_forward_dev", "lde_sample_kl_backward_dev",
+           "lde_sample_kl_pair_forward_dev", "lde_sample_kl_pair_backward_dev", "lde_adamw_flux_step", "lde_adamw_flux_step_dev", "lde_guard_init", "lde_adamw_flux_step_guarded", "lde_clip_ws_bytes", "lde_adamw_flux_step_clipped",
            "lde_adabelief_flux_step", "lde_adabelief_flux_step_dev", "lde_adabelief_flux_step_guarded", "lde_adabelief_flux_step_clipped", "lde_set_dw_stream", "lde_join_dw",
            "lde_comm_unique_id", "lde_comm_init", "lde_comm_allreduce_f32", "lde_comm_nranks", "lde_comm_rank",
            "lde_comm_destroy", "lde_comm_last_error"]
@@ -213,6 +214,14 @@ def load():
     lib.lde_sample_kl_forward.argtypes = [vp, vp, vp, i64, f32, vp, vp, vp, vp, vp]
     lib.lde_sample_kl_backward.argtypes = [vp, vp, vp, vp, vp, f32, i64, vp, vp, vp]
     lib.lde_mse_forward_add.argtypes = [vp, vp, i64, f32, vp, vp, vp, vp]
+    # the KL-carrying terms with β in device memory: (beta_dev, divisor) where the twin has scale
+    lib.lde_kl_forward_dev.argtypes = [vp, vp, i64, vp, f32, vp, vp, vp, vp]
+    lib.lde_kl_backward_dev.argtypes = [vp, vp, i64, vp, f32, vp, vp, vp, vp]
+    lib.lde_sample_kl_forward_dev.argtypes = [vp, vp, vp, i64, vp, f32, vp, vp, vp, vp, vp]
+    lib.lde_sample_kl_backward_dev.argtypes = [vp, vp, vp, vp, vp, vp, f32, i64, vp, vp, vp]
+    lib.lde_sample_kl_pair_forward_dev.argtypes = [vp, vp, i64, f32, vp, vp, i64, f32, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                   vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.lde_sample_kl_pair_backward_dev.argtypes = [vp, vp, vp, vp, i64, f32, vp, vp, vp, vp, i64, f32, vp, vp, vp, vp, vp, vp, vp]
     lib.lde_set_dw_stream.argtypes = [vp]
     lib.lde_join_dw.argtypes = [vp]
     lib.lde_adamw_flux_step.argtypes = [i32, C.POINTER(AdamTensor), f32, f32, f32, f32, f32, i64, vp]

@@ -47,12 +47,18 @@ __device__ __forceinline__ float wg_sum(float v) {
   return s;
 }
 
+// Where a kernel takes the scale of its KL term from. ScaleArg: the kernel argument, as ever. ScaleDev: β in DEVICE memory (one float the
+// host rewrites between the replays of a captured step) over the batch size — ONE correctly rounded f32 division, formed where the scale is
+// used (once per launch, by the thread that uses it), never a reciprocal-multiply: s is bit for bit the f32 quotient a host would pass.
+struct ScaleArg { float v; __device__ __forceinline__ float get() const { return v; } };
+struct ScaleDev { const float* beta; float divisor; __device__ __forceinline__ float get() const { return __fdiv_rn(beta[0], divisor); } };
+
 __device__ __forceinline__ float kl_term(float m, float lv) { return 0.5f * (__expf(lv) + m * m - lv - 1.0f); }
 
 // TERM 0: kl(a = μ, b = logσ²); TERM 1: (a − b)²; TERM 2: kl(a, b) and, in the same pass, the sample l = a + c·exp(b/2) → l
-template <int TERM>
+template <int TERM, class SCALE>
 __device__ __forceinline__ void loss_partial_body(const float* __restrict__ a, const float* __restrict__ b, int64_t n,
-                                                  float* __restrict__ scratch, const float* __restrict__ c, float* __restrict__ l, float fscale,
+                                                  float* __restrict__ scratch, const float* __restrict__ c, float* __restrict__ l, const SCALE fscale,
                                                   float* fout, const float* fbase, const unsigned bx, const unsigned nblk) {   // (fout may BE fbase: k_sample_kl_pair's second part adds to the first's result)
   // workgroup w owns the slice [w·per, (w+1)·per) with per a multiple of 4 floats
   const int64_t nwg = nblk;
@@ -94,7 +100,7 @@ __device__ __forceinline__ void loss_partial_body(const float* __restrict__ a, c
     if (fout) {   // a one-workgroup sum (n ≤ 8192: the KL terms of a training step) is its own last kernel: what k_loss_final computes from
                   // one partial, with the same separately rounded product and addition — one launch instead of two
 #pragma clang fp contract(off)
-      const float term = fscale * s;
+      const float term = fscale.get() * s;
       fout[0] = fbase ? fbase[0] + term : term;
     }
   }
@@ -104,7 +110,15 @@ __global__ void __launch_bounds__(LOSS_WG) k_loss_partial(const float* __restric
                                                           float* __restrict__ scratch, const float* __restrict__ c = nullptr,
                                                           float* __restrict__ l = nullptr, float fscale = 0.f, float* __restrict__ fout = nullptr,
                                                           const float* __restrict__ fbase = nullptr) {
-  loss_partial_body<TERM>(a, b, n, scratch, c, l, fscale, fout, fbase, blockIdx.x, gridDim.x);
+  loss_partial_body<TERM>(a, b, n, scratch, c, l, ScaleArg{fscale}, fout, fbase, blockIdx.x, gridDim.x);
+}
+// the same with the scale β/divisor read from device memory (the lde_*_dev entry points); only the fused last store (fout) looks at it
+template <int TERM>
+__global__ void __launch_bounds__(LOSS_WG) k_loss_partial_dev(const float* __restrict__ a, const float* __restrict__ b, int64_t n,
+                                                              float* __restrict__ scratch, const float* __restrict__ c, float* __restrict__ l,
+                                                              const float* __restrict__ beta, float divisor, float* __restrict__ fout,
+                                                              const float* __restrict__ fbase) {
+  loss_partial_body<TERM>(a, b, n, scratch, c, l, ScaleDev{beta, divisor}, fout, fbase, blockIdx.x, gridDim.x);
 }
 
 // out = scale·Σ partials (+ base[0]: a running total of loss terms — the elementwise additions of the loss expression folded in)
@@ -116,6 +130,18 @@ __global__ void __launch_bounds__(64) k_loss_final(const float* __restrict__ scr
   s = wave_sum(s);
   // (no contraction into an fma: base + the separately rounded term, the bits of the separate entry point followed by an addition)
   if (threadIdx.x == 0) out[0] = base ? base[0] + scale * s : scale * s;
+}
+// the same with scale = β/divisor, β read from device memory by the one thread that uses it
+__global__ void __launch_bounds__(64) k_loss_final_dev(const float* __restrict__ scratch, int nwg, const float* __restrict__ beta, float divisor,
+                                                       float* __restrict__ out, const float* __restrict__ base) {
+#pragma clang fp contract(off)
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nwg; i += 64) s += scratch[i];
+  s = wave_sum(s);
+  if (threadIdx.x == 0) {
+    const float scale = __fdiv_rn(beta[0], divisor);
+    out[0] = base ? base[0] + scale * s : scale * s;
+  }
 }
 
 // OP 0: l = μ + ε·exp(lv/2)                           (a = μ, b = lv, c = ε → o0)
@@ -173,11 +199,24 @@ __global__ void __launch_bounds__(LOSS_WG) k_sample_kl_bwd(const float* __restri
                                                            float* __restrict__ dmu, float* __restrict__ dlv) {
   sample_kl_bwd_body(mu, lv, eps, dl, g, scale, n, dmu, dlv, blockIdx.x, gridDim.x);
 }
+// scale = β/divisor with β in device memory: the division beside the body's g[0]·scale, once per thread
+__global__ void __launch_bounds__(LOSS_WG) k_sample_kl_bwd_dev(const float* __restrict__ mu, const float* __restrict__ lv,
+                                                               const float* __restrict__ eps, const float* __restrict__ dl,
+                                                               const float* __restrict__ g, const float* __restrict__ beta, float divisor, int64_t n,
+                                                               float* __restrict__ dmu, float* __restrict__ dlv) {
+  sample_kl_bwd_body(mu, lv, eps, dl, g, __fdiv_rn(beta[0], divisor), n, dmu, dlv, blockIdx.x, gridDim.x);
+}
 // two parts (the GOKU tuple (z₀, θ) [REF src/models/GOKU.jl:155-163]) in one launch: workgroups [0, nblk_a) the first, the rest the second
 struct SampleBwdPart { const float* mu; const float* lv; const float* eps; const float* dl; float scale; long long n; float* dmu; float* dlv; };
 __global__ void __launch_bounds__(LOSS_WG) k_sample_kl_bwd_pair(SampleBwdPart pa, SampleBwdPart pb, const float* __restrict__ g, unsigned nblk_a) {
   if (blockIdx.x < nblk_a) sample_kl_bwd_body(pa.mu, pa.lv, pa.eps, pa.dl, g, pa.scale, pa.n, pa.dmu, pa.dlv, blockIdx.x, nblk_a);
   else sample_kl_bwd_body(pb.mu, pb.lv, pb.eps, pb.dl, g, pb.scale, pb.n, pb.dmu, pb.dlv, blockIdx.x - nblk_a, gridDim.x - nblk_a);
+}
+// (the parts' `scale` fields carry the divisors)
+__global__ void __launch_bounds__(LOSS_WG) k_sample_kl_bwd_pair_dev(SampleBwdPart pa, SampleBwdPart pb, const float* __restrict__ g,
+                                                                    const float* __restrict__ beta, unsigned nblk_a) {
+  if (blockIdx.x < nblk_a) sample_kl_bwd_body(pa.mu, pa.lv, pa.eps, pa.dl, g, __fdiv_rn(beta[0], pa.scale), pa.n, pa.dmu, pa.dlv, blockIdx.x, nblk_a);
+  else sample_kl_bwd_body(pb.mu, pb.lv, pb.eps, pb.dl, g, __fdiv_rn(beta[0], pb.scale), pb.n, pb.dmu, pb.dlv, blockIdx.x - nblk_a, gridDim.x - nblk_a);
 }
 
 template <int OP>
@@ -213,6 +252,38 @@ __global__ void __launch_bounds__(LOSS_WG) k_loss_map(const float* __restrict__ 
       if (two_out) o1[i + q] = r1;
     }
 }
+// lde_kl_backward_dev: k_loss_map<2> with scale = β/divisor, β in device memory — the division beside g[0]·scale, the same loops and the same
+// loss_map1<2> per element. (A kernel of its own rather than a shared body: k_loss_map's instructions stay what they were.)
+__global__ void __launch_bounds__(LOSS_WG) k_kl_bwd_dev(const float* __restrict__ mu, const float* __restrict__ lv, const float* __restrict__ g,
+                                                        const float* __restrict__ beta, float divisor, int64_t n, float* __restrict__ dmu,
+                                                        float* __restrict__ dlv) {
+  const float k = g[0] * __fdiv_rn(beta[0], divisor);
+  const bool al = ((((uintptr_t)mu) | ((uintptr_t)lv) | ((uintptr_t)dmu) | ((uintptr_t)dlv)) & 15) == 0;
+  const int64_t stride = 4 * (int64_t)gridDim.x * LOSS_WG;
+  int64_t i = 4 * ((int64_t)blockIdx.x * LOSS_WG + threadIdx.x);
+  if (al) {
+    for (; i + 4 <= n; i += stride) {
+      const f4 va = *reinterpret_cast<const f4*>(mu + i), vb = *reinterpret_cast<const f4*>(lv + i);
+      f4 r0, r1;
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        float t0, t1 = 0.f;
+        loss_map1<2>(va[q], vb[q], 0.f, k, t0, t1);
+        r0[q] = t0;
+        r1[q] = t1;
+      }
+      *reinterpret_cast<f4*>(dmu + i) = r0;
+      *reinterpret_cast<f4*>(dlv + i) = r1;
+    }
+  }
+  for (; i < n; i += stride)
+    for (int q = 0; q < 4 && i + q < n; q++) {
+      float r0, r1 = 0.f;
+      loss_map1<2>(mu[i + q], lv[i + q], 0.f, k, r0, r1);
+      dmu[i + q] = r0;
+      dlv[i + q] = r1;
+    }
+}
 
 static inline int map_grid(int64_t n) {
   const int64_t g = (n + 4 * LOSS_WG - 1) / (4 * LOSS_WG);
@@ -230,6 +301,26 @@ static int loss_reduce(const float* a, const float* b, int64_t n, float scale, f
   else {
     if (g) hipLaunchKernelGGL(k_loss_partial<TERM>, dim3(g), dim3(LOSS_WG), 0, stream, a, b, n, scratch, c, l, 0.f, (float*)nullptr, (const float*)nullptr);
     hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(64), 0, stream, scratch, g, scale, out, base);
+  }
+  return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
+}
+
+// what every lde_*_dev entry point refuses on top of its twin, before any device call
+static inline bool beta_dev_ok(const float* beta_dev, float divisor) { return beta_dev && divisor > 0.f && divisor <= 3.402823466e38f; }   // (NaN fails `>`)
+
+// loss_reduce with scale = *beta_dev ⊘ divisor formed on the device (TERM 0: kl, TERM 2: sample + kl)
+template <int TERM>
+static int loss_reduce_dev(const float* a, const float* b, int64_t n, const float* beta_dev, float divisor, float* out, float* scratch, void* stream_,
+                           const float* base, const float* c = nullptr, float* l = nullptr) {
+  if (!beta_dev_ok(beta_dev, divisor)) return LDE_ERR_INVALID_ARG;
+  if (!out || !scratch || n < 0 || (n > 0 && (!a || !b))) return LDE_ERR_INVALID_ARG;
+  if (TERM == 2 && n > 0 && (!c || !l)) return LDE_ERR_INVALID_ARG;
+  hipStream_t stream = (hipStream_t)stream_;
+  const int g = n == 0 ? 0 : loss_grid(n);   // an empty sum is 0
+  if (g == 1) hipLaunchKernelGGL(k_loss_partial_dev<TERM>, dim3(1), dim3(LOSS_WG), 0, stream, a, b, n, scratch, c, l, beta_dev, divisor, out, base);
+  else {
+    if (g) hipLaunchKernelGGL(k_loss_partial<TERM>, dim3(g), dim3(LOSS_WG), 0, stream, a, b, n, scratch, c, l, 0.f, (float*)nullptr, (const float*)nullptr);
+    hipLaunchKernelGGL(k_loss_final_dev, dim3(1), dim3(64), 0, stream, (const float*)scratch, g, beta_dev, divisor, out, base);
   }
   return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
 }
@@ -282,10 +373,25 @@ __global__ void __launch_bounds__(PAIR_WG) k_sample_kl_pair(SampleFwdPart pa, Sa
   for (long long blk = threadIdx.x; 4 * blk < pb.n; blk += PAIR_WG) randn_block(pb.eps, pb.n, seed, pb.offset, pb.call, epoch, nullptr, blk);
   __syncthreads();   // (the workgroup's own global stores, read back below: drained and visible)
   const bool summing = threadIdx.x < LOSS_WG;   // wave-uniform; the other waves keep the barrier count of loss_partial_body (one, in wg_sum)
-  if (summing) loss_partial_body<2>(pa.mu, pa.lv, pa.n, scratch, pa.eps, pa.l, pa.scale, out, base, 0u, 1u);
+  if (summing) loss_partial_body<2>(pa.mu, pa.lv, pa.n, scratch, pa.eps, pa.l, ScaleArg{pa.scale}, out, base, 0u, 1u);
   else __syncthreads();
   __syncthreads();   // wg_sum's staging is reused; thread 0 wrote out[0] and reads it as the second part's base
-  if (summing) loss_partial_body<2>(pb.mu, pb.lv, pb.n, scratch + 1, pb.eps, pb.l, pb.scale, out, out, 0u, 1u);
+  if (summing) loss_partial_body<2>(pb.mu, pb.lv, pb.n, scratch + 1, pb.eps, pb.l, ScaleArg{pb.scale}, out, out, 0u, 1u);
+  else __syncthreads();
+}
+// lde_sample_kl_pair_forward_dev: the same kernel with β in device memory — the parts' `scale` fields carry the divisors. (A copy rather than
+// a shared body: k_sample_kl_pair's instructions stay what they were.)
+__global__ void __launch_bounds__(PAIR_WG) k_sample_kl_pair_dev(SampleFwdPart pa, SampleFwdPart pb, unsigned long long seed, const long long* __restrict__ epoch,
+                                                                const float* __restrict__ beta, const float* __restrict__ base, float* __restrict__ out,
+                                                                float* __restrict__ scratch) {
+  for (long long blk = threadIdx.x; 4 * blk < pa.n; blk += PAIR_WG) randn_block(pa.eps, pa.n, seed, pa.offset, pa.call, epoch, nullptr, blk);
+  for (long long blk = threadIdx.x; 4 * blk < pb.n; blk += PAIR_WG) randn_block(pb.eps, pb.n, seed, pb.offset, pb.call, epoch, nullptr, blk);
+  __syncthreads();
+  const bool summing = threadIdx.x < LOSS_WG;
+  if (summing) loss_partial_body<2>(pa.mu, pa.lv, pa.n, scratch, pa.eps, pa.l, ScaleDev{beta, pa.scale}, out, base, 0u, 1u);
+  else __syncthreads();
+  __syncthreads();
+  if (summing) loss_partial_body<2>(pb.mu, pb.lv, pb.n, scratch + 1, pb.eps, pb.l, ScaleDev{beta, pb.scale}, out, out, 0u, 1u);
   else __syncthreads();
 }
 
@@ -371,6 +477,63 @@ int lde_sample_kl_pair_backward(const float* mu_a, const float* logvar_a, const 
   const SampleBwdPart pb{mu_b, logvar_b, eps_b, dl_b, scale_b, (long long)n_b, dmu_b, dlogvar_b};
   const unsigned ga = (unsigned)map_grid(n_a), gb = (unsigned)map_grid(n_b);   // each part's grid as in lde_sample_kl_backward
   hipLaunchKernelGGL(k_sample_kl_bwd_pair, dim3(ga + gb), dim3(LOSS_WG), 0, (hipStream_t)stream, pa, pb, dout, ga);
+  return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
+}
+
+// ---- the KL-carrying terms with β in device memory: scale = *beta_dev ⊘ divisor, formed by the kernel at run time -----------------------
+int lde_kl_forward_dev(const float* mu, const float* logvar, int64_t n, const float* beta_dev, float divisor, const float* base, float* out,
+                       float* scratch, void* stream) {
+  return loss_reduce_dev<0>(mu, logvar, n, beta_dev, divisor, out, scratch, stream, base);
+}
+
+int lde_kl_backward_dev(const float* mu, const float* logvar, int64_t n, const float* beta_dev, float divisor, const float* dout, float* dmu,
+                        float* dlogvar, void* stream) {
+  if (!beta_dev_ok(beta_dev, divisor) || n < 0 || (n > 0 && (!mu || !logvar || !dout || !dmu || !dlogvar))) return LDE_ERR_INVALID_ARG;
+  if (n == 0) return LDE_OK;
+  hipLaunchKernelGGL(k_kl_bwd_dev, dim3(map_grid(n)), dim3(LOSS_WG), 0, (hipStream_t)stream, mu, logvar, dout, beta_dev, divisor, n, dmu, dlogvar);
+  return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
+}
+
+int lde_sample_kl_forward_dev(const float* mu, const float* logvar, const float* eps, int64_t n, const float* beta_dev, float divisor,
+                              const float* base, float* l, float* out, float* scratch, void* stream) {
+  return loss_reduce_dev<2>(mu, logvar, n, beta_dev, divisor, out, scratch, stream, base, eps, l);
+}
+
+int lde_sample_kl_backward_dev(const float* mu, const float* logvar, const float* eps, const float* dl, const float* dout, const float* beta_dev,
+                               float divisor, int64_t n, float* dmu, float* dlogvar, void* stream) {
+  if (!beta_dev_ok(beta_dev, divisor)) return LDE_ERR_INVALID_ARG;
+  if (n < 0 || (n > 0 && (!mu || !logvar || !eps || !dl || !dout || !dmu || !dlogvar))) return LDE_ERR_INVALID_ARG;
+  if (n == 0) return LDE_OK;
+  hipLaunchKernelGGL(k_sample_kl_bwd_dev, dim3(map_grid(n)), dim3(LOSS_WG), 0, (hipStream_t)stream, mu, logvar, eps, dl, dout, beta_dev, divisor, n,
+                     dmu, dlogvar);
+  return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
+}
+
+int lde_sample_kl_pair_forward_dev(const float* mu_a, const float* logvar_a, int64_t n_a, float divisor_a, const float* mu_b, const float* logvar_b,
+                                   int64_t n_b, float divisor_b, const float* beta_dev, const float* base, uint64_t seed, uint64_t offset_a,
+                                   uint64_t offset_b, uint32_t call_a, uint32_t call_b, const int64_t* epoch_dev, float* eps_a, float* eps_b,
+                                   float* l_a, float* l_b, float* out, float* scratch, void* stream) {
+  if (n_a < 1 || n_b < 1 || n_a > LOSS_CHUNK || n_b > LOSS_CHUNK) return LDE_ERR_UNSUPPORTED;   // the caller makes the separate calls
+  if (!beta_dev_ok(beta_dev, divisor_a) || !beta_dev_ok(beta_dev, divisor_b)) return LDE_ERR_INVALID_ARG;
+  if (!mu_a || !logvar_a || !mu_b || !logvar_b || !eps_a || !eps_b || !l_a || !l_b || !out || !scratch) return LDE_ERR_INVALID_ARG;
+  const SampleFwdPart pa{mu_a, logvar_a, eps_a, l_a, divisor_a, (long long)n_a, (unsigned long long)offset_a, (unsigned)call_a};
+  const SampleFwdPart pb{mu_b, logvar_b, eps_b, l_b, divisor_b, (long long)n_b, (unsigned long long)offset_b, (unsigned)call_b};
+  hipLaunchKernelGGL(k_sample_kl_pair_dev, dim3(1), dim3(PAIR_WG), 0, (hipStream_t)stream, pa, pb, (unsigned long long)seed, (const long long*)epoch_dev,
+                     beta_dev, base, out, scratch);
+  return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
+}
+int lde_sample_kl_pair_backward_dev(const float* mu_a, const float* logvar_a, const float* eps_a, const float* dl_a, int64_t n_a, float divisor_a,
+                                    const float* mu_b, const float* logvar_b, const float* eps_b, const float* dl_b, int64_t n_b, float divisor_b,
+                                    const float* beta_dev, const float* dout, float* dmu_a, float* dlogvar_a, float* dmu_b, float* dlogvar_b,
+                                    void* stream) {
+  if (n_a < 1 || n_b < 1) return LDE_ERR_UNSUPPORTED;
+  if (!beta_dev_ok(beta_dev, divisor_a) || !beta_dev_ok(beta_dev, divisor_b)) return LDE_ERR_INVALID_ARG;
+  if (!mu_a || !logvar_a || !eps_a || !dl_a || !mu_b || !logvar_b || !eps_b || !dl_b || !dout || !dmu_a || !dlogvar_a || !dmu_b || !dlogvar_b)
+    return LDE_ERR_INVALID_ARG;
+  const SampleBwdPart pa{mu_a, logvar_a, eps_a, dl_a, divisor_a, (long long)n_a, dmu_a, dlogvar_a};
+  const SampleBwdPart pb{mu_b, logvar_b, eps_b, dl_b, divisor_b, (long long)n_b, dmu_b, dlogvar_b};
+  const unsigned ga = (unsigned)map_grid(n_a), gb = (unsigned)map_grid(n_b);   // each part's grid as in lde_sample_kl_backward
+  hipLaunchKernelGGL(k_sample_kl_bwd_pair_dev, dim3(ga + gb), dim3(LOSS_WG), 0, (hipStream_t)stream, pa, pb, dout, beta_dev, ga);
   return hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
 }
 

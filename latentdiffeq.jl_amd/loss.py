@@ -9,7 +9,12 @@
 
 On HIP tensors every function is one liblde.so kernel (two for the reductions) forward and one backward
 (lde_sample_* / lde_kl_* / lde_mse_*, include/lde.h): no chain of broadcast kernels, no host synchronisation. ε is drawn
-by lde_randn from the state of torch's CUDA generator (`randn` below), like the reference draws it with randn. There is no CPU path."""
+by lde_randn from the state of torch's CUDA generator (`randn` below), like the reference draws it with randn. There is no CPU path.
+
+β, the KL weight, is a Python / numpy number — it then travels as a kernel argument, β/B formed on the host — or a β WORD: a float32 HIP
+tensor of one element, read by the kernels at run time (the lde_*_dev entry points: s = β ⊘ B, one f32 division on the device). A captured
+training step whose β is a word follows the schedule by the host writing into the word between replays (train.train(graphed=True)).
+β gets no gradient. A β tensor on the CPU is read as the number it holds, once, at the call."""
 from __future__ import annotations
 
 
@@ -107,6 +112,71 @@ class _SampleKlFn(torch.autograd.Function):
         L.call("lde_sample_kl_backward", None, L.ptr(mu), L.ptr(logvar), L.ptr(eps), L.ptr(dl), L.ptr(g), ctx.scale, mu.numel(), L.ptr(dmu),
                L.ptr(dlv), _stream())
         return dmu, dlv, None, None, (g if ctx.has_base else None)
+
+
+def beta_word(beta):
+    """(word, number) of a β argument: a float32 HIP tensor of one element is a β word (detached: β gets no gradient); anything else —
+    a Python or numpy number, a CPU tensor — is the number it holds."""
+    if torch.is_tensor(beta):
+        if beta.is_cuda:
+            if beta.dtype != torch.float32 or beta.numel() != 1:
+                raise TypeError("a β word is ONE float32 on the GPU")
+            return beta.detach(), None
+        return None, float(beta)
+    return None, beta
+
+
+def _same_device(word, t):
+    if word.device != t.device:
+        raise ValueError(f"the β word lives on {word.device}, the loss term on {t.device}")
+
+
+class _KlDevFn(torch.autograd.Function):
+    """base + (β ⊘ divisor)·Σ kl(μ, logσ²) with β a device word: lde_kl_forward_dev / lde_kl_backward_dev."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, word, divisor, base):
+        _need_gpu(mu)
+        _same_device(word, mu)
+        mu, logvar = mu.contiguous().float(), logvar.contiguous().float()
+        ws, p_out, p_scratch = L.loss_scratch(mu.device)
+        L.call("lde_kl_forward_dev", None, L.ptr(mu), L.ptr(logvar), mu.numel(), L.ptr(word), divisor, L.ptr(base), p_out, p_scratch, _stream())
+        ctx.save_for_backward(mu, logvar, word)
+        ctx.divisor, ctx.has_base = divisor, base is not None
+        return ws[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        mu, logvar, word = ctx.saved_tensors
+        g = g.contiguous().float()
+        dmu, dlv = torch.empty_like(mu), torch.empty_like(logvar)
+        L.call("lde_kl_backward_dev", None, L.ptr(mu), L.ptr(logvar), mu.numel(), L.ptr(word), ctx.divisor, L.ptr(g), L.ptr(dmu), L.ptr(dlv), _stream())
+        return dmu, dlv, None, None, (g if ctx.has_base else None)
+
+
+class _SampleKlDevFn(torch.autograd.Function):
+    """_SampleKlFn with β a device word: lde_sample_kl_forward_dev / _backward_dev (scale = β ⊘ divisor, formed by the kernel)."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, eps, word, divisor, base):
+        _need_gpu(mu)
+        _same_device(word, mu)
+        out = torch.empty_like(mu)
+        ws, p_out, p_scratch = L.loss_scratch(mu.device)
+        L.call("lde_sample_kl_forward_dev", None, L.ptr(mu), L.ptr(logvar), L.ptr(eps), mu.numel(), L.ptr(word), divisor, L.ptr(base), L.ptr(out),
+               p_out, p_scratch, _stream())
+        ctx.save_for_backward(mu, logvar, eps, word)
+        ctx.divisor, ctx.has_base = divisor, base is not None
+        return out, ws[0]
+
+    @staticmethod
+    def backward(ctx, dl, g):
+        mu, logvar, eps, word = ctx.saved_tensors
+        dl, g = dl.contiguous(), g.contiguous().float()
+        dmu, dlv = torch.empty_like(mu), torch.empty_like(logvar)
+        L.call("lde_sample_kl_backward_dev", None, L.ptr(mu), L.ptr(logvar), L.ptr(eps), L.ptr(dl), L.ptr(g), L.ptr(word), ctx.divisor, mu.numel(),
+               L.ptr(dmu), L.ptr(dlv), _stream())
+        return dmu, dlv, None, None, None, (g if ctx.has_base else None)
 
 
 class _MseAddFn(torch.autograd.Function):
@@ -229,6 +299,32 @@ class _SampleKlPairFn(torch.autograd.Function):
         return dmu_a, dlv_a, dmu_b, dlv_b, None, None, None
 
 
+class _SampleKlPairDevFn(torch.autograd.Function):
+    """_SampleKlPairFn with β a device word: lde_sample_kl_pair_forward_dev / _backward_dev, one divisor per part."""
+
+    @staticmethod
+    def forward(ctx, mu_a, lv_a, mu_b, lv_b, word, div_a, div_b, keys):
+        _same_device(word, mu_a)
+        (seed, off_a, call_a, ep), (_, off_b, call_b, _) = keys
+        eps_a, eps_b, l_a, l_b = torch.empty_like(mu_a), torch.empty_like(mu_b), torch.empty_like(mu_a), torch.empty_like(mu_b)
+        ws, p_out, p_parts = L.loss_scratch(mu_a.device, 2)          # [0]: the total, then two partial sums
+        L.call("lde_sample_kl_pair_forward_dev", None, L.ptr(mu_a), L.ptr(lv_a), mu_a.numel(), div_a, L.ptr(mu_b), L.ptr(lv_b), mu_b.numel(), div_b,
+               L.ptr(word), None, seed, off_a, off_b, call_a, call_b, ep, L.ptr(eps_a), L.ptr(eps_b), L.ptr(l_a), L.ptr(l_b), p_out, p_parts, _stream())
+        ctx.save_for_backward(mu_a, lv_a, eps_a, mu_b, lv_b, eps_b, word)
+        ctx.divisors = (div_a, div_b)
+        return l_a, l_b, ws[0]
+
+    @staticmethod
+    def backward(ctx, dl_a, dl_b, g):
+        mu_a, lv_a, eps_a, mu_b, lv_b, eps_b, word = ctx.saved_tensors
+        dl_a, dl_b, g = dl_a.contiguous(), dl_b.contiguous(), g.contiguous().float()
+        dmu_a, dlv_a, dmu_b, dlv_b = torch.empty_like(mu_a), torch.empty_like(lv_a), torch.empty_like(mu_b), torch.empty_like(lv_b)
+        L.call("lde_sample_kl_pair_backward_dev", None, L.ptr(mu_a), L.ptr(lv_a), L.ptr(eps_a), L.ptr(dl_a), mu_a.numel(), ctx.divisors[0],
+               L.ptr(mu_b), L.ptr(lv_b), L.ptr(eps_b), L.ptr(dl_b), mu_b.numel(), ctx.divisors[1], L.ptr(word), L.ptr(g), L.ptr(dmu_a), L.ptr(dlv_a),
+               L.ptr(dmu_b), L.ptr(dlv_b), _stream())
+        return dmu_a, dlv_a, dmu_b, dlv_b, None, None, None, None
+
+
 _SAMPLE_PAIR = True                                             # sample_with_kl of a two-part tuple: one launch each way
 _PAIR_MAX = 8192                                                # entries per part (one workgroup of the separate kernels)
 
@@ -246,8 +342,13 @@ def _sample_kl_pair(mu, logvar, beta, batch_size):
     if not _NATIVE_RNG or (capturing and (idx not in _noise_epoch or idx not in _noise_base)):
         return None
     keys = (_draw_key(lay[0][0].numel(), idx), _draw_key(lay[1][0].numel(), idx))      # in the order the separate calls draw
-    scales = [float(beta / (batch_size or m.shape[1])) for m in mu]
-    l_a, l_b, total = _SampleKlPairFn.apply(lay[0][0], lay[0][1], lay[1][0], lay[1][1], scales[0], scales[1], keys)
+    word, beta = beta_word(beta)
+    if word is not None:
+        divs = [float(batch_size or m.shape[1]) for m in mu]
+        l_a, l_b, total = _SampleKlPairDevFn.apply(lay[0][0], lay[0][1], lay[1][0], lay[1][1], word, divs[0], divs[1], keys)
+    else:
+        scales = [float(beta / (batch_size or m.shape[1])) for m in mu]
+        l_a, l_b, total = _SampleKlPairFn.apply(lay[0][0], lay[0][1], lay[1][0], lay[1][1], scales[0], scales[1], keys)
     outs = []
     for l, (_, _, order), m in zip((l_a, l_b), lay, mu):
         outs.append(l.permute([order.index(d) for d in range(m.dim())]) if order is not None else l)
@@ -270,14 +371,18 @@ def sample(mu, logvar, model_type=None):
     return _sample1(mu, logvar)
 
 
-def _sample_kl1(mu, logvar, scale: float, base, eps=None):
+def _sample_kl1(mu, logvar, scale: float, base, eps=None, word=None):
+    """`word`: a β word — `scale` is then the divisor (the batch size) and the kernel forms β ⊘ divisor."""
     m, s, order = _same_layout(mu.float(), logvar.float())
     if eps is None:
         eps = randn(m.shape, m.device)
     else:   # the caller's ε in the layout of μ (tests that compare two runs draw it once)
         eps = eps.float().permute(order) if order is not None else eps.float()
         eps = eps.contiguous()
-    out, total = _SampleKlFn.apply(m, s, eps, float(scale), base)
+    if word is not None:
+        out, total = _SampleKlDevFn.apply(m, s, eps, word, float(scale), base)
+    else:
+        out, total = _SampleKlFn.apply(m, s, eps, float(scale), base)
     if order is not None:
         out = out.permute([order.index(d) for d in range(mu.dim())])
     return out, total
@@ -286,18 +391,22 @@ def _sample_kl1(mu, logvar, scale: float, base, eps=None):
 def sample_with_kl(mu, logvar, beta: float = 1.0, batch_size=None, eps=None):
     """(l̃, β·kl_loss): `sample(μ, logσ²)` and `β·vector_kl(μ, logσ²)` of the same arguments, computed together (one kernel pass
     each way per part instead of a sample pass, a KL pass and the additions of their cotangents)  [REF src/models/GOKU.jl:155-163],
-    [REF src/utils/utils.jl:15-49]. For the GOKU tuple the second part's total continues the first's."""
+    [REF src/utils/utils.jl:15-49]. For the GOKU tuple the second part's total continues the first's. `beta`: a number, or a β word
+    (module docstring) — the lde_*_dev entry points with divisor = the batch size."""
+    word, beta = beta_word(beta)
     if isinstance(mu, tuple):
         if eps is None:
-            pair = _sample_kl_pair(mu, logvar, beta, batch_size)
+            pair = _sample_kl_pair(mu, logvar, beta if word is None else word, batch_size)
             if pair is not None:
                 return pair
         outs, total = [], None
         for i, (m, s) in enumerate(zip(mu, logvar)):
-            o, total = _sample_kl1(m, s, beta / (batch_size or m.shape[1]), total, None if eps is None else eps[i])
+            B = batch_size or m.shape[1]
+            o, total = _sample_kl1(m, s, B if word is not None else beta / B, total, None if eps is None else eps[i], word)
             outs.append(o)
         return tuple(outs), total
-    return _sample_kl1(mu, logvar, beta / (batch_size or mu.shape[1]), None, eps)
+    B = batch_size or mu.shape[1]
+    return _sample_kl1(mu, logvar, B if word is not None else beta / B, None, eps, word)
 
 
 def _kl_sum(mu, logvar, scale: float):
@@ -315,6 +424,20 @@ def vector_kl(mu, logvar, batch_size=None):
             out = out + p
         return out
     return _kl_sum(mu, logvar, 1.0 / (batch_size or mu.shape[1]))
+
+
+def beta_kl(mu, logvar, beta, batch_size=None):
+    """β·vector_kl(μ, logσ²) as ONE scalar with β inside the reduction's last kernel. With a β word (module docstring):
+    lde_kl_forward_dev — (β ⊘ B)·Σ kl, for the GOKU tuple the second part's total continuing the first's through `base`; the pullback is
+    lde_kl_backward_dev. With a number: `beta * vector_kl(...)`, as `loss_batch` has always written it."""
+    word, beta = beta_word(beta)
+    if word is None:
+        return beta * vector_kl(mu, logvar, batch_size)
+    total = None
+    for m, s in (zip(mu, logvar) if isinstance(mu, tuple) else [(mu, logvar)]):
+        mm, ss, _ = _same_layout(m.float(), s.float())
+        total = _KlDevFn.apply(mm, ss, word, float(batch_size or m.shape[1]), total)
+    return total
 
 
 def reconstruction_loss(x, x_hat, batch_size=None, plus=None):

@@ -18,6 +18,7 @@ no kernel of its own.
 from __future__ import annotations
 
 import contextlib
+import copy
 import math
 import os
 from typing import Callable, Iterable, List, Optional, Sequence
@@ -28,7 +29,7 @@ import torch
 from . import _lib as L
 from .api import Decoder
 from .chain import decode, decode_loss, default_decoder_layers
-from .loss import reconstruction_loss, sample, sample_with_kl, vector_kl  # noqa: F401
+from .loss import beta_kl, beta_word, reconstruction_loss, sample, sample_with_kl, vector_kl  # noqa: F401
 from .loss import backward as _loss_backward
 from .recurrent import Encoder, default_encoder_layers, encode
 
@@ -84,7 +85,9 @@ def kl(mu, logvar):
 
 def loss_batch(model, x, t, beta: float, variational: bool, batch_size: Optional[int] = None):
     """reconstruction_loss + β·kl_loss with reconstruction_loss = sum(mean((x − x̂)², dims=(2,3)))  [REF model_train.jl:225-238].
-    `batch_size`: the GLOBAL minibatch size when x is one rank's shard (the per-rank losses then add up to the reference's)."""
+    `batch_size`: the GLOBAL minibatch size when x is one rank's shard (the per-rank losses then add up to the reference's).
+    `beta`: a number, or a β word — one float32 on the GPU that the loss kernels read at run time (loss.py), so that a captured step
+    follows the β schedule; the non-variational loss is then reconstruction_loss(x, x̂, plus=beta_kl(μ, logσ², β))."""
     if variational and _FUSED_LOSS:
         # the same expression with the sample and the KL term read in one pass and the scalar additions folded into the
         # reductions (loss.sample_with_kl): encoder → (l̃, β·kl) → decoder → reconstruction_loss + β·kl
@@ -93,6 +96,8 @@ def loss_batch(model, x, t, beta: float, variational: bool, batch_size: Optional
         loss, _ = decode_loss(model.decoder, l_tilde, t, x, batch_size, plus=bkl, want_x_hat=False)   # (the reconstructor and the loss as one autograd node; x̂ is not kept)
         return loss
     (x_hat, _z, _l), mu, logvar = model(x, t, variational)
+    if beta_word(beta)[0] is not None:
+        return reconstruction_loss(x, x_hat, batch_size, plus=beta_kl(mu, logvar, beta, batch_size))
     return reconstruction_loss(x, x_hat, batch_size) + beta * vector_kl(mu, logvar, batch_size)
 
 
@@ -611,7 +616,8 @@ def train(model: LatentDiffEqModel, loader_train: Iterable, val_set, dt: float, 
           lr: float = 1e-3, decay: float = 1e-10, start_beta: float = 0.0, end_beta: float = 1.0, n_cycle: int = 3, ratio: float = 0.9,
           progressive_training: bool = False, prog_training_duration: int = 0, start_seq_len: int = 0, variational: bool = True,
           rng: Optional[np.random.Generator] = None, on_epoch: Optional[Callable] = None, grad_sync: Optional[Callable] = None,
-          clip_norm: Optional[float] = None, clip_mode: str = "global", optimiser: str = "adamw"):
+          clip_norm: Optional[float] = None, clip_mode: str = "global", optimiser: str = "adamw", graphed: bool = False,
+          check_every: int = 50):
     """The epoch loop of the example script  [REF examples/pendulum_friction-less/model_train.jl:138-218]: cyclical β, optional
     progressive sequence length, Flux-flavour ADAMW, validation loss after every minibatch, best weights kept. `loader_train` yields
     x [pixels, B, full_seq_len] tensors on the model's device; `grad_sync` is called between backward and the optimiser step
@@ -619,11 +625,35 @@ def train(model: LatentDiffEqModel, loader_train: Iterable, val_set, dt: float, 
     every update — on the GPU the optimiser is then built in its capturable, guarded, clipped form (one submission per step, a step with
     non-finite gradients or norms is withheld) and is left in `model.optimizer`, where `grad_norms()` and `guard_state()` can be read;
     None: the loop as it was. `optimiser`: "adamw" (the scripts' choice) or "adabelief" — FluxAdaBelief, the alternative they name
-    [REF model_train.jl:136-138], with the same η, β and decay. Returns (history, best_state)."""
+    [REF model_train.jl:136-138], with the same η, β and decay. Returns (history, best_state).
+    `graphed=True` (every parameter on a GPU): the loop on captured graphs. The optimiser is built capturable and guarded (clipped too with
+    `clip_norm`) and left in `model.optimizer`; β lives in ONE device word that the host fills once per epoch and the loss kernels read
+    (loss.py: the β word), so one capture serves the whole schedule; the training step AND the validation pass that follows it are one
+    `GraphedStep(guard=opt, check_every=check_every)` whose static input is the minibatch window. A minibatch then costs the window copy,
+    one graph launch and two scalar device-to-device copies into the epoch's history tensor; the host reads that tensor once per epoch —
+    which is also when `val_loss < best` is decided, as in the reference [REF model_train.jl:212-217] — and otherwise synchronises only at
+    the guard's look every `check_every` replays (a withheld step's loss is recorded as it came out). The encoder's branch streams
+    (`recurrent._BRANCH_STREAMS`) are off for the call — a capture needs one stream — and put back at the end; with progressive training
+    the epochs shorter than `seq_len` run the same step eagerly (same optimiser, same β word) and the capture happens at the first epoch
+    that runs at `seq_len`: no graph per sequence length. `on_epoch` sees the epoch's history after the host has read it; if it solves
+    with the model on another time grid it should do so on a decoder of its own (the captured solve reads the grid its handle holds). Not here: η on
+    the device (the reference's η is constant), and the multi-GPU split — `grad_sync` with `graphed=True` is refused: the collective stays
+    outside the graphs, which is `GraphedStep(between=, fn2=)` used directly."""
     if optimiser not in ("adamw", "adabelief"):
         raise ValueError(f"train(optimiser={optimiser!r}): 'adamw' or 'adabelief'")
     Opt = FluxADAMW if optimiser == "adamw" else FluxAdaBelief
     params = model.parameters()
+    if graphed:
+        if grad_sync is not None:
+            raise ValueError("train(graphed=True) takes no grad_sync: the all-reduce stays outside the graphs — build the step as "
+                             "GraphedStep(between=, fn2=) (the two-graph multi-GPU form is not inside train())")
+        if not (params and all(p.is_cuda for p in params)):
+            raise ValueError("train(graphed=True) needs every parameter on a GPU")
+        if check_every < 1:
+            raise ValueError("check_every must be at least 1")
+        return _train_graphed(model, Opt, params, loader_train, val_set, dt, epochs, seq_len, full_seq_len, lr, decay, start_beta, end_beta,
+                              n_cycle, ratio, progressive_training, prog_training_duration, start_seq_len, variational, rng, on_epoch,
+                              clip_norm, clip_mode, int(check_every))
     if clip_norm is None:
         opt = Opt(params, lr=lr, betas=(0.9, 0.999), decay=decay)      # ADAMW(η, (0.9, 0.999), decay), Flux flavour
     else:
@@ -660,4 +690,95 @@ def train(model: LatentDiffEqModel, loader_train: Iterable, val_set, dt: float, 
         if val_loss < best:
             best = val_loss
             best_state = [p.detach().clone() for p in params]
+    return history, best_state
+
+
+def _train_graphed(model, Opt, params, loader_train, val_set, dt, epochs, seq_len, full_seq_len, lr, decay, start_beta, end_beta, n_cycle, ratio,
+                   progressive_training, prog_training_duration, start_seq_len, variational, rng, on_epoch, clip_norm, clip_mode, check_every):
+    """train(graphed=True): see there. The step function is the eager loop's body with β read from the word and the two losses left on
+    the device; `GraphedStep` replays it once an epoch runs at `seq_len`."""
+    from . import recurrent as _rec
+    dev = params[0].device
+    opt = Opt(params, lr=lr, betas=(0.9, 0.999), decay=decay, capturable=True, guard=True, clip_norm=clip_norm, clip_mode=clip_mode)
+    model.optimizer = opt
+    schedule = frange_cycle_linear(epochs, start_beta, end_beta, n_cycle, ratio)
+    if progressive_training:
+        prog = np.rint(np.linspace(start_seq_len, seq_len, prog_training_duration)).astype(int)
+    else:
+        prog_training_duration = 0
+    t_val = np.arange(val_set.shape[2]) * dt
+    beta_w = torch.zeros(1, dtype=torch.float32, device=dev)         # the β word: written once per epoch, outside any graph
+    val_static = torch.zeros((), dtype=torch.float32, device=dev)    # the validation loss of the last step
+    # The validation pass solves on ITS OWN solver handle (a twin of the decoder's diffeq: same settings, same weights by reference): a
+    # handle keeps ONE save-time grid on the device and restages it whenever a call brings another — with the training window's grid and
+    # the validation set's alternating on one handle that upload would sit inside the graph, twice per replay, reading host staging
+    # buffers that later eager calls reuse. With a handle per grid the warm-up leaves both grids in place and the graph uploads nothing.
+    val_model = copy.copy(model)
+    val_model.decoder = copy.copy(model.decoder)
+    val_model.decoder.diffeq = copy.copy(model.decoder.diffeq)
+    val_model.decoder.diffeq._handle = None
+    window = [None]                                                  # the minibatch window the step reads (static once captured)
+    t_now = [None]
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = loss_batch(model, window[0], t_now[0], beta_w, variational)
+        _loss_backward(loss)
+        L.join_weight_gradients()
+        opt.step()
+        model.refresh_weights()
+        with torch.no_grad():
+            val_static.copy_(loss_batch(val_model, val_set, t_val, beta_w, False))
+        return loss
+
+    try:
+        n_rows = max(int(len(loader_train)), 1)
+    except TypeError:
+        n_rows = 64
+    rows = torch.zeros(n_rows, 2, dtype=torch.float32, device=dev)   # (loss, validation loss) per minibatch of the epoch
+    best, best_state, history = float("inf"), None, []
+    gs = None
+    keep_branch = _rec._BRANCH_STREAMS
+    _rec._BRANCH_STREAMS = False
+    try:
+        for epoch in range(1, epochs + 1):
+            beta_w.fill_(float(schedule[epoch - 1]))
+            sl = int(prog[epoch - 1]) if epoch <= prog_training_duration else seq_len
+            t_now[0] = np.arange(sl) * dt
+            k = 0
+            for x in loader_train:
+                xb = time_loader(x, full_seq_len, sl, rng)
+                if k == rows.shape[0]:                                # a loader without a length that outgrew the guess
+                    rows = torch.cat([rows, torch.zeros_like(rows)])
+                if sl != seq_len:                                     # progressive training: not yet the captured length — eager
+                    window[0] = xb
+                    loss = step().detach()
+                elif gs is None:
+                    # the first minibatch at seq_len: size every workspace with eager passes whose update is withheld (the parameters, the
+                    # moments, the step count and the guard's counters stay what they were), capture, then replay for the real step
+                    window[0] = xb.detach().clone().contiguous()
+                    side = torch.cuda.Stream(dev)
+                    side.wait_stream(torch.cuda.current_stream(dev))
+                    with torch.cuda.stream(side):
+                        for _ in range(2):
+                            with opt.withheld():
+                                step()
+                    torch.cuda.current_stream(dev).wait_stream(side)
+                    gs = GraphedStep(step, static_inputs=[window[0]], warmup=0, guard=opt, check_every=check_every)
+                    loss = gs.replay(xb)
+                else:
+                    loss = gs.replay(xb)
+                rows[k, 0].copy_(loss)
+                rows[k, 1].copy_(val_static)
+                k += 1
+            got = rows[:k].tolist()                                   # the epoch's one read
+            history.extend((epoch, float(a), float(b)) for a, b in got)
+            if on_epoch is not None:
+                on_epoch(epoch, history)
+            if got and got[-1][1] < best:
+                best = got[-1][1]
+                best_state = [p.detach().clone() for p in params]
+    finally:
+        _rec._BRANCH_STREAMS = keep_branch
+    model.graphed_step, model.beta_word = gs, beta_w              # (left for inspection, like model.optimizer)
     return history, best_state
