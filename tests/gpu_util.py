@@ -173,8 +173,31 @@ class NativeChain:
         L.check(self.lib.lde_chain_set_dtype(self.h, {"f32": L.DTYPE_F32, "bf16": L.DTYPE_BF16}[dtype]), self.h,
                 "lde_chain_set_dtype", chain=True)
 
-    def forward(self, x):
-        xd = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to("cuda")
+    @staticmethod
+    def _dev(a, offset=0):
+        """numpy → float32 device tensor (a device tensor is taken as it is); `offset` floats into a larger buffer: offset = 1 puts
+        the operand one float past a 16-byte boundary (the allocator's blocks are 512-byte aligned)."""
+        if isinstance(a, torch.Tensor):
+            assert offset == 0 and a.is_cuda and a.dtype == torch.float32 and a.is_contiguous()
+            return a
+        a = np.ascontiguousarray(a, np.float32)
+        if not offset:
+            return torch.from_numpy(a).to("cuda")
+        buf = torch.empty(a.size + offset, device="cuda", dtype=torch.float32)
+        t = buf[offset:].view(a.shape)
+        t.copy_(torch.from_numpy(a))
+        assert t.data_ptr() % 16 == 4 * offset % 16
+        return t
+
+    def _dW(self, dW0):
+        """The weight-gradient buffer a pullback adds to: zeros, or a copy of `dW0` (f32 in either dtype of the chain)."""
+        if dW0 is None:
+            return torch.zeros((self.nW,), device="cuda")
+        assert np.shape(dW0) == (self.nW,)
+        return torch.from_numpy(np.array(dW0, np.float32)).to("cuda")
+
+    def forward(self, x, x_offset=0):
+        xd = self._dev(x, x_offset)
         N = xd.shape[0]
         y = torch.full((N, self.sizes[-1]), 7.0, device="cuda")
         s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -183,8 +206,8 @@ class NativeChain:
         torch.cuda.synchronize()
         return y.cpu().numpy()
 
-    def forward_save(self, x):
-        xd = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to("cuda")
+    def forward_save(self, x, x_offset=0):
+        xd = self._dev(x, x_offset)
         N = xd.shape[0]
         y = torch.full((N, self.sizes[-1]), 7.0, device="cuda")
         self.lib.lde_chain_saved_floats.restype = C.c_int64
@@ -195,14 +218,11 @@ class NativeChain:
         torch.cuda.synchronize()
         return y.cpu().numpy(), saved
 
-    def backward_saved(self, x, y, dy, saved, need_dx=True):
-        dev = "cuda"
-        xd = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
-        yd = torch.from_numpy(np.ascontiguousarray(y, np.float32)).to(dev)
-        dyd = torch.from_numpy(np.ascontiguousarray(dy, np.float32)).to(dev)
+    def backward_saved(self, x, y, dy, saved, need_dx=True, dW0=None, x_offset=0):
+        xd, yd, dyd = self._dev(x, x_offset), self._dev(y), self._dev(dy)
         N = xd.shape[0]
-        dx = torch.full_like(xd, 7.0) if need_dx else None
-        dW = torch.zeros((self.nW,), device=dev)
+        dx = torch.full((N, self.sizes[0]), 7.0, device="cuda") if need_dx else None
+        dW = self._dW(dW0)
         s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         L.check(self.lib.lde_chain_backward_saved(self.h, C.c_void_p(xd.data_ptr()), C.c_void_p(yd.data_ptr()), C.c_void_p(dyd.data_ptr()),
                                                   C.c_void_p(saved.data_ptr()), N,
@@ -211,14 +231,11 @@ class NativeChain:
         torch.cuda.synchronize()
         return (None if dx is None else dx.cpu().numpy()), dW.cpu().numpy()
 
-    def backward(self, x, y, dy, need_dx=True, dW0=None):
-        dev = "cuda"
-        xd = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
-        yd = torch.from_numpy(np.ascontiguousarray(y, np.float32)).to(dev)
-        dyd = torch.from_numpy(np.ascontiguousarray(dy, np.float32)).to(dev)
+    def backward(self, x, y, dy, need_dx=True, dW0=None, x_offset=0):
+        xd, yd, dyd = self._dev(x, x_offset), self._dev(y), self._dev(dy)
         N = xd.shape[0]
-        dx = torch.full_like(xd, 7.0) if need_dx else None
-        dW = torch.zeros((self.nW,), device=dev) if dW0 is None else torch.from_numpy(np.ascontiguousarray(dW0, np.float32)).to(dev)
+        dx = torch.full((N, self.sizes[0]), 7.0, device="cuda") if need_dx else None
+        dW = self._dW(dW0)
         s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         L.check(self.lib.lde_chain_backward(self.h, C.c_void_p(xd.data_ptr()), C.c_void_p(yd.data_ptr()),
                                             C.c_void_p(dyd.data_ptr()), N,

@@ -55,7 +55,7 @@ def _step(enc, dec, mods, x, ts, eps_seed):
 
 def test_mixed_precision_goku_step_b256():
     import torch
-    from tests.test_gpu_chain_bf16 import bf16r, chain_ref
+    from tests.chain_exact_ref import bf16r, chain_ref
     from latentdiffeq_amd import _lib as L
     B, T, NI = 256, 50, 784
     torch.manual_seed(1000)
