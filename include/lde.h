@@ -262,7 +262,7 @@ int lde_set_noise(lde_handle* h, uint64_t seed, uint64_t offset, uint64_t first_
  * is LDE_ERR_INVALID_ARG for every right-hand side without an MLP.)
  * The dual record has the layout below with NP = 6: J float [T][2][6][B] at A(4B), the step trace at A(4B) + A(48TB). Failure semantics,
  * statistics, lde_step_record_* and option "step_trace" are those of the pendulum's dual solve. lde_last_kernel: "k_lv_forward_dual" /
- * "k_lv_adjoint_dual". */
+ * "k_lv_adjoint_dual" (labels of this path, not symbols: see lde_last_kernel). */
 
 /* Pre-size the handle's workspace for batches up to B and T save points (so that later
  * lde_forward/lde_adjoint calls allocate nothing and can be captured in a hipGraph). */
@@ -390,7 +390,10 @@ const char* lde_last_error(const lde_handle* h);
 /* The name (prefix) of the solve kernel the last lde_forward (which = 0) / lde_adjoint (which = 1) on this handle launched, e.g.
  * "k_pend_forward_lp", "k_pend_adjoint_disc_tp", "k_mlpc" — "" before the first call. A measurement aid like lde_get_phase_ms: bench.py attaches
  * HBM counter bytes from a committed rocprofv3 summary to its roofline line only when that summary's kernel IS the one the run launched
- * (a stale summary must not survive a kernel change). Static strings; never NULL. */
+ * (a stale summary must not survive a kernel change). Static strings; never NULL.
+ * Under LDE_SENSE_FORWARD_DUAL the strings are labels of the path taken, not symbol names — the deterministic systems run one kernel
+ * template over the system: "k_pend_forward_dual" / "k_pend_adjoint_dual" (the pendulums), "k_lv_forward_dual" / "k_lv_adjoint_dual"
+ * (Lotka–Volterra), "k_pend_forward_sde" / "k_pend_adjoint_dual" (the stochastic pendulum). */
 const char* lde_last_kernel(const lde_handle* h, int which);
 
 

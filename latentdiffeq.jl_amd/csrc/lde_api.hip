@@ -28,18 +28,13 @@ int launch_pend_adjoint(int kind, int solver, int sensealg, const float* z_out, 
                         const float* dz_out, float* dz0, float* dtheta, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret,
                         hipStream_t stream, const PendTune& tn);
 const char* pend_last_kernel(int which);
-int launch_pend_forward_dual(int kind, int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o,
-                             const DualRec& rec, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej,
-                             int32_t* ret, hipStream_t stream);
-int launch_pend_adjoint_dual(const DualRec& rec, const float* dz_out, int T, int B, float* dz0, float* dtheta, int32_t* nfe,
-                             int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
+int launch_forward_dual(int kind, int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o, const DualRec& rec,
+                        float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
+int launch_adjoint_dual(int kind, const DualRec& rec, const float* dz_out, int T, int B, float* dz0, float* dtheta, int32_t* nfe,
+                        int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
 int launch_pend_forward_sde(int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o, const DualRec& rec,
                             const SdeNoise& nz, bool over, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej,
                             int32_t* ret, hipStream_t stream);
-int launch_lv_forward_dual(int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o, const DualRec& rec,
-                           float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
-int launch_lv_adjoint_dual(const DualRec& rec, const float* dz_out, int T, int B, float* dz0, float* dtheta, int32_t* nfe, int32_t* nacc,
-                           int32_t* nrej, int32_t* ret, hipStream_t stream);
 struct MlpPlan;
 int mlp_plan_create(const lde_problem_desc& d, MlpPlan** out, std::string& err);
 void mlp_plan_destroy(MlpPlan* p);
@@ -418,17 +413,14 @@ int lde_forward(lde_handle* h, const float* z0, const float* theta, const double
     if (r.t) h->rec_last[0] = lde::StepRec{r.n, r.t, r.dt, nullptr, r.cap, B};   // (lde_get_step_record's view of the trace)
     h->last_B[0] = B;
     int32_t** st = h->st[0];
+    // lde_last_kernel's strings name the path taken (include/lde.h), not a symbol: the deterministic systems share k_forward_dual
     if (is_sde(h->d)) {   // the stochastic pendulum: its own stepper writes the same dual record (csrc/lde_pend_sde.hip)
       rc = lde::launch_pend_forward_sde(h->d.solver, z0, theta, h->ts_dev, o, r, h->noise, sde_plan(h->d, ts, T).over, z_out, retcode, st[0],
                                         st[1], st[2], st[3], stream);
       h->last_kernel[0] = "k_pend_forward_sde";
-    } else if (is_lv(h->d)) {   // Lotka–Volterra: six partials per component, kernels and dispatch of its own (csrc/lde_lv_dual.hip)
-      rc = lde::launch_lv_forward_dual(h->d.solver, z0, theta, h->ts_dev, o, r, z_out, retcode, st[0], st[1], st[2], st[3], stream);
-      h->last_kernel[0] = "k_lv_forward_dual";
-    } else {
-      rc = lde::launch_pend_forward_dual(h->d.rhs_kind, h->d.solver, z0, theta, h->ts_dev, o, r, z_out, retcode, st[0], st[1], st[2], st[3],
-                                         stream);
-      h->last_kernel[0] = "k_pend_forward_dual";
+    } else {              // the pendulums and Lotka–Volterra: one kernel over the system (csrc/lde_dual.hip)
+      rc = lde::launch_forward_dual(h->d.rhs_kind, h->d.solver, z0, theta, h->ts_dev, o, r, z_out, retcode, st[0], st[1], st[2], st[3], stream);
+      h->last_kernel[0] = is_lv(h->d) ? "k_lv_forward_dual" : "k_pend_forward_dual";
     }
     if (rc) h->err = "lde_forward: kernel launch failed";
     return rc;
@@ -491,13 +483,8 @@ int lde_adjoint(lde_handle* h, const float* z_out, const float* theta, const dou
       }
       r = h->dual_last;
     }
-    if (is_lv(h->d)) {
-      rc = lde::launch_lv_adjoint_dual(r, dz_out, T, B, dz0, dtheta, st[0], st[1], st[2], st[3], stream);
-      h->last_kernel[1] = "k_lv_adjoint_dual";
-    } else {
-      rc = lde::launch_pend_adjoint_dual(r, dz_out, T, B, dz0, dtheta, st[0], st[1], st[2], st[3], stream);
-      h->last_kernel[1] = "k_pend_adjoint_dual";
-    }
+    rc = lde::launch_adjoint_dual(h->d.rhs_kind, r, dz_out, T, B, dz0, dtheta, st[0], st[1], st[2], st[3], stream);
+    h->last_kernel[1] = is_lv(h->d) ? "k_lv_adjoint_dual" : "k_pend_adjoint_dual";
     if (rc) h->err = "lde_adjoint: kernel launch failed";
     return rc;
   }

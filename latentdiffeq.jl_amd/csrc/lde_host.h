@@ -231,7 +231,7 @@ static PendRing pend_ring_shape(bool recording, const lde::PendTune& tn) {
 }
 
 // Which pullback of the analytic right-hand sides serves an lde_adjoint (csrc/lde_pendulum.hip's launch code switches on this; DESIGN.md
-// §4.2). LDE_SENSE_FORWARD_DUAL has a pullback of its own (csrc/lde_pend_dual.hip).
+// §4.2). LDE_SENSE_FORWARD_DUAL has a pullback of its own (csrc/lde_dual.hip).
 enum PendAdjMap {
   PEND_ADJ_SEQ = 0,   // k_pend_adjoint: a lane per trajectory, the reverse-time solve (LDE_SENSE_BACKSOLVE[_CHECKPOINTED])
   PEND_ADJ_FUSED,     // k_pend_adjoint_fused: a workgroup per trajectory, a lane per save interval, the interval operators composed in a tree
@@ -266,10 +266,10 @@ static int pend_dispatch(int kind, int solver, bool adaptive, F&& f) {
   return LDE_ERR_UNSUPPORTED;
 }
 
-// The template arguments of the Lotka–Volterra kernels (csrc/lde_lv_dual.hip): calls f(SOLVER) with a std::integral_constant for exactly the
-// three (solver, adaptive) combinations validate() admits for LDE_RHS_LOTKA_VOLTERRA — Tsit5 adaptive, Tsit5 fixed-step, RK4 fixed-step (the
-// kernel reads `adaptive` at run time) — and returns what f returns; anything else is LDE_ERR_UNSUPPORTED. A dispatch of its own:
-// pend_dispatch serves the pendulums' six combinations and nothing else.
+// The template arguments of k_forward_dual (csrc/lde_dual.hip) for Lotka–Volterra: calls f(SOLVER) with a std::integral_constant for exactly
+// the three (solver, adaptive) combinations validate() admits for LDE_RHS_LOTKA_VOLTERRA — Tsit5 adaptive, Tsit5 fixed-step, RK4 fixed-step
+// (the kernel reads `adaptive` at run time) — and returns what f returns; anything else is LDE_ERR_UNSUPPORTED. A dispatch of its own:
+// pend_dispatch serves the pendulums' six combinations and nothing else; the two meet in launch_forward_dual's one launch lambda.
 template <class F>
 static int lv_dispatch(int solver, bool adaptive, F&& f) {
   if (solver == LDE_SOLVER_TSIT5) return f(std::integral_constant<int, LDE_SOLVER_TSIT5>{});
@@ -277,13 +277,13 @@ static int lv_dispatch(int solver, bool adaptive, F&& f) {
   return LDE_ERR_UNSUPPORTED;
 }
 
-// Which mapping serves a solve under LDE_SENSE_FORWARD_DUAL (csrc/lde_pend_dual.hip switches on this). Kept apart from pend_forward_mapping,
-// whose seven results tests/host_logic_driver.cpp pins: the dual solve has ONE mapping, a lane per trajectory (two values and six partials in
-// registers), and the batch only sizes its workgroups — a wave each up to 4 096 trajectories (one wave per CU as long as there are CUs to spare),
-// four waves beyond.
+// Which mapping serves a solve under LDE_SENSE_FORWARD_DUAL (csrc/lde_dual.h: dual_block switches on this, for every system and for the
+// stochastic pendulum). Kept apart from pend_forward_mapping, whose seven results tests/host_logic_driver.cpp pins: the dual solve has ONE
+// mapping, a lane per trajectory (two values and their partials in registers), and the batch only sizes its workgroups — a wave each up to
+// 4 096 trajectories (one wave per CU as long as there are CUs to spare), four waves beyond.
 enum PendDualMap {
-  PEND_DUAL_LANE64 = 0,   // k_pend_forward_dual, 64-lane workgroups
-  PEND_DUAL_LANE256       // k_pend_forward_dual, 256-lane workgroups
+  PEND_DUAL_LANE64 = 0,   // k_forward_dual / k_pend_forward_sde, 64-lane workgroups
+  PEND_DUAL_LANE256       // … 256-lane workgroups
 };
 static PendDualMap pend_dual_mapping(int B) { return B <= 4096 ? PEND_DUAL_LANE64 : PEND_DUAL_LANE256; }
 

@@ -6,12 +6,13 @@
 // (trajectory, substep) is ONE Philox4x32-10 block keyed by the caller's seed (csrc/lde_philox.h: lde_randn's device code) — a pure function
 // of its counter, so the launch geometry, a shard's place in the batch and a graph replay do not enter it.
 //
-// k_pend_forward_sde: a lane per trajectory, modelled on k_pend_forward_dual — the state and its six partials ∂(x, v)/∂(x₀, v₀, L) in registers
-// (the noise has zero partials: the gradient is the exact derivative of the scheme along the drawn path, the reference's
-// ForwardDiffSensitivity() at a fixed step), `ts` in LDS where it fits, one hw_sincos on the step's turn anchor per evaluation, one Philox block
-// and one Box–Muller pair per substep; per save interval n_j, h_j and σ·√h are formed once. ẑ and J_j go out trajectory fastest, as the dual
-// kernel writes them: a wave stores whole lines. The pullback is k_pend_adjoint_dual (csrc/lde_pend_dual.hip) on the dual record this
-// kernel leaves. Per trajectory: 12 B read, 8·T + 24·T B written.
+// k_pend_forward_sde: a lane per trajectory, its own stepper inside the dual solve's frame — the state and its six partials ∂(x, v)/∂(x₀, v₀, L)
+// in registers (the noise has zero partials: the gradient is the exact derivative of the scheme along the drawn path, the reference's
+// ForwardDiffSensitivity() at a fixed step), one hw_sincos on the step's turn anchor per evaluation, one Philox block and one Box–Muller pair
+// per substep; per save interval n_j, h_j and σ·√h are formed once. What surrounds the stepper is csrc/lde_dual.h's, as in k_forward_dual:
+// `ts` in LDS where it fits, the (ẑ_j, J_j) rows trajectory fastest (a wave stores whole lines), the failed solve's fill, the closing
+// statistics, the workgroup size; the system is csrc/lde_pend_dualrhs.h's PendDual. The pullback is k_adjoint_dual<3> (csrc/lde_dual.hip) on
+// the dual record this kernel leaves. Per trajectory: 12 B read, 8·T + 24·T B written.
 #include "lde_device.h"
 #include "lde_host.h"
 #include "lde_pend_dualrhs.h"
@@ -26,26 +27,18 @@ __global__ void __launch_bounds__(256) k_pend_forward_sde(const float2* __restri
                                                           float2* __restrict__ z_out, int32_t* __restrict__ retcode,
                                                           int32_t* __restrict__ st_nfe, int32_t* __restrict__ st_nacc,
                                                           int32_t* __restrict__ st_nrej, int32_t* __restrict__ st_ret) {
-  extern __shared__ __attribute__((aligned(16))) double s_ts_sde[];
+  using SYS = PendDual<LDE_RHS_PENDULUM>;
+  constexpr int NP = SYS::NP, DN = SYS::DN;
   const int T = o.T, B = o.B;
-  if (TS_LDS)
-    for (int i = threadIdx.x; i < T; i += blockDim.x) s_ts_sde[i] = ts_g[i];
-  __syncthreads();
-  auto s_ts = [&](int i) -> double { return TS_LDS ? s_ts_sde[i] : ts_g[i]; };
+  dual_stage_ts<TS_LDS>(ts_g, T);
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
 
-  auto save = [&](int j, const float (&u)[DN]) {
-    z_out[(size_t)j * B + b] = make_float2(u[0], u[1]);
-    float* Jj = rec.J + (size_t)j * 6 * B + b;
-#pragma unroll
-    for (int c = 0; c < 6; c++) Jj[(size_t)c * B] = u[2 + c];
-  };
-
+  SYS f = SYS::load(theta, b);
+  float y[DN];
   const float2 zi = z0[b];
-  PendDual<LDE_RHS_PENDULUM> f(theta[b]);
-  float y[DN] = {zi.x, zi.y, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f};   // seeds: ∂y₀/∂x₀ = e₀, ∂y₀/∂v₀ = e₁, ∂y₀/∂L = 0
-  save(0, y);   // ẑ(ts[0]) = ẑ₀
+  SYS::seed(zi.x, zi.y, y);
+  dual_save<NP>(z_out, rec, 0, B, b, y);   // ẑ(ts[0]) = ẑ₀
   int ret = over ? LDE_RET_MAXITERS : LDE_RET_SUCCESS;
   long long nsub = 0;
 
@@ -57,7 +50,7 @@ __global__ void __launch_bounds__(256) k_pend_forward_sde(const float2* __restri
     unsigned s = 0;   // the substep index of the whole solve: the counter's second word
     double tprev = o.t_first;
     for (int j = 1; j < T; j++) {
-      const double tj = s_ts(j), D = tj - tprev;
+      const double tj = dual_ts<TS_LDS>(ts_g, j), D = tj - tprev;
       const int n = sde_substeps(D, o.dt_fixed);
       const double hd = D / (double)n;
       const float h = (float)hd, hh = 0.5f * h, sw = 0.01f * sqrtf(h);
@@ -93,27 +86,14 @@ __global__ void __launch_bounds__(256) k_pend_forward_sde(const float2* __restri
       nsub += n;
       // (a non-finite value never becomes finite again under y ← y + …: one look per save interval sees it)
       if (!all_finite<DN>(y)) { ret = LDE_RET_NONFINITE; break; }
-      save(j, y);
+      dual_save<NP>(z_out, rec, j, B, b, y);
       tprev = tj;
     }
   }
-  if (ret != LDE_RET_SUCCESS) {   // failed solve ⇒ NaN block and zero Jacobians (zero gradient) [REF GOKU.jl:114]
-    const float qn = __int_as_float(0x7fc00000);
-    for (int j = 0; j < T; j++) {
-      z_out[(size_t)j * B + b] = make_float2(qn, qn);
-      float* Jj = rec.J + (size_t)j * 6 * B + b;
-#pragma unroll
-      for (int c = 0; c < 6; c++) Jj[(size_t)c * B] = 0.f;
-    }
-  }
+  if (ret != LDE_RET_SUCCESS) dual_fill_failed<NP>(z_out, rec, T, B, b);
   constexpr int NFE = SOLVER == LDE_SOLVER_EM ? 1 : 2;
   const int nacc = (int)(nsub < 0x3fffffffLL ? nsub : 0x3fffffffLL);   // (int32 statistics: a longer solve saturates)
-  if (retcode) retcode[b] = ret;
-  st_ret[b] = ret;
-  st_nfe[b] = NFE * nacc;
-  st_nacc[b] = nacc;
-  st_nrej[b] = 0;
-  rec.n[b] = ret == LDE_RET_SUCCESS ? nacc : -ret;
+  dual_finish(b, ret, NFE * nacc, nacc, 0, rec, retcode, st_nfe, st_nacc, st_nrej, st_ret);
 }
 
 // ---- host-side launcher (called from lde_api.hip) ------------------------------------------------------------------------------------
@@ -122,7 +102,7 @@ __global__ void __launch_bounds__(256) k_pend_forward_sde(const float2* __restri
 int launch_pend_forward_sde(int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o, const DualRec& rec,
                             const SdeNoise& nz, bool over, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej,
                             int32_t* ret, hipStream_t stream) {
-  const int block = lde_host::pend_dual_mapping(o.B) == lde_host::PEND_DUAL_LANE64 ? 64 : 256, grid = (o.B + block - 1) / block;
+  const int block = dual_block(o.B), grid = (o.B + block - 1) / block;
   const size_t shm = o.T <= DUAL_TS_LDS_MAX ? (size_t)o.T * sizeof(double) : 0;
   auto launch = [&](auto S) -> int {
     if (shm)

@@ -21,10 +21,10 @@ struct StepRec {
   int cap, nseq;
 };
 
-// LDE_SENSE_FORWARD_DUAL's record in device memory (include/lde.h: lde_set_step_record): written by k_pend_forward_dual, read by
-// k_pend_adjoint_dual. J holds ∂ẑ(t_j)/∂(x₀, v₀, L) of every save time, trajectory fastest: element (j, i, q, b) at ((j·2 + i)·3 + q)·B + b.
-// The Lotka–Volterra kernels (csrc/lde_lv_dual.hip) use the same view with NP = 6 partials per component, a compile-time constant of
-// theirs: J [T][2][6][B], element (j, i, q, b) at ((j·2 + i)·6 + q)·B + b. No field says which: the pendulum kernels read none.
+// LDE_SENSE_FORWARD_DUAL's record in device memory (include/lde.h: lde_set_step_record): written by k_forward_dual (csrc/lde_dual.hip) or
+// k_pend_forward_sde, read by k_adjoint_dual. J holds ∂ẑ(t_j)/∂q of every save time, trajectory fastest, with NP partials per component — a
+// compile-time constant of the kernels (the system's: 3 for the pendulums, q = (x₀, v₀, L); 6 for Lotka–Volterra, q = (x₀, y₀, α, β, γ, δ)):
+// element (j, i, q, b) at ((j·2 + i)·NP + q)·B + b. No field says which NP: the kernels read none.
 struct DualRec {
   int32_t* n;    // [B] accepted steps; −retcode for a failed trajectory
   float* J;      // [T][2][NP][B]

@@ -12,7 +12,8 @@ from oracle import oracle as O
 from tests.golden import make_golden as G
 
 FIX = sorted(f for f in glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz"))
-             if not os.path.basename(f).startswith("chain_"))   # chain fixtures: tests/test_oracle_chain.py
+             if not os.path.basename(f).startswith(("chain_", "dual_parent_bits")))   # chain fixtures: tests/test_oracle_chain.py; the dual
+#                                                                                      kernels' recorded bits: tests/test_gpu_dual_bits.py
 
 
 def test_fixture_set_is_complete():

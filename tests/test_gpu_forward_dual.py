@@ -72,6 +72,8 @@ def _replay_gates(od, o32, o64, z0, L, ts, dz, z, J, g0, gL, tr, idx=None):
     for orc in (o32, o64):
         zr, Jr, (r0, rL), retr, _, _ = orc.forward_dual(od, z0, L, ts, dz_out=dz, dual_norm=True, rec=tr)
         assert (retr == 0).all()
+        print(f"replay {orc.dtype.__name__}: |z - ref| {np.abs(z - zr).max():.2e}, J columns {max(_col_err(J, Jr)):.2e}, "
+              f"dz0 {np.abs(g0 - r0).max() / np.abs(r0).max():.2e}, dtheta {np.abs(gL - rL).max() / np.abs(rL).max():.2e}")
         assert np.abs(z - zr).max() <= 2e-5, np.abs(z - zr).max()
         assert max(_col_err(J, Jr)) <= 1e-4, _col_err(J, Jr)
         assert np.abs(g0 - r0).max() <= 1e-4 * np.abs(r0).max()
@@ -158,6 +160,34 @@ def test_batch_sizes(o32, o64, B):
     assert per_traj.max() <= 3e-4 and np.quantile(per_traj, 0.99) <= 1e-4
     nk = tr["n"].sum() if idx is None else tr["n"][idx].sum()
     assert abs(nk - infod["naccept"]) <= 0.02 * infod["naccept"] + 1
+
+
+def test_save_grid_outside_lds(o32, o64):
+    """The pendulum twin of test_gpu_lv.py::test_save_grid_outside_lds: T = DUAL_TS_LDS_MAX + 1 = 6001 save times 1e-3 apart (the kernel reads
+    the grid from global memory), B = 3, Tsit5 at the fixed step 0.0125 — 480 steps, a dozen save times inside each — replayed in the f32 and
+    f64 oracles through _replay_gates. The first 88 save points — those before the T = 100 solve's clipped last step, which starts at 0.0875
+    — are the bits of the solve with the grid in LDS.
+    Measured on the MI355X, on the per-system kernels before csrc/lde_dual.hip and again on it (the same figures), f32 / f64 replay:
+    |ẑ − ref| 1.2e-6 / 1.3e-6, J columns 1.0e-6 / 9.0e-7, dz0 5.7e-7 / 2.3e-6, dθ 9.6e-7 / 4.7e-7 of the largest entry."""
+    T, B, dt = 6001, 3, 0.0125
+    ts = 1e-3 * np.arange(T)
+    nat, od = _native(adaptive=0, dt=dt)
+    nat.set_option("step_trace", 1)
+    nat.set_option("record_capacity", 512)
+    z0, L = O.pendulum_inputs(B, seed=13)
+    dz = O.cotangent(T, B, 2)
+    rec = _Record(nat, B, T)
+    z, ret, st = nat.forward(z0, L, ts)
+    J = rec.J()
+    g0, gL, _, _ = nat.adjoint(z, L, ts, dz)
+    tr = nat.step_record(0, B, cap=512)
+    assert (ret == 0).all() and np.array_equal(z[0], z0)
+    assert (tr["n"] == 480).all() and st["naccept"] == 480 * B and st["nfe"] == (6 * 480 + 1) * B
+    _replay_gates(od, o32, o64, z0, L, ts, dz, z, J, g0, gL, tr)
+    rec100 = _Record(nat, B, 100)
+    z100, ret100, _ = nat.forward(z0, L, ts[:100])
+    assert (ret100 == 0).all()
+    assert np.array_equal(z100[:88], z[:88]) and np.array_equal(rec100.J()[:88], J[:88])
 
 
 def test_failed_trajectory_gives_nan_block_and_zero_gradient():

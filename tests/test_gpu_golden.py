@@ -44,7 +44,8 @@ GRAD_LIM = {
 # held to 1e-4 on the same steps in tests/test_gpu_same_steps.py / tests/test_gpu_discrete.py
 SAME_STEPS_ONLY = {"c4_latentode_tsit5_d32_h128_b16", "c3_pendulum_plus_mlp_b32", "latentode_ref_tsit5_d16_h200_b16"}
 FIX = sorted(f for f in glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz"))
-             if not os.path.basename(f).startswith("chain_"))   # chain fixtures: tests/test_oracle_chain.py
+             if not os.path.basename(f).startswith(("chain_", "dual_parent_bits")))   # chain fixtures: tests/test_oracle_chain.py; the dual
+#                                                                                      kernels' recorded bits: tests/test_gpu_dual_bits.py
 
 
 @pytest.mark.parametrize("path", FIX, ids=[os.path.basename(f)[:-4] for f in FIX])

@@ -1,4 +1,4 @@
-"""GPU: the Lotka–Volterra right-hand side (LDE_RHS_LOTKA_VOLTERRA: k_lv_forward_dual + k_lv_adjoint_dual, csrc/lde_lv_dual.hip) against the
+"""GPU: the Lotka–Volterra right-hand side (LDE_RHS_LOTKA_VOLTERRA: the k_lv_forward_dual + k_lv_adjoint_dual path of csrc/lde_dual.hip) against the
 float64 numpy restatement of the solve on dual numbers (tests/lv_ref.py, pinned on the CPU by tests/test_lv_host.py).
 
 Inputs: seeded, x₀, y₀ ∈ [0.5, 2], α, β, γ, δ ∈ [0.5, 1.5], ts = 0.05·j. Bounds: the pendulum dual tests' (tests/test_gpu_forward_dual.py), each

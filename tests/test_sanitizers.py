@@ -47,12 +47,13 @@ def test_lde_api_is_built_from_the_checked_logic():
     src = open(os.path.join(ROOT, "latentdiffeq.jl_amd", "csrc", "lde_api.hip")).read()
     assert '#include "lde_host.h"' in src and "using namespace lde_host" in src
     pend = open(os.path.join(ROOT, "latentdiffeq.jl_amd", "csrc", "lde_pendulum.hip")).read()
-    dual = open(os.path.join(ROOT, "latentdiffeq.jl_amd", "csrc", "lde_pend_dual.hip")).read()
+    dual = open(os.path.join(ROOT, "latentdiffeq.jl_amd", "csrc", "lde_dual.hip")).read()
     assert "lde_host::pend_forward_mapping(" in pend and "tn.sh_max_b" not in pend and "tn.tl_max_b" not in pend   # the launch code follows the checked function, no thresholds of its own
     assert "lde_host::pend_adjoint_mapping(" in pend and "lde_host::pend_ring_shape(" in pend
     assert "tn." not in pend and "24576" not in pend   # no PendTune field read and no pullback threshold outside lde_host.h
     for s in (pend, dual):   # the (rhs_kind, solver, adaptive) → template-argument chain lives in lde_host::pend_dispatch only
         assert "lde_host::pend_dispatch(" in s and "#define LDE_LAUNCH" not in s
+    assert "lde_host::lv_dispatch(" in dual   # (Lotka–Volterra's three combinations likewise)
     # the MLP path likewise: the family choice and every threshold live in lde_host.h's two mappings, the launch code switches on their result
     mlp = open(os.path.join(ROOT, "latentdiffeq.jl_amd", "csrc", "lde_mlp.hip")).read()
     assert "lde_host::mlp_forward_mapping(" in mlp and "lde_host::mlp_adjoint_mapping(" in mlp
