@@ -56,6 +56,11 @@ enum lde_rhs_kind {
   LDE_RHS_SPENDULUM         = 4,  /* the stochastic pendulum: dx = v dt + σ dW₁, dv = −(G/L) sin x dt + σ dW₂, G=10, L=p[1], σ=0.01 (diagonal,
                                      additive, constant: Itô = Stratonovich)   [REF examples/pendulum_friction-less/pendulum.jl:93-140].
                                      Solvers LDE_SOLVER_EM / LDE_SOLVER_EULER_HEUN, LDE_SENSE_FORWARD_DUAL; see "the stochastic pendulum" below */
+  LDE_RHS_KURAMOTO          = 7,  /* N Kuramoto phase oscillators: dφ_i = ω_i + (K/N) Σ_j sin(φ_j − φ_i), θ = (ω₁ … ω_N, K) per trajectory
+                                     (state_dim N, 2 ≤ N ≤ 7; param_dim N + 1) — the system the reference keeps `transform_after_diffeq` for
+                                     [REF src/models/LatentODE.jl:74]. LDE_SENSE_FORWARD_DUAL only; see "the Kuramoto system" below.
+                                     7, not 6: the value 6 is no right-hand side and stays refused as "unknown rhs_kind" (a test of the
+                                     Lotka–Volterra host logic pins that refusal) */
   LDE_RHS_LOTKA_VOLTERRA    = 5   /* Lotka–Volterra: dx = αx − βxy, dy = −γy + δxy, θ = (α, β, γ, δ) = p[1:4] per trajectory (state_dim 2,
                                      param_dim 4). The first right-hand side with more than one parameter — the reference's `diffeq` plug-in is
                                      "any Julia function" [REF src/models/GOKU.jl:98-130]; this one has no file of its own there.
@@ -117,7 +122,8 @@ enum lde_sensealg {
                                            its two fixed-step schemes, whose only sensealg this is; any other description gives
                                            LDE_ERR_UNSUPPORTED (lde_desc_error names the missing piece). Opt-in: lde_problem_desc_default keeps
                                            LDE_SENSE_DISCRETE. LDE_RHS_LOTKA_VOLTERRA runs the same solve with NP = 6 partials per component,
-                                           (x₀, y₀, α, β, γ, δ): "the Lotka–Volterra system" below. */
+                                           (x₀, y₀, α, β, γ, δ): "the Lotka–Volterra system" below. LDE_RHS_KURAMOTO runs it for N states with
+                                           NP = 2N + 1 partials per component, a lane per partial direction: "the Kuramoto system" below. */
 };
 
 enum lde_activation { LDE_ACT_RELU = 0, LDE_ACT_TANH = 1 };
@@ -264,6 +270,33 @@ int lde_set_noise(lde_handle* h, uint64_t seed, uint64_t offset, uint64_t first_
  * statistics, lde_step_record_* and option "step_trace" are those of the pendulum's dual solve. lde_last_kernel: "k_lv_forward_dual" /
  * "k_lv_adjoint_dual" (labels of this path, not symbols: see lde_last_kernel). */
 
+/* ---- the Kuramoto system (LDE_RHS_KURAMOTO = 7): dφ_i/dt = ω_i + (K/N) Σ_j sin(φ_j − φ_i), i = 1 … N ----
+ * N phase oscillators, N = state_dim, 2 ≤ N ≤ 7; θ = (ω₁ … ω_N, K) per trajectory — theta [(N+1)×B], trajectory b's values at
+ * theta[(N+1)·b … (N+1)·b + N]; dtheta likewise; z0, dz0 [N×B] and z_out, dz_out [T×B×N] as for every D. The system the reference keeps its
+ * `transform_after_diffeq` hook for [REF src/models/LatentODE.jl:74]; the hook itself (the sine of the phases) is the host's.
+ * Evaluated in mean-field form — s_i = sin φ_i, c_i = cos φ_i, S = Σ s_j, C = Σ c_j, f_i = ω_i + (K/N)(c_i S − s_i C): N sine / cosine pairs
+ * per evaluation — with
+ *     ∂f_i/∂φ_j = (K/N)(c_i c_j + s_i s_j) (j ≠ i),  ∂f_i/∂φ_i = −(K/N)(c_i C + s_i S − 1),  ∂f_i/∂ω_j = δ_ij,  ∂f_i/∂K = (c_i S − s_i C)/N.
+ * The sines are the hardware's, each oscillator's whole turns anchored once per step attempt: phases beyond 256 turns keep their coupling
+ * (at |φ| ≈ 2 000 an f32 phase itself is a multiple of 1.2e-4 rad, which is then what limits J).
+ * Served: state_dim = N ∈ 2 … 7, param_dim = N + 1, augment_dim = 0, n_layers = 0 (anything else: LDE_ERR_INVALID_ARG),
+ * LDE_BATCH_PER_TRAJECTORY, LDE_SOLVER_TSIT5 adaptive or fixed-step and LDE_SOLVER_RK4 fixed-step, sensealg LDE_SENSE_FORWARD_DUAL — the solve on
+ * dual numbers described at that enum value, from 2 to N components: NP = 2N + 1 partials per component in the order (φ₀ (N), ω (N), K),
+ * all of them in every norm of the step control, the RMS over the N components. lde_num_weights = 0; dW must be NULL. The enum value is 7:
+ * rhs_kind = 6 is no right-hand side ("unknown rhs_kind").
+ * Refused with LDE_ERR_UNSUPPORTED, lde_desc_error naming the missing piece: another sensealg ("… use LDE_SENSE_FORWARD_DUAL"),
+ * LDE_BATCH_COUPLED, the stochastic steppers and adaptive RK4 (their own texts); lde_set_noise on such a handle.
+ * The kernels give a trajectory a GROUP of G consecutive lanes, one per partial direction — G = 8 for N ≤ 3, 16 for N ≥ 4; lanes NP … G − 1
+ * are pad lanes — and the dual record of this kind has its own extents (A(x) = x rounded up to a multiple of 256 bytes):
+ *     n  int32 [B]                at 0                      as below
+ *     J  float [T][N][B][G]       at A(4B)                  J[j][i][b][q] = ∂ẑ_i(t_j)/∂q_q of trajectory b, q fastest: element
+ *                                                           ((j·N + i)·B + b)·G + q; q = 0 … N−1: φ₀, N … 2N−1: ω, 2N: K; q ≥ NP: 0 (pad lanes)
+ *     t, dt double [cap][B]       at A(4B) + A(4·N·G·TB)    option "step_trace" = 1 only, as below
+ * so that a wave's 64 lanes write, and the pullback's read, 64 consecutive floats per (save time, component). lde_step_record_bytes,
+ * lde_set_step_record, lde_reserve, lde_step_record_status and lde_get_step_record serve it as they serve the other dual records. Failure
+ * semantics (NaN ẑ block, zero J, n = −retcode, zero gradient) and statistics are those of the pendulum's dual solve. lde_last_kernel:
+ * "k_forward_dual_dir" / "k_adjoint_dual_dir". */
+
 /* Pre-size the handle's workspace for batches up to B and T save points (so that later
  * lde_forward/lde_adjoint calls allocate nothing and can be captured in a hipGraph). */
 int lde_reserve(lde_handle* h, int B, int T);
@@ -349,7 +382,7 @@ int lde_set_global_sum_peers(lde_handle* h, int rank, int nranks, void* const* m
  *                                                           LDE_RHS_LOTKA_VOLTERRA
  *     t  double [cap][B]          at A(4B) + A(4·2·NP·TB)   option "step_trace" = 1 only: start time of accepted step s of trajectory b at s·B + b
  *     dt double [cap][B]          at … + A(8·cap·B)         … and its size; cap = lde_step_record_capacity(h, T)
- * (Pendulums: J [T][2][3][B], the trace at A(4B) + A(24TB), as before.) J of a failed trajectory is zero. With "step_trace" = 1 lde_get_step_record(h, 0, …) returns the accepted steps (what a checker replays). */
+ * (Pendulums: J [T][2][3][B], the trace at A(4B) + A(24TB), as before. LDE_RHS_KURAMOTO: J [T][N][B][G], "the Kuramoto system" above.) J of a failed trajectory is zero. With "step_trace" = 1 lde_get_step_record(h, 0, …) returns the accepted steps (what a checker replays). */
 int64_t lde_step_record_bytes(const lde_handle* h, int B, int T);
 int lde_set_step_record(lde_handle* h, void* rec_dev, int64_t bytes);
 /* Did the record hold the solve? lde_step_record_capacity(h, T) = the accepted steps per sequence a record made now would hold;
@@ -393,7 +426,8 @@ const char* lde_last_error(const lde_handle* h);
  * (a stale summary must not survive a kernel change). Static strings; never NULL.
  * Under LDE_SENSE_FORWARD_DUAL the strings are labels of the path taken, not symbol names — the deterministic systems run one kernel
  * template over the system: "k_pend_forward_dual" / "k_pend_adjoint_dual" (the pendulums), "k_lv_forward_dual" / "k_lv_adjoint_dual"
- * (Lotka–Volterra), "k_pend_forward_sde" / "k_pend_adjoint_dual" (the stochastic pendulum). */
+ * (Lotka–Volterra), "k_pend_forward_sde" / "k_pend_adjoint_dual" (the stochastic pendulum); the Kuramoto system runs the
+ * lane-per-direction kernels: "k_forward_dual_dir" / "k_adjoint_dual_dir". */
 const char* lde_last_kernel(const lde_handle* h, int which);
 
 

@@ -78,6 +78,7 @@ solver_code(::RK4)   = Int32(1)                                         # fixed 
 solver_code(::EM)        = Int32(2)                                     # LDE_SOLVER_EM          } `SPendulum` (rhs_kind 4) only, fixed step:
 solver_code(::EulerHeun) = Int32(3)                                     # LDE_SOLVER_EULER_HEUN  } dt = h through kwargs
 const LDE_RHS_SPENDULUM = Int32(4)
+const LDE_RHS_KURAMOTO = Int32(7)   # N phase oscillators, state_dim = N (2 … 7), param_dim = N + 1; LDE_SENSE_FORWARD_DUAL only (6 is no right-hand side)
 
 # one handle per `diffeq` struct, built lazily from its fields (solver, sensealg, kwargs...)  [REF GOKU.jl:105-108]. The analytic right-hand
 # sides are a closed menu (include/lde.h: lde_rhs_kind) and the example structs live outside the package

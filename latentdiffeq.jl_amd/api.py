@@ -10,6 +10,7 @@ include/lde.h. PyTorch is used only for device memory, streams and autograd plum
     Pendulum_friction(...)                    [REF pendulum.jl:50-91]  Pendulum_friction(...)
     SPendulum(; solver, sensalg, kwargs...)   [REF pendulum.jl:93-140] SPendulum(solver=EulerHeun(), sensalg=, dt=, seed=, **kwargs)
     (a plug-in struct of one's own: "any Julia function")              LotkaVolterra(solver=Tsit5(), **kwargs)  — LDE_RHS_LOTKA_VOLTERRA
+    (… with more than two states and transform_after_diffeq)           Kuramoto(N=3, solver=Tsit5(), **kwargs)  — LDE_RHS_KURAMOTO
     NODE(latent_dim_in; hidden_dim, augment_dim, kwargs...) [REF nODE.jl:3-32]   NODE(latent_dim_in, hidden_dim=, augment_dim=, **kwargs)
     GOKU_basic(), LatentODE()                 [REF GOKU.jl:6-7], [REF LatentODE.jl:6]   same
     Decoder(model_type, (latent_out, diffeq, reconstructor)) [REF LatentDiffEqModel.jl:79-99]   same
@@ -101,7 +102,7 @@ class ForwardDiffSensitivity(DiscreteSensitivity):
 
     `dual_norm=True` (opt-in; LDE_SENSE_FORWARD_DUAL): the solve on dual numbers as upstream runs it during training — the error norm sees
     the partials, so the accepted steps are the reference's training-time ones, not the primal solve's. The forward pass carries the
-    Jacobians ∂ẑ(t_j)/∂(ẑ₀, θ̂) and the pullback contracts them. Analytic right-hand sides (Pendulum, Pendulum_friction, LotkaVolterra) only."""
+    Jacobians ∂ẑ(t_j)/∂(ẑ₀, θ̂) and the pullback contracts them. Analytic right-hand sides (Pendulum, Pendulum_friction, LotkaVolterra, Kuramoto) only."""
 
     def __init__(self, exact: bool = True, dual_norm: bool = False):
         self.dual_norm = bool(dual_norm)
@@ -293,6 +294,35 @@ class LotkaVolterra(_PhysicsDiffEq):
             d = _make_desc(self._rhs_kind, 2, 4, 0, (), self.solver, self.sensealg, L.BATCH_PER_TRAJECTORY, self.kwargs)
             self._handle = _Handle(d)
         return self._handle
+
+
+class Kuramoto(_PhysicsDiffEq):
+    """N Kuramoto phase oscillators, dφ_i = ω_i + (K/N) Σ_j sin(φ_j − φ_i), p = (ω₁ … ω_N, K) — LDE_RHS_KURAMOTO (include/lde.h: "the
+    Kuramoto system"), 2 ≤ N ≤ 7. The first plug-in with more than two states: `prob.u0` has N entries and `prob.p` N + 1, so
+    `default_layers` builds an N-wide `lo_z₀` and an (N+1)-wide `lo_θ` (softplus: ω, K > 0); diffeq_layer takes ẑ₀ [N, B] and θ̂ [N+1, B]
+    and autograd returns gradients of those shapes.
+
+    `transform_after_diffeq` is the sine of the phases — what the reference keeps that hook for ("mainly used for Kuramoto-like systems"
+    [REF src/models/LatentODE.jl:74]): the reconstructor sees a 2π-periodic function of ẑ. Plain torch, so autograd carries it.
+
+    Served on the dual-number path only, like LotkaVolterra: `ForwardDiffSensitivity(dual_norm=True)` (LDE_SENSE_FORWARD_DUAL), Tsit5
+    adaptive or fixed-step and RK4 fixed-step; another sensealg is refused by the library, with its text ("… use LDE_SENSE_FORWARD_DUAL")."""
+    _rhs_kind = L.RHS_KURAMOTO
+
+    def __init__(self, N: int = 3, solver=None, sensalg=None, sensealg=None, **kwargs):
+        sa = sensealg if sensealg is not None else sensalg
+        super().__init__(solver=solver, sensealg=sa if sa is not None else ForwardDiffSensitivity(dual_norm=True), **kwargs)
+        self.N = int(N)
+        self.prob = _ODEProblemStub(np.ones(self.N, np.float32), np.ones(self.N + 1, np.float32), (0.0, 1.0))
+
+    def _native(self) -> _Handle:
+        if self._handle is None:
+            d = _make_desc(self._rhs_kind, self.N, self.N + 1, 0, (), self.solver, self.sensealg, L.BATCH_PER_TRAJECTORY, self.kwargs)
+            self._handle = _Handle(d)
+        return self._handle
+
+    def transform_after_diffeq(self, x):
+        return torch.sin(x)
 
 
 def _set_noise(handle: _Handle, nz):

@@ -19,11 +19,26 @@ using lde::KOpts;
 using lde::StepRec;
 using lde::DualRec;
 
+// ---- the lane-per-direction dual solve (csrc/lde_dual_dir.hip: k_forward_dual_dir / k_adjoint_dual_dir; LDE_RHS_KURAMOTO, N states and
+// NP = 2N + 1 partial directions q = (φ₀ (N), ω (N), K)): a trajectory is a group of G consecutive lanes, lane q of it carries the N values
+// and the ONE tangent column ∂φ/∂q_q. G = 8 holds NP ≤ 7 (N ≤ 3), G = 16 holds NP ≤ 15 (N ≤ 7): a group never leaves a 16-lane row, which
+// is what its cross-lane sums (DPP within a row) need. 0: N is not served.
+constexpr int KURAMOTO_MIN_N = 2, KURAMOTO_MAX_N = 7;
+static constexpr bool dir_state_ok(int N) { return N >= KURAMOTO_MIN_N && N <= KURAMOTO_MAX_N; }
+static constexpr int dir_partials(int N) { return dir_state_ok(N) ? 2 * N + 1 : 0; }
+static constexpr int dir_group_width(int N) { return !dir_state_ok(N) ? 0 : N <= 3 ? 8 : 16; }
+// lanes of a launch over B trajectories (0: none — B < 1 or N not served) and its workgroups, by the dual solve's batch rule
+// (pend_dual_mapping) applied to the LANES: a wave per workgroup up to 4 096 lanes, four waves beyond. A workgroup holds whole groups.
+static int64_t dir_lanes(int N, int B) { return B < 1 ? 0 : (int64_t)B * dir_group_width(N); }
+static int dir_block(int N, int B) { return dir_lanes(N, B) <= 4096 ? 64 : 256; }
+static int64_t dir_grid(int N, int B) { return (dir_lanes(N, B) + dir_block(N, B) - 1) / dir_block(N, B); }
+
 static bool has_mlp(const lde_problem_desc& d) {
   return d.rhs_kind == LDE_RHS_MLP || d.rhs_kind == LDE_RHS_PENDULUM_PLUS_MLP;
 }
 static bool is_lv(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_LOTKA_VOLTERRA; }
-static bool has_pend(const lde_problem_desc& d) { return d.rhs_kind != LDE_RHS_MLP && !is_lv(d); }
+static bool is_kuramoto(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_KURAMOTO; }
+static bool has_pend(const lde_problem_desc& d) { return d.rhs_kind != LDE_RHS_MLP && !is_lv(d) && !is_kuramoto(d); }
 static bool is_sde(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_SPENDULUM; }
 static bool sde_solver(int solver) { return solver == LDE_SOLVER_EM || solver == LDE_SOLVER_EULER_HEUN; }
 
@@ -34,12 +49,15 @@ static int validate(const lde_problem_desc* d, std::string* why) {
   };
   if (!d) return bad("desc is NULL");
   if (d->abi_version != LDE_ABI_VERSION) return bad("abi_version mismatch");
-  if (d->rhs_kind < 0 || d->rhs_kind > LDE_RHS_LOTKA_VOLTERRA) return bad("unknown rhs_kind");
+  // 6 is no right-hand side and stays refused: tests/lv_host_driver.cpp pins it as "unknown rhs_kind", so the Kuramoto system took 7
+  if (d->rhs_kind < 0 || d->rhs_kind > LDE_RHS_KURAMOTO || d->rhs_kind == 6) return bad("unknown rhs_kind");
   if (d->state_dim < 1 || d->param_dim < 0 || d->augment_dim < 0) return bad("bad dims");
   if (has_pend(*d) && (d->state_dim != 2 || d->param_dim != 1 || d->augment_dim != 0))
     return bad("pendulum RHS needs state_dim=2, param_dim=1, augment_dim=0");
   if (is_lv(*d) && (d->state_dim != 2 || d->param_dim != 4 || d->augment_dim != 0))
     return bad("LDE_RHS_LOTKA_VOLTERRA needs state_dim=2, param_dim=4, augment_dim=0");
+  if (is_kuramoto(*d) && (d->state_dim < KURAMOTO_MIN_N || d->state_dim > KURAMOTO_MAX_N || d->param_dim != d->state_dim + 1 || d->augment_dim != 0))
+    return bad("LDE_RHS_KURAMOTO needs state_dim=N with 2 <= N <= 7, param_dim=N+1, augment_dim=0");
   if (d->rhs_kind == LDE_RHS_MLP && d->param_dim != 0) return bad("MLP RHS takes no per-trajectory parameters");
   if (has_mlp(*d)) {
     if (d->n_layers < 1 || d->n_layers > LDE_MAX_LAYERS) return bad("n_layers out of range");
@@ -51,6 +69,7 @@ static int validate(const lde_problem_desc* d, std::string* why) {
   }
   if (is_sde(*d) && d->n_layers != 0) return bad("LDE_RHS_SPENDULUM is analytic: n_layers must be 0");
   if (is_lv(*d) && d->n_layers != 0) return bad("LDE_RHS_LOTKA_VOLTERRA is analytic: n_layers must be 0");
+  if (is_kuramoto(*d) && d->n_layers != 0) return bad("LDE_RHS_KURAMOTO is analytic: n_layers must be 0");
   if (d->solver != LDE_SOLVER_TSIT5 && d->solver != LDE_SOLVER_RK4 && !sde_solver(d->solver)) return bad("unknown solver");
   if (d->batching != LDE_BATCH_PER_TRAJECTORY && d->batching != LDE_BATCH_COUPLED && d->batching != LDE_BATCH_COUPLED_GLOBAL)
     return bad("unknown batching");
@@ -80,6 +99,12 @@ static int validate(const lde_problem_desc* d, std::string* why) {
     if (d->batching != LDE_BATCH_PER_TRAJECTORY) return unsupported("LDE_RHS_LOTKA_VOLTERRA: no coupled solve; LDE_BATCH_PER_TRAJECTORY only");
     if (d->sensealg != LDE_SENSE_FORWARD_DUAL)
       return unsupported("LDE_RHS_LOTKA_VOLTERRA: only the solve on dual numbers exists for this system (no discrete sweep, no continuous adjoint); use LDE_SENSE_FORWARD_DUAL");
+  }
+  // the Kuramoto system likewise: its kernels (csrc/lde_dual_dir.hip) are the dual-number solve with a lane per partial direction
+  if (is_kuramoto(*d)) {
+    if (d->batching != LDE_BATCH_PER_TRAJECTORY) return unsupported("LDE_RHS_KURAMOTO: no coupled solve; LDE_BATCH_PER_TRAJECTORY only");
+    if (d->sensealg != LDE_SENSE_FORWARD_DUAL)
+      return unsupported("LDE_RHS_KURAMOTO: only the solve on dual numbers exists for this system (no discrete sweep, no continuous adjoint); use LDE_SENSE_FORWARD_DUAL");
   }
   if (d->solver == LDE_SOLVER_RK4 && d->adaptive) {
     if (why) *why = "RK4 is fixed-step only here: pass adaptive=0, dt=h";
@@ -132,7 +157,13 @@ static StepRec rec_view(const lde_problem_desc& d, void* base, int B, int cap, b
 // LDE_SENSE_FORWARD_DUAL's record (include/lde.h: "the dual record"): n [B] | J [T][2][NP][B] f32 | with the step trace t, dt [cap][B] f64;
 // `np` = NP = D + P partials per component — 3 for the pendulums (the four-argument forms), 6 for Lotka–Volterra (dual_partials).
 // J first: its place depends on B alone, so the pullback (which reads n and J) finds it whether or not the forward traced its steps.
-static int dual_partials(const lde_problem_desc& d) { return is_lv(d) ? 6 : 3; }
+// The Kuramoto system's record is its own (include/lde.h: "the Kuramoto system"): n [B] | J [T][N][B][G] f32 | t, dt — a trajectory's G
+// lanes (dir_group_width) fastest, so N·G floats per (save time, trajectory) where the two-state systems have 2·NP; `np` is then N·G/2 (G is
+// even), and every size and offset below serves this kind unchanged.
+static int dual_partials(const lde_problem_desc& d) {
+  if (is_kuramoto(d)) return dir_state_ok(d.state_dim) ? d.state_dim * dir_group_width(d.state_dim) / 2 : 0;
+  return is_lv(d) ? 6 : 3;
+}
 static size_t dual_rec_bytes(int B, int T, int cap, bool trace, int np) {
   return align256((size_t)B * 4) + align256((size_t)T * 2 * np * B * 4) + (trace ? 2 * align256((size_t)cap * B * 8) : 0);
 }
@@ -275,6 +306,26 @@ static int lv_dispatch(int solver, bool adaptive, F&& f) {
   if (solver == LDE_SOLVER_TSIT5) return f(std::integral_constant<int, LDE_SOLVER_TSIT5>{});
   if (solver == LDE_SOLVER_RK4 && !adaptive) return f(std::integral_constant<int, LDE_SOLVER_RK4>{});
   return LDE_ERR_UNSUPPORTED;
+}
+
+// The template arguments of k_forward_dual_dir (csrc/lde_dual_dir.hip): calls f(N, SOLVER) with std::integral_constants for N = 2 … 7 and
+// the three (solver, adaptive) combinations of lv_dispatch — what validate() admits for LDE_RHS_KURAMOTO — and returns what f returns;
+// anything else is LDE_ERR_UNSUPPORTED. dir_dispatch_n alone serves the pullback, which has no solver.
+template <class F>
+static int dir_dispatch_n(int N, F&& f) {
+  switch (N) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    default: return LDE_ERR_UNSUPPORTED;
+  }
+}
+template <class F>
+static int dir_dispatch(int N, int solver, bool adaptive, F&& f) {
+  return dir_dispatch_n(N, [&](auto n) -> int { return lv_dispatch(solver, adaptive, [&](auto S) -> int { return f(n, S); }); });
 }
 
 // Which mapping serves a solve under LDE_SENSE_FORWARD_DUAL (csrc/lde_dual.h: dual_block switches on this, for every system and for the
