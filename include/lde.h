@@ -61,6 +61,10 @@ enum lde_rhs_kind {
                                      [REF src/models/LatentODE.jl:74]. LDE_SENSE_FORWARD_DUAL only; see "the Kuramoto system" below.
                                      7, not 6: the value 6 is no right-hand side and stays refused as "unknown rhs_kind" (a test of the
                                      Lotka–Volterra host logic pins that refusal) */
+  LDE_RHS_DOUBLE_PENDULUM   = 9,  /* the double pendulum: z = (θ₁, θ₂, ω₁, ω₂), θ = (L₁, L₂, m₁, m₂) per trajectory (state_dim 4, param_dim 4),
+                                     g = 10 — the GOKU-net paper's second benchmark. LDE_SENSE_FORWARD_DUAL only; see "the double pendulum"
+                                     below. 9, not 8: the value 8, like 6, is no right-hand side and stays refused as "unknown rhs_kind"
+                                     (the tests of the Lotka–Volterra and Kuramoto host logic pin both refusals) */
   LDE_RHS_LOTKA_VOLTERRA    = 5   /* Lotka–Volterra: dx = αx − βxy, dy = −γy + δxy, θ = (α, β, γ, δ) = p[1:4] per trajectory (state_dim 2,
                                      param_dim 4). The first right-hand side with more than one parameter — the reference's `diffeq` plug-in is
                                      "any Julia function" [REF src/models/GOKU.jl:98-130]; this one has no file of its own there.
@@ -297,6 +301,32 @@ int lde_set_noise(lde_handle* h, uint64_t seed, uint64_t offset, uint64_t first_
  * semantics (NaN ẑ block, zero J, n = −retcode, zero gradient) and statistics are those of the pendulum's dual solve. lde_last_kernel:
  * "k_forward_dual_dir" / "k_adjoint_dual_dir". */
 
+/* ---- the double pendulum (LDE_RHS_DOUBLE_PENDULUM = 9): z = (θ₁, θ₂, ω₁, ω₂), θ = (L₁, L₂, m₁, m₂), g = 10 (the pendulums' G) ----
+ * With Δ = θ₁ − θ₂ and den = 2m₁ + m₂ − m₂ cos 2Δ:
+ *     θ₁' = ω₁,  θ₂' = ω₂
+ *     ω₁' = [ −g(2m₁+m₂) sin θ₁ − m₂ g sin(θ₁−2θ₂) − 2 sinΔ · m₂ (ω₂² L₂ + ω₁² L₁ cosΔ) ] / (L₁ · den)
+ *     ω₂' = [ 2 sinΔ ( ω₁² L₁ (m₁+m₂) + g (m₁+m₂) cos θ₁ + ω₂² L₂ m₂ cosΔ ) ] / (L₂ · den)
+ * z0, dz0 [4×B] — trajectory b's values at z0[4·b … 4·b + 3] — z_out, dz_out [T×B×4]; theta, dtheta [4×B], trajectory b's (L₁, L₂, m₁, m₂)
+ * at theta[4·b … 4·b + 3]. The right-hand side is homogeneous of degree 0 in (m₁, m₂) — m₁·∂ẑ/∂m₁ + m₂·∂ẑ/∂m₂ = 0 — and with m₂ = 0 its
+ * (θ₁, ω₁) is LDE_RHS_PENDULUM with L = L₁. Two hardware sine / cosine pairs per evaluation, on θ₁ and θ₂, each angle's whole turns anchored
+ * once per step attempt; sin Δ, cos Δ, cos 2Δ and sin(θ₁ − 2θ₂) follow from those four numbers by the angle-sum identities, so angles beyond
+ * 256 turns keep their dynamics.
+ * Served: state_dim = 4, param_dim = 4, augment_dim = 0, n_layers = 0 (anything else: LDE_ERR_INVALID_ARG), LDE_BATCH_PER_TRAJECTORY,
+ * LDE_SOLVER_TSIT5 adaptive or fixed-step and LDE_SOLVER_RK4 fixed-step, sensealg LDE_SENSE_FORWARD_DUAL: NP = 8 partials per component in the
+ * order (θ₁₀, θ₂₀, ω₁₀, ω₂₀, L₁, L₂, m₁, m₂), all of them in every norm of the step control, the RMS over the four components.
+ * lde_num_weights = 0; dW must be NULL. The enum value is 9: rhs_kind = 6 and 8 are no right-hand sides ("unknown rhs_kind").
+ * Refused with LDE_ERR_UNSUPPORTED, lde_desc_error naming the missing piece: another sensealg ("… use LDE_SENSE_FORWARD_DUAL"),
+ * LDE_BATCH_COUPLED, the stochastic steppers and adaptive RK4 (their own texts); lde_set_noise on such a handle.
+ * The kernels are the Kuramoto system's, a lane per partial direction: one group of G = 8 lanes per trajectory with no pad lane. The dual
+ * record (A(x) = x rounded up to a multiple of 256 bytes):
+ *     n  int32 [B]                at 0                      as below
+ *     J  float [T][4][B][8]       at A(4B)                  J[j][i][b][q] = ∂ẑ_i(t_j)/∂q_q of trajectory b, q fastest: element
+ *                                                           ((j·4 + i)·B + b)·8 + q; q = 0 … 3: ẑ₀, 4 … 7: L₁, L₂, m₁, m₂
+ *     t, dt double [cap][B]       at A(4B) + A(128·TB)      option "step_trace" = 1 only, as below
+ * served by lde_step_record_bytes, lde_set_step_record, lde_reserve, lde_step_record_status and lde_get_step_record as the other dual
+ * records are. Failure semantics (NaN ẑ block, zero J, n = −retcode, zero gradient) and statistics are those of the pendulum's dual solve.
+ * lde_last_kernel: "k_forward_dual_dir" / "k_adjoint_dual_dir" (labels of the path, shared with the Kuramoto system). */
+
 /* Pre-size the handle's workspace for batches up to B and T save points (so that later
  * lde_forward/lde_adjoint calls allocate nothing and can be captured in a hipGraph). */
 int lde_reserve(lde_handle* h, int B, int T);
@@ -382,7 +412,7 @@ int lde_set_global_sum_peers(lde_handle* h, int rank, int nranks, void* const* m
  *                                                           LDE_RHS_LOTKA_VOLTERRA
  *     t  double [cap][B]          at A(4B) + A(4·2·NP·TB)   option "step_trace" = 1 only: start time of accepted step s of trajectory b at s·B + b
  *     dt double [cap][B]          at … + A(8·cap·B)         … and its size; cap = lde_step_record_capacity(h, T)
- * (Pendulums: J [T][2][3][B], the trace at A(4B) + A(24TB), as before. LDE_RHS_KURAMOTO: J [T][N][B][G], "the Kuramoto system" above.) J of a failed trajectory is zero. With "step_trace" = 1 lde_get_step_record(h, 0, …) returns the accepted steps (what a checker replays). */
+ * (Pendulums: J [T][2][3][B], the trace at A(4B) + A(24TB), as before. LDE_RHS_KURAMOTO: J [T][N][B][G], "the Kuramoto system" above; LDE_RHS_DOUBLE_PENDULUM: J [T][4][B][8], "the double pendulum" above.) J of a failed trajectory is zero. With "step_trace" = 1 lde_get_step_record(h, 0, …) returns the accepted steps (what a checker replays). */
 int64_t lde_step_record_bytes(const lde_handle* h, int B, int T);
 int lde_set_step_record(lde_handle* h, void* rec_dev, int64_t bytes);
 /* Did the record hold the solve? lde_step_record_capacity(h, T) = the accepted steps per sequence a record made now would hold;

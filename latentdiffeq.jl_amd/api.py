@@ -11,6 +11,7 @@ include/lde.h. PyTorch is used only for device memory, streams and autograd plum
     SPendulum(; solver, sensalg, kwargs...)   [REF pendulum.jl:93-140] SPendulum(solver=EulerHeun(), sensalg=, dt=, seed=, **kwargs)
     (a plug-in struct of one's own: "any Julia function")              LotkaVolterra(solver=Tsit5(), **kwargs)  — LDE_RHS_LOTKA_VOLTERRA
     (… with more than two states and transform_after_diffeq)           Kuramoto(N=3, solver=Tsit5(), **kwargs)  — LDE_RHS_KURAMOTO
+    (… the GOKU-net paper's second benchmark: four states, four parameters)  DoublePendulum(solver=Tsit5(), **kwargs)  — LDE_RHS_DOUBLE_PENDULUM
     NODE(latent_dim_in; hidden_dim, augment_dim, kwargs...) [REF nODE.jl:3-32]   NODE(latent_dim_in, hidden_dim=, augment_dim=, **kwargs)
     GOKU_basic(), LatentODE()                 [REF GOKU.jl:6-7], [REF LatentODE.jl:6]   same
     Decoder(model_type, (latent_out, diffeq, reconstructor)) [REF LatentDiffEqModel.jl:79-99]   same
@@ -102,7 +103,7 @@ class ForwardDiffSensitivity(DiscreteSensitivity):
 
     `dual_norm=True` (opt-in; LDE_SENSE_FORWARD_DUAL): the solve on dual numbers as upstream runs it during training — the error norm sees
     the partials, so the accepted steps are the reference's training-time ones, not the primal solve's. The forward pass carries the
-    Jacobians ∂ẑ(t_j)/∂(ẑ₀, θ̂) and the pullback contracts them. Analytic right-hand sides (Pendulum, Pendulum_friction, LotkaVolterra, Kuramoto) only."""
+    Jacobians ∂ẑ(t_j)/∂(ẑ₀, θ̂) and the pullback contracts them. Analytic right-hand sides (Pendulum, Pendulum_friction, LotkaVolterra, Kuramoto, DoublePendulum) only."""
 
     def __init__(self, exact: bool = True, dual_norm: bool = False):
         self.dual_norm = bool(dual_norm)
@@ -323,6 +324,29 @@ class Kuramoto(_PhysicsDiffEq):
 
     def transform_after_diffeq(self, x):
         return torch.sin(x)
+
+
+class DoublePendulum(_PhysicsDiffEq):
+    """The double pendulum, z = (θ₁, θ₂, ω₁, ω₂), p = (L₁, L₂, m₁, m₂), g = 10 — LDE_RHS_DOUBLE_PENDULUM (include/lde.h: "the double
+    pendulum"), the GOKU-net paper's second benchmark. `prob.u0` and `prob.p` have four entries each, so `default_layers` builds a four-wide
+    `lo_z₀` and a four-wide `lo_θ` (softplus: lengths and masses > 0); diffeq_layer takes ẑ₀ [4, B] and θ̂ [4, B] and autograd returns
+    gradients of those shapes. `transform_after_diffeq` is the identity.
+
+    Served on the dual-number path only, like Kuramoto, on its lane-per-direction kernels: `ForwardDiffSensitivity(dual_norm=True)`
+    (LDE_SENSE_FORWARD_DUAL), Tsit5 adaptive or fixed-step and RK4 fixed-step; another sensealg is refused by the library, with its text
+    ("… use LDE_SENSE_FORWARD_DUAL")."""
+    _rhs_kind = L.RHS_DOUBLE_PENDULUM
+
+    def __init__(self, solver=None, sensalg=None, sensealg=None, **kwargs):
+        sa = sensealg if sensealg is not None else sensalg
+        super().__init__(solver=solver, sensealg=sa if sa is not None else ForwardDiffSensitivity(dual_norm=True), **kwargs)
+        self.prob = _ODEProblemStub(np.ones(4, np.float32), np.ones(4, np.float32), (0.0, 1.0))
+
+    def _native(self) -> _Handle:
+        if self._handle is None:
+            d = _make_desc(self._rhs_kind, 4, 4, 0, (), self.solver, self.sensealg, L.BATCH_PER_TRAJECTORY, self.kwargs)
+            self._handle = _Handle(d)
+        return self._handle
 
 
 def _set_noise(handle: _Handle, nz):

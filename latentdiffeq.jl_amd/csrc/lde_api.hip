@@ -32,10 +32,11 @@ int launch_forward_dual(int kind, int solver, const float* z0, const float* thet
                         float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
 int launch_adjoint_dual(int kind, const DualRec& rec, const float* dz_out, int T, int B, float* dz0, float* dtheta, int32_t* nfe,
                         int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
-int launch_forward_dual_dir(int N, int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o, const DualRec& rec,
-                            float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
-int launch_adjoint_dual_dir(int N, const DualRec& rec, const float* dz_out, int T, int B, float* dz0, float* dtheta, int32_t* nfe,
-                            int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
+int launch_forward_dual_dir(const lde_problem_desc& d, const float* z0, const float* theta, const double* ts_dev, const KOpts& o,
+                            const DualRec& rec, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret,
+                            hipStream_t stream);
+int launch_adjoint_dual_dir(const lde_problem_desc& d, const DualRec& rec, const float* dz_out, int T, int B, float* dz0, float* dtheta,
+                            int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
 int launch_pend_forward_sde(int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o, const DualRec& rec,
                             const SdeNoise& nz, bool over, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej,
                             int32_t* ret, hipStream_t stream);
@@ -99,7 +100,7 @@ struct lde_handle {
   std::string err = "";
 };
 
-using namespace lde_host;   // validate, has_mlp, has_pend, is_sde, is_lv, is_kuramoto, dual_partials, sde_plan, rec_nseq, rec_capacity, rec_bytes, rec_view, align256, make_opts, num_weights, grid_ok, fixed_step_count
+using namespace lde_host;   // validate, has_mlp, has_pend, is_sde, is_lv, is_kuramoto, is_dpend, is_dir, dual_partials, sde_plan, rec_nseq, rec_capacity, rec_bytes, rec_view, align256, make_opts, num_weights, grid_ok, fixed_step_count
 static int rec_capacity(const lde_handle* h, int T, int which);
 
 #define HIP_TRY(h, expr)                                                                   \
@@ -422,8 +423,8 @@ int lde_forward(lde_handle* h, const float* z0, const float* theta, const double
       rc = lde::launch_pend_forward_sde(h->d.solver, z0, theta, h->ts_dev, o, r, h->noise, sde_plan(h->d, ts, T).over, z_out, retcode, st[0],
                                         st[1], st[2], st[3], stream);
       h->last_kernel[0] = "k_pend_forward_sde";
-    } else if (is_kuramoto(h->d)) {   // the Kuramoto system: a lane per (trajectory, partial direction) (csrc/lde_dual_dir.hip)
-      rc = lde::launch_forward_dual_dir(h->d.state_dim, h->d.solver, z0, theta, h->ts_dev, o, r, z_out, retcode, st[0], st[1], st[2], st[3], stream);
+    } else if (is_dir(h->d)) {   // Kuramoto and the double pendulum: a lane per (trajectory, partial direction) (csrc/lde_dual_dir.hip)
+      rc = lde::launch_forward_dual_dir(h->d, z0, theta, h->ts_dev, o, r, z_out, retcode, st[0], st[1], st[2], st[3], stream);
       h->last_kernel[0] = "k_forward_dual_dir";
     } else {              // the pendulums and Lotka–Volterra: one kernel over the system (csrc/lde_dual.hip)
       rc = lde::launch_forward_dual(h->d.rhs_kind, h->d.solver, z0, theta, h->ts_dev, o, r, z_out, retcode, st[0], st[1], st[2], st[3], stream);
@@ -490,8 +491,8 @@ int lde_adjoint(lde_handle* h, const float* z_out, const float* theta, const dou
       }
       r = h->dual_last;
     }
-    if (is_kuramoto(h->d)) {
-      rc = lde::launch_adjoint_dual_dir(h->d.state_dim, r, dz_out, T, B, dz0, dtheta, st[0], st[1], st[2], st[3], stream);
+    if (is_dir(h->d)) {
+      rc = lde::launch_adjoint_dual_dir(h->d, r, dz_out, T, B, dz0, dtheta, st[0], st[1], st[2], st[3], stream);
       h->last_kernel[1] = "k_adjoint_dual_dir";
     } else {
       rc = lde::launch_adjoint_dual(h->d.rhs_kind, r, dz_out, T, B, dz0, dtheta, st[0], st[1], st[2], st[3], stream);

@@ -1,16 +1,20 @@
 // lde_dual_dir.hip — LDE_SENSE_FORWARD_DUAL with ONE LANE PER (TRAJECTORY, PARTIAL DIRECTION): the dual-number solve for systems of more than
-// two states (LDE_RHS_KURAMOTO, N = 2 … 7 phase oscillators: csrc/lde_kuramoto_dualrhs.h).
+// two states, as kernels over a system: LDE_RHS_KURAMOTO (N = 2 … 7 phase oscillators: csrc/lde_kuramoto_dualrhs.h, KuramotoDir<N>) and
+// LDE_RHS_DOUBLE_PENDULUM (four states, four parameters: csrc/lde_dpend_dualrhs.h, DoublePendDir).
 //
 // k_forward_dual (csrc/lde_dual.hip) keeps a trajectory's whole dual state, D·(1 + D + P) floats, and Tsit5's seven slopes of it in one lane:
 // 14 floats per vector for Lotka–Volterra, 112 for seven oscillators — it cannot grow in D. Here a trajectory is a GROUP of G consecutive
-// lanes (lde_host::dir_group_width: 8 for N ≤ 3, 16 for N ≤ 7 — a group never leaves a 16-lane row) and lane q of the group carries
-//   * the N values φ — redundant: every lane of the group computes the same bits from the same inputs by the same instructions —
-//   * and ONE tangent column v = ∂φ/∂q_q, q = (φ₀ (N), ω (N), K),
-// 2N floats per vector, ≈ 12 vectors live. Lanes q ≥ NP = 2N + 1 are pad lanes: zero seed, zero forcing, so their tangent stays 0, adds 0
-// to every norm, and they need no branch. The stage sums, the solution weights and the interpolant are lde_device.h's on the 2N-vector
-// (tsit5_attempt / rk4_step / tsit5_dense_*), as k_forward_dual uses them on its DN-vector; the loop around them is k_forward_dual's.
+// lanes (SYS::G: 8 or 16 — a group never leaves a 16-lane row; lde_host::dir_group_width is the host's copy of the rule) and lane q of the
+// group carries
+//   * the D values z — redundant: every lane of the group computes the same bits from the same inputs by the same instructions —
+//   * and ONE tangent column v = ∂z/∂q_q, q = (ẑ₀ (D), θ (NP − D)),
+// 2D floats per vector, ≈ 12 vectors live. Lanes q ≥ NP are pad lanes (Kuramoto: G − 2N − 1 of them; the double pendulum: none): zero seed,
+// zero forcing, so their tangent stays 0, adds 0 to every norm, and they need no branch. The stage sums, the solution weights and the
+// interpolant are lde_device.h's on the 2D-vector (tsit5_attempt / rk4_step / tsit5_dense_*), as k_forward_dual uses them on its DN-vector;
+// the loop around them is k_forward_dual's. What a system supplies: D, NP ≤ G, G, DN = 2·D, load(theta, b, q), seed(z0, b, q, y),
+// anchor(y) (once per step attempt: the whole turns of its angles) and operator()(u, du).
 //
-// Step control is csrc/lde_dual.h's, from 2 to N components: ‖u_i‖ = sqrt(v_i² + Σ_q p_iq²), scale abstol + reltol·max(‖y_i‖, ‖y_new,i‖),
+// Step control is csrc/lde_dual.h's, from 2 to D components: ‖u_i‖ = sqrt(v_i² + Σ_q p_iq²), scale abstol + reltol·max(‖y_i‖, ‖y_new,i‖),
 // EEst the RMS over i of ‖e_i‖ / scale_i — ratios and squares in f32, the sum over i and the root in f64 — and the Hairer initial step on
 // the same norms. Σ_q runs ACROSS the lanes of a group, and every lane of a group must hold the same bits of it: EEst, the accept decision
 // and dt follow from it, and lanes that disagreed would walk different step sequences. The sum is a BUTTERFLY over the group (group_sum):
@@ -21,17 +25,18 @@
 // a group, so a lane's partners are always active; a group whose trajectory is past the batch leaves as a whole, after dual_stage_ts's
 // barrier. Groups of one wave do take different numbers of steps: that is divergence between groups, never inside one.
 //
-// The dual record of this kind (lde_types.h: DualRec; include/lde.h: "the Kuramoto system") is n [B] | J [T][N][B][G]: element (j, i, b, q)
-// = ∂ẑ_i(t_j)/∂q_q at ((j·N + i)·B + b)·G + q — a wave's 64 lanes write 64 consecutive floats per (save time, component), and the pullback
-// reads them the same way (the trajectory-fastest layout of the two-state kernels would put neighbouring lanes B floats apart). Pad lanes
-// write their zeros. ẑ goes to z_out [T×B×N] from the group's first lane, which also writes the step trace, the return code and the
-// statistics (dual_finish). Failed solve: NaN block in ẑ, zero J, rec.n[b] = −retcode [REF GOKU.jl:114].
-// k_adjoint_dual_dir<N>: lane (b, q) forms g_q = Σ_j Σ_i J_j[i][q]·dz_out_j[i], j outer, i inner, in f32 (the checkers' order); lanes q < N
-// write dz0 [B×N], lanes N ≤ q < NP write dθ [B×(N+1)], pad lanes nothing.
+// The dual record of this kind (lde_types.h: DualRec; include/lde.h: "the Kuramoto system", "the double pendulum") is n [B] | J [T][D][B][G]:
+// element (j, i, b, q) = ∂ẑ_i(t_j)/∂q_q at ((j·D + i)·B + b)·G + q — a wave's 64 lanes write 64 consecutive floats per (save time,
+// component), and the pullback reads them the same way (the trajectory-fastest layout of the two-state kernels would put neighbouring lanes
+// B floats apart). Pad lanes write their zeros. ẑ goes to z_out [T×B×D] from the group's first lane, which also writes the step trace, the
+// return code and the statistics (dual_finish). Failed solve: NaN block in ẑ, zero J, rec.n[b] = −retcode [REF GOKU.jl:114].
+// k_adjoint_dual_dir<D, NP, G>: lane (b, q) forms g_q = Σ_j Σ_i J_j[i][q]·dz_out_j[i], j outer, i inner, in f32 (the checkers' order); lanes
+// q < D write dz0 [B×D], lanes D ≤ q < NP write dθ [B×(NP−D)], pad lanes nothing.
 #include "lde_device.h"
 #include "lde_dual.h"
 #include "lde_host.h"
 #include "lde_kuramoto_dualrhs.h"
+#include "lde_dpend_dualrhs.h"
 
 namespace lde {
 
@@ -52,44 +57,44 @@ __device__ __forceinline__ float group_sum(float x) {
   return x;
 }
 
-// ‖u_i‖ of every component, the same bits on every lane of the group: sqrt(v_i² + Σ_q p_iq²), this lane's p_i = u[N + i]
-template <int N, int G>
-__device__ __forceinline__ void dir_abs(const float (&u)[2 * N], float (&nrm)[N]) {
+// ‖u_i‖ of every component, the same bits on every lane of the group: sqrt(v_i² + Σ_q p_iq²), this lane's p_i = u[D + i]
+template <int D, int G>
+__device__ __forceinline__ void dir_abs(const float (&u)[2 * D], float (&nrm)[D]) {
 #pragma clang fp contract(off)
 #pragma unroll
-  for (int i = 0; i < N; i++) {
-    const float p2 = group_sum<G>(u[N + i] * u[N + i]);
+  for (int i = 0; i < D; i++) {
+    const float p2 = group_sum<G>(u[D + i] * u[D + i]);
     nrm[i] = sqrtf(u[i] * u[i] + p2);
   }
 }
 
-// RMS over the N components of ‖e_i‖ / sk_i: each ratio and its square in f32, the sum of squares and the root in f64 (lde_dual.h: dual_rms)
-template <int N>
-__device__ __forceinline__ double dir_rms(const float (&ne)[N], const float (&sk)[N]) {
+// RMS over the D components of ‖e_i‖ / sk_i: each ratio and its square in f32, the sum of squares and the root in f64 (lde_dual.h: dual_rms)
+template <int D>
+__device__ __forceinline__ double dir_rms(const float (&ne)[D], const float (&sk)[D]) {
 #pragma clang fp contract(off)
   double s2 = 0.0;
 #pragma unroll
-  for (int i = 0; i < N; i++) {
+  for (int i = 0; i < D; i++) {
     const float r = ne[i] / sk[i];
     s2 += (double)(r * r);
   }
-  return sqrt(s2 / (double)N);
+  return sqrt(s2 / (double)D);
 }
 
 // Hairer–Nørsett–Wanner initial step with every norm the dual norm; f0 = f(y0) given (lde_dual.h: dual_init_dt)
-template <int N, int G, class F>
-__device__ __forceinline__ double dir_init_dt(F& f, const float (&y)[2 * N], const float (&f0)[2 * N], double dtmax, const KOpts& o) {
-  constexpr int DN = 2 * N;
-  float sk[N], nn[N];
-  dir_abs<N, G>(y, nn);
+template <int D, int G, class F>
+__device__ __forceinline__ double dir_init_dt(F& f, const float (&y)[2 * D], const float (&f0)[2 * D], double dtmax, const KOpts& o) {
+  constexpr int DN = 2 * D;
+  float sk[D], nn[D];
+  dir_abs<D, G>(y, nn);
   {
 #pragma clang fp contract(off)
 #pragma unroll
-    for (int i = 0; i < N; i++) sk[i] = o.abstol + nn[i] * o.reltol;
+    for (int i = 0; i < D; i++) sk[i] = o.abstol + nn[i] * o.reltol;
   }
-  const double d0 = dir_rms<N>(nn, sk);
-  dir_abs<N, G>(f0, nn);
-  const double d1 = dir_rms<N>(nn, sk);
+  const double d0 = dir_rms<D>(nn, sk);
+  dir_abs<D, G>(f0, nn);
+  const double d1 = dir_rms<D>(nn, sk);
   double dt0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
   if (dt0 > dtmax) dt0 = dtmax;
   const float h = (float)dt0;
@@ -99,17 +104,17 @@ __device__ __forceinline__ double dir_init_dt(F& f, const float (&y)[2 * N], con
   f(tmp, f1);
 #pragma unroll
   for (int c = 0; c < DN; c++) f1[c] -= f0[c];
-  dir_abs<N, G>(f1, nn);
-  const double d2 = dir_rms<N>(nn, sk) / dt0, dm = d1 > d2 ? d1 : d2;
+  dir_abs<D, G>(f1, nn);
+  const double d2 = dir_rms<D>(nn, sk) / dt0, dm = d1 > d2 ? d1 : d2;
   const double dt1 = (dm <= 1e-15) ? fmax(1e-6, dt0 * 1e-3) : pow(10.0, -(2.0 + log10(dm)) / 5.0);
   const double dt = fmin(100.0 * dt0, dt1);
   return dt > dtmax ? dtmax : dt;
 }
 
 // EEst of a Tsit5 attempt: e = h·Σ_j b̃_j k_j per entry, scale abstol + reltol·max(‖y_i‖, ‖y_new,i‖), RMS of ‖e_i‖ / scale (lde_dual.h: dual_eest)
-template <int N, int G>
-__device__ __forceinline__ float dir_eest(float h, const float (&y)[2 * N], const float (&yn)[2 * N], const float (&k)[7][2 * N], const KOpts& o) {
-  constexpr int DN = 2 * N;
+template <int D, int G>
+__device__ __forceinline__ float dir_eest(float h, const float (&y)[2 * D], const float (&yn)[2 * D], const float (&k)[7][2 * D], const KOpts& o) {
+  constexpr int DN = 2 * D;
   float e[DN];
 #pragma unroll
   for (int c = 0; c < DN; c++) {
@@ -118,40 +123,41 @@ __device__ __forceinline__ float dir_eest(float h, const float (&y)[2 * N], cons
     for (int j = 1; j < 7; j++) a += ts5::BT[j] * k[j][c];
     e[c] = a * h;
   }
-  float sk[N], na[N], nb[N];
-  dir_abs<N, G>(y, na);
-  dir_abs<N, G>(yn, nb);
+  float sk[D], na[D], nb[D];
+  dir_abs<D, G>(y, na);
+  dir_abs<D, G>(yn, nb);
   {
 #pragma clang fp contract(off)
 #pragma unroll
-    for (int i = 0; i < N; i++) sk[i] = o.abstol + fmaxf(na[i], nb[i]) * o.reltol;
+    for (int i = 0; i < D; i++) sk[i] = o.abstol + fmaxf(na[i], nb[i]) * o.reltol;
   }
-  dir_abs<N, G>(e, na);
-  return (float)dir_rms<N>(na, sk);
+  dir_abs<D, G>(e, na);
+  return (float)dir_rms<D>(na, sk);
 }
 
-// ẑ_j from the group's first lane, this lane's column of J_j: J [T][N][B][G]
-template <int N, int G>
-__device__ __forceinline__ void dir_save(float* z_out, const DualRec& rec, int j, int B, long long b, int q, const float (&u)[2 * N]) {
+// ẑ_j from the group's first lane, this lane's column of J_j: J [T][D][B][G]
+template <int D, int G>
+__device__ __forceinline__ void dir_save(float* z_out, const DualRec& rec, int j, int B, long long b, int q, const float (&u)[2 * D]) {
   if (q == 0) {
-    float* zj = z_out + ((size_t)j * B + b) * N;
+    float* zj = z_out + ((size_t)j * B + b) * D;
 #pragma unroll
-    for (int i = 0; i < N; i++) zj[i] = u[i];
+    for (int i = 0; i < D; i++) zj[i] = u[i];
   }
-  float* Jj = rec.J + ((size_t)j * N * B + b) * G + q;
+  float* Jj = rec.J + ((size_t)j * D * B + b) * G + q;
 #pragma unroll
-  for (int i = 0; i < N; i++) Jj[(size_t)i * B * G] = u[N + i];
+  for (int i = 0; i < D; i++) Jj[(size_t)i * B * G] = u[D + i];
 }
 
-template <int N, int SOLVER, bool TS_LDS>
+// SYS (csrc/lde_kuramoto_dualrhs.h: KuramotoDir<N>; csrc/lde_dpend_dualrhs.h: DoublePendDir) supplies D components, NP ≤ G directions, the
+// group width G (8 or 16), DN = 2·D, load(theta, b, q), seed(z0, b, q, y), anchor(y) and operator()(u, du).
+template <class SYS, int SOLVER, bool TS_LDS>
 __global__ void __launch_bounds__(256) k_forward_dual_dir(const float* __restrict__ z0, const float* __restrict__ theta,
                                                           const double* __restrict__ ts_g, KOpts o, DualRec rec, float* __restrict__ z_out,
                                                           int32_t* __restrict__ retcode, int32_t* __restrict__ st_nfe,
                                                           int32_t* __restrict__ st_nacc, int32_t* __restrict__ st_nrej,
                                                           int32_t* __restrict__ st_ret) {
-  using SYS = KuramotoDir<N>;
-  constexpr int DN = 2 * N, G = lde_host::dir_group_width(N);
-  static_assert(SYS::NP <= G && 64 % G == 0, "a trajectory's directions fit its group, and groups tile a wave");
+  constexpr int D = SYS::D, DN = SYS::DN, G = SYS::G;
+  static_assert(DN == 2 * D && SYS::NP <= G && (G == 8 || G == 16), "a trajectory's directions fit its group, and groups tile a 16-lane row");
   const int T = o.T, B = o.B;
   dual_stage_ts<TS_LDS>(ts_g, T);
   auto s_ts = [&](int i) -> double { return dual_ts<TS_LDS>(ts_g, i); };
@@ -164,7 +170,7 @@ __global__ void __launch_bounds__(256) k_forward_dual_dir(const float* __restric
   float y[DN];
   SYS::seed(z0, b, q, y);
   float k[7][DN], yn[DN];
-  dir_save<N, G>(z_out, rec, 0, B, b, q, y);   // ts[0] is saved as ẑ₀ itself
+  dir_save<D, G>(z_out, rec, 0, B, b, q, y);   // ts[0] is saved as ẑ₀ itself
   int ret = LDE_RET_SUCCESS, nfe = 0, nacc = 0, nrej = 0;
 
   if (T > 1) {
@@ -177,7 +183,7 @@ __global__ void __launch_bounds__(256) k_forward_dual_dir(const float* __restric
     if (!o.adaptive) dt = o.dt_fixed;
     else if (o.dt_fixed > 0) dt = fmin(o.dt_fixed, dtmax);
     else {
-      dt = dir_init_dt<N, G>(f, y, k[0], dtmax, o);
+      dt = dir_init_dt<D, G>(f, y, k[0], dtmax, o);
       nfe++;
     }
     float qold = 1e-4f;
@@ -194,7 +200,7 @@ __global__ void __launch_bounds__(256) k_forward_dual_dir(const float* __restric
       f.anchor(y);
       if (SOLVER == LDE_SOLVER_TSIT5) {
         tsit5_attempt<DN, SYS, false, 0>(f, h, y, k, yn, o);
-        if (o.adaptive) EEst = dir_eest<N, G>(h, y, yn, k, o);
+        if (o.adaptive) EEst = dir_eest<D, G>(h, y, yn, k, o);
         nfe += 6;
       } else {
         rk4_step<DN>(f, h, y, k, yn);
@@ -248,7 +254,7 @@ __global__ void __launch_bounds__(256) k_forward_dual_dir(const float* __restric
               for (int c = 0; c < DN; c++) u[c] = h00 * y[c] + h10 * k[0][c] + h01 * yn[c] + h11 * k[4][c];
             }
           }
-          dir_save<N, G>(z_out, rec, j, B, b, q, u);
+          dir_save<D, G>(z_out, rec, j, B, b, q, u);
           j++;
           tj = tjn;
           tjn = s_ts(min(j + 1, T - 1));
@@ -266,19 +272,19 @@ __global__ void __launch_bounds__(256) k_forward_dual_dir(const float* __restric
   if (ret != LDE_RET_SUCCESS) {   // failed solve ⇒ NaN block and zero Jacobians (zero gradient) [REF GOKU.jl:114]
     float u[DN];
 #pragma unroll
-    for (int c = 0; c < DN; c++) u[c] = c < N ? __int_as_float(0x7fc00000) : 0.f;
-    for (int jj = 0; jj < T; jj++) dir_save<N, G>(z_out, rec, jj, B, b, q, u);
+    for (int c = 0; c < DN; c++) u[c] = c < D ? __int_as_float(0x7fc00000) : 0.f;
+    for (int jj = 0; jj < T; jj++) dir_save<D, G>(z_out, rec, jj, B, b, q, u);
   }
   if (q == 0) dual_finish((int)b, ret, nfe, nacc, nrej, rec, retcode, st_nfe, st_nacc, st_nrej, st_ret);
 }
 
 // g_q = Σ_j Σ_i J_j[i][q]·dz_out_j[i]: j outer, i inner
-template <int N>
+template <int D, int NP, int G>
 __global__ void __launch_bounds__(256) k_adjoint_dual_dir(DualRec rec, const float* __restrict__ dz_out, int T, int B, float* __restrict__ dz0,
                                                           float* __restrict__ dtheta, int32_t* __restrict__ st_nfe,
                                                           int32_t* __restrict__ st_nacc, int32_t* __restrict__ st_nrej,
                                                           int32_t* __restrict__ st_ret) {
-  constexpr int G = lde_host::dir_group_width(N), NP = 2 * N + 1;
+  static_assert(D <= NP && NP <= G && (G == 8 || G == 16), "directions: the D of ẑ₀ first, then θ's");
   const long long lane = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long b = lane / G;
   const int q = (int)(lane % G);
@@ -288,14 +294,14 @@ __global__ void __launch_bounds__(256) k_adjoint_dual_dir(DualRec rec, const flo
   if (n >= 0) {   // (a failed trajectory's gradient is zero whatever its cotangent holds: a NaN ẑ block usually brings a NaN one)
     const float* Jb = rec.J + (size_t)b * G + q;
     for (int j = 0; j < T; j++) {
-      const float* d = dz_out + ((size_t)j * B + b) * N;
-      const float* Jj = Jb + (size_t)j * N * B * G;
+      const float* d = dz_out + ((size_t)j * B + b) * D;
+      const float* Jj = Jb + (size_t)j * D * B * G;
 #pragma unroll
-      for (int i = 0; i < N; i++) g += Jj[(size_t)i * B * G] * d[i];
+      for (int i = 0; i < D; i++) g += Jj[(size_t)i * B * G] * d[i];
     }
   }
-  if (q < N) dz0[(size_t)N * b + q] = g;
-  else if (q < NP) dtheta[(size_t)(N + 1) * b + (q - N)] = g;
+  if (q < D) dz0[(size_t)D * b + q] = g;
+  else if (q < NP) dtheta[(size_t)(NP - D) * b + (q - D)] = g;
   if (q == 0) {
     st_nfe[b] = 0;
     st_nacc[b] = 0;
@@ -305,31 +311,44 @@ __global__ void __launch_bounds__(256) k_adjoint_dual_dir(DualRec rec, const flo
 }
 
 // ---- host-side launchers (called from lde_api.hip) -------------------------------------------------------------------------------
-int launch_forward_dual_dir(int N, int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o, const DualRec& rec,
-                            float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream) {
-  const int block = lde_host::dir_block(N, o.B);
-  const int64_t grid = lde_host::dir_grid(N, o.B);
+// lde_host::dir_dispatch hands out (rhs_kind, state_dim) as constants; this is the system they name
+template <int KIND, int N>
+struct DirSystem;
+template <int N>
+struct DirSystem<LDE_RHS_KURAMOTO, N> { using type = KuramotoDir<N>; };
+template <>
+struct DirSystem<LDE_RHS_DOUBLE_PENDULUM, 4> { using type = DoublePendDir; };
+
+int launch_forward_dual_dir(const lde_problem_desc& d, const float* z0, const float* theta, const double* ts_dev, const KOpts& o,
+                            const DualRec& rec, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret,
+                            hipStream_t stream) {
+  const int block = lde_host::dir_block(d, o.B);
+  const int64_t grid = lde_host::dir_grid(d, o.B);
   if (grid < 1 || grid > 0x7fffffff) return LDE_ERR_INVALID_ARG;
   const size_t shm = o.T <= DUAL_TS_LDS_MAX ? (size_t)o.T * sizeof(double) : 0;
-  const int rc = lde_host::dir_dispatch(N, solver, o.adaptive != 0, [&](auto n, auto S) -> int {
+  const int rc = lde_host::dir_dispatch(d, [&](auto kind, auto n, auto S) -> int {
+    using SYS = typename DirSystem<kind, n>::type;
+    static_assert(SYS::D == n && SYS::G == lde_host::dir_group_width(kind, n) && SYS::NP == lde_host::dir_partials(kind, n), "the host's shape of the launch is the system's");
     if (shm)
-      hipLaunchKernelGGL((k_forward_dual_dir<n, S, true>), dim3((unsigned)grid), dim3(block), shm, stream, z0, theta, ts_dev, o, rec, z_out,
+      hipLaunchKernelGGL((k_forward_dual_dir<SYS, S, true>), dim3((unsigned)grid), dim3(block), shm, stream, z0, theta, ts_dev, o, rec, z_out,
                          retcode, nfe, nacc, nrej, ret);
     else
-      hipLaunchKernelGGL((k_forward_dual_dir<n, S, false>), dim3((unsigned)grid), dim3(block), 0, stream, z0, theta, ts_dev, o, rec, z_out,
+      hipLaunchKernelGGL((k_forward_dual_dir<SYS, S, false>), dim3((unsigned)grid), dim3(block), 0, stream, z0, theta, ts_dev, o, rec, z_out,
                          retcode, nfe, nacc, nrej, ret);
     return LDE_OK;
   });
   return rc != LDE_OK ? rc : hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
 }
 
-int launch_adjoint_dual_dir(int N, const DualRec& rec, const float* dz_out, int T, int B, float* dz0, float* dtheta, int32_t* nfe,
-                            int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream) {
-  const int block = lde_host::dir_block(N, B);
-  const int64_t grid = lde_host::dir_grid(N, B);
+int launch_adjoint_dual_dir(const lde_problem_desc& d, const DualRec& rec, const float* dz_out, int T, int B, float* dz0, float* dtheta,
+                            int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream) {
+  const int block = lde_host::dir_block(d, B);
+  const int64_t grid = lde_host::dir_grid(d, B);
   if (grid < 1 || grid > 0x7fffffff) return LDE_ERR_INVALID_ARG;
-  const int rc = lde_host::dir_dispatch_n(N, [&](auto n) -> int {
-    hipLaunchKernelGGL(k_adjoint_dual_dir<n>, dim3((unsigned)grid), dim3(block), 0, stream, rec, dz_out, T, B, dz0, dtheta, nfe, nacc, nrej, ret);
+  const int rc = lde_host::dir_dispatch_n(d, [&](auto kind, auto n) -> int {
+    constexpr int NP = lde_host::dir_partials(kind, n), G = lde_host::dir_group_width(kind, n);
+    hipLaunchKernelGGL((k_adjoint_dual_dir<n, NP, G>), dim3((unsigned)grid), dim3(block), 0, stream, rec, dz_out, T, B, dz0, dtheta, nfe, nacc,
+                       nrej, ret);
     return LDE_OK;
   });
   return rc != LDE_OK ? rc : hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;

@@ -19,10 +19,12 @@ using lde::KOpts;
 using lde::StepRec;
 using lde::DualRec;
 
-// ---- the lane-per-direction dual solve (csrc/lde_dual_dir.hip: k_forward_dual_dir / k_adjoint_dual_dir; LDE_RHS_KURAMOTO, N states and
-// NP = 2N + 1 partial directions q = (φ₀ (N), ω (N), K)): a trajectory is a group of G consecutive lanes, lane q of it carries the N values
-// and the ONE tangent column ∂φ/∂q_q. G = 8 holds NP ≤ 7 (N ≤ 3), G = 16 holds NP ≤ 15 (N ≤ 7): a group never leaves a 16-lane row, which
-// is what its cross-lane sums (DPP within a row) need. 0: N is not served.
+// ---- the lane-per-direction dual solve (csrc/lde_dual_dir.hip: k_forward_dual_dir / k_adjoint_dual_dir over a system): a trajectory of D
+// states and NP partial directions is a group of G consecutive lanes, lane q of it carries the D values and the ONE tangent column ∂z/∂q_q.
+// G = 8 holds NP ≤ 8, G = 16 holds NP ≤ 16: a group never leaves a 16-lane row, which is what its cross-lane sums (DPP within a row) need.
+// Two systems: LDE_RHS_KURAMOTO, D = N and NP = 2N + 1 directions q = (φ₀ (N), ω (N), K), N ≤ 3 in 8 lanes and N ≤ 7 in 16 (the forms that
+// take N alone are this system's; 0: N is not served), and LDE_RHS_DOUBLE_PENDULUM, D = 4 and NP = 8 = (ẑ₀ (4), L₁, L₂, m₁, m₂): one 8-lane
+// group with no pad lane. The forms that take (rhs_kind, state_dim) or a description serve both.
 constexpr int KURAMOTO_MIN_N = 2, KURAMOTO_MAX_N = 7;
 static constexpr bool dir_state_ok(int N) { return N >= KURAMOTO_MIN_N && N <= KURAMOTO_MAX_N; }
 static constexpr int dir_partials(int N) { return dir_state_ok(N) ? 2 * N + 1 : 0; }
@@ -32,13 +34,24 @@ static constexpr int dir_group_width(int N) { return !dir_state_ok(N) ? 0 : N <=
 static int64_t dir_lanes(int N, int B) { return B < 1 ? 0 : (int64_t)B * dir_group_width(N); }
 static int dir_block(int N, int B) { return dir_lanes(N, B) <= 4096 ? 64 : 256; }
 static int64_t dir_grid(int N, int B) { return (dir_lanes(N, B) + dir_block(N, B) - 1) / dir_block(N, B); }
+// … of either system: D = state_dim of a right-hand side of `kind` (0: not a system of these kernels, or a D it does not serve)
+constexpr int DPEND_D = 4, DPEND_P = 4;
+static constexpr bool dir_state_ok(int kind, int D) { return kind == LDE_RHS_KURAMOTO ? dir_state_ok(D) : kind == LDE_RHS_DOUBLE_PENDULUM && D == DPEND_D; }
+static constexpr int dir_partials(int kind, int D) { return kind == LDE_RHS_KURAMOTO ? dir_partials(D) : dir_state_ok(kind, D) ? DPEND_D + DPEND_P : 0; }
+static constexpr int dir_group_width(int kind, int D) { return kind == LDE_RHS_KURAMOTO ? dir_group_width(D) : dir_state_ok(kind, D) ? 8 : 0; }
+static int dir_group_width(const lde_problem_desc& d) { return dir_group_width(d.rhs_kind, d.state_dim); }
+static int64_t dir_lanes(const lde_problem_desc& d, int B) { return B < 1 ? 0 : (int64_t)B * dir_group_width(d); }
+static int dir_block(const lde_problem_desc& d, int B) { return dir_lanes(d, B) <= 4096 ? 64 : 256; }
+static int64_t dir_grid(const lde_problem_desc& d, int B) { return (dir_lanes(d, B) + dir_block(d, B) - 1) / dir_block(d, B); }
 
 static bool has_mlp(const lde_problem_desc& d) {
   return d.rhs_kind == LDE_RHS_MLP || d.rhs_kind == LDE_RHS_PENDULUM_PLUS_MLP;
 }
 static bool is_lv(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_LOTKA_VOLTERRA; }
 static bool is_kuramoto(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_KURAMOTO; }
-static bool has_pend(const lde_problem_desc& d) { return d.rhs_kind != LDE_RHS_MLP && !is_lv(d) && !is_kuramoto(d); }
+static bool is_dpend(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_DOUBLE_PENDULUM; }
+static bool is_dir(const lde_problem_desc& d) { return is_kuramoto(d) || is_dpend(d); }   // the systems of the lane-per-direction kernels
+static bool has_pend(const lde_problem_desc& d) { return d.rhs_kind != LDE_RHS_MLP && !is_lv(d) && !is_dir(d); }
 static bool is_sde(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_SPENDULUM; }
 static bool sde_solver(int solver) { return solver == LDE_SOLVER_EM || solver == LDE_SOLVER_EULER_HEUN; }
 
@@ -49,8 +62,9 @@ static int validate(const lde_problem_desc* d, std::string* why) {
   };
   if (!d) return bad("desc is NULL");
   if (d->abi_version != LDE_ABI_VERSION) return bad("abi_version mismatch");
-  // 6 is no right-hand side and stays refused: tests/lv_host_driver.cpp pins it as "unknown rhs_kind", so the Kuramoto system took 7
-  if (d->rhs_kind < 0 || d->rhs_kind > LDE_RHS_KURAMOTO || d->rhs_kind == 6) return bad("unknown rhs_kind");
+  // 6 and 8 are no right-hand sides and stay refused: tests/lv_host_driver.cpp and tests/kuramoto_host_driver.cpp pin them as "unknown
+  // rhs_kind", so the Kuramoto system took 7 and the double pendulum 9
+  if (d->rhs_kind < 0 || d->rhs_kind > LDE_RHS_DOUBLE_PENDULUM || d->rhs_kind == 6 || d->rhs_kind == 8) return bad("unknown rhs_kind");
   if (d->state_dim < 1 || d->param_dim < 0 || d->augment_dim < 0) return bad("bad dims");
   if (has_pend(*d) && (d->state_dim != 2 || d->param_dim != 1 || d->augment_dim != 0))
     return bad("pendulum RHS needs state_dim=2, param_dim=1, augment_dim=0");
@@ -58,6 +72,8 @@ static int validate(const lde_problem_desc* d, std::string* why) {
     return bad("LDE_RHS_LOTKA_VOLTERRA needs state_dim=2, param_dim=4, augment_dim=0");
   if (is_kuramoto(*d) && (d->state_dim < KURAMOTO_MIN_N || d->state_dim > KURAMOTO_MAX_N || d->param_dim != d->state_dim + 1 || d->augment_dim != 0))
     return bad("LDE_RHS_KURAMOTO needs state_dim=N with 2 <= N <= 7, param_dim=N+1, augment_dim=0");
+  if (is_dpend(*d) && (d->state_dim != DPEND_D || d->param_dim != DPEND_P || d->augment_dim != 0))
+    return bad("LDE_RHS_DOUBLE_PENDULUM needs state_dim=4, param_dim=4, augment_dim=0");
   if (d->rhs_kind == LDE_RHS_MLP && d->param_dim != 0) return bad("MLP RHS takes no per-trajectory parameters");
   if (has_mlp(*d)) {
     if (d->n_layers < 1 || d->n_layers > LDE_MAX_LAYERS) return bad("n_layers out of range");
@@ -70,6 +86,7 @@ static int validate(const lde_problem_desc* d, std::string* why) {
   if (is_sde(*d) && d->n_layers != 0) return bad("LDE_RHS_SPENDULUM is analytic: n_layers must be 0");
   if (is_lv(*d) && d->n_layers != 0) return bad("LDE_RHS_LOTKA_VOLTERRA is analytic: n_layers must be 0");
   if (is_kuramoto(*d) && d->n_layers != 0) return bad("LDE_RHS_KURAMOTO is analytic: n_layers must be 0");
+  if (is_dpend(*d) && d->n_layers != 0) return bad("LDE_RHS_DOUBLE_PENDULUM is analytic: n_layers must be 0");
   if (d->solver != LDE_SOLVER_TSIT5 && d->solver != LDE_SOLVER_RK4 && !sde_solver(d->solver)) return bad("unknown solver");
   if (d->batching != LDE_BATCH_PER_TRAJECTORY && d->batching != LDE_BATCH_COUPLED && d->batching != LDE_BATCH_COUPLED_GLOBAL)
     return bad("unknown batching");
@@ -105,6 +122,11 @@ static int validate(const lde_problem_desc* d, std::string* why) {
     if (d->batching != LDE_BATCH_PER_TRAJECTORY) return unsupported("LDE_RHS_KURAMOTO: no coupled solve; LDE_BATCH_PER_TRAJECTORY only");
     if (d->sensealg != LDE_SENSE_FORWARD_DUAL)
       return unsupported("LDE_RHS_KURAMOTO: only the solve on dual numbers exists for this system (no discrete sweep, no continuous adjoint); use LDE_SENSE_FORWARD_DUAL");
+  }
+  if (is_dpend(*d)) {   // … and the double pendulum, their second system
+    if (d->batching != LDE_BATCH_PER_TRAJECTORY) return unsupported("LDE_RHS_DOUBLE_PENDULUM: no coupled solve; LDE_BATCH_PER_TRAJECTORY only");
+    if (d->sensealg != LDE_SENSE_FORWARD_DUAL)
+      return unsupported("LDE_RHS_DOUBLE_PENDULUM: only the solve on dual numbers exists for this system (no discrete sweep, no continuous adjoint); use LDE_SENSE_FORWARD_DUAL");
   }
   if (d->solver == LDE_SOLVER_RK4 && d->adaptive) {
     if (why) *why = "RK4 is fixed-step only here: pass adaptive=0, dt=h";
@@ -157,11 +179,12 @@ static StepRec rec_view(const lde_problem_desc& d, void* base, int B, int cap, b
 // LDE_SENSE_FORWARD_DUAL's record (include/lde.h: "the dual record"): n [B] | J [T][2][NP][B] f32 | with the step trace t, dt [cap][B] f64;
 // `np` = NP = D + P partials per component — 3 for the pendulums (the four-argument forms), 6 for Lotka–Volterra (dual_partials).
 // J first: its place depends on B alone, so the pullback (which reads n and J) finds it whether or not the forward traced its steps.
-// The Kuramoto system's record is its own (include/lde.h: "the Kuramoto system"): n [B] | J [T][N][B][G] f32 | t, dt — a trajectory's G
-// lanes (dir_group_width) fastest, so N·G floats per (save time, trajectory) where the two-state systems have 2·NP; `np` is then N·G/2 (G is
-// even), and every size and offset below serves this kind unchanged.
+// The record of the lane-per-direction kernels' systems is its own (include/lde.h: "the Kuramoto system", "the double pendulum"): n [B] |
+// J [T][D][B][G] f32 | t, dt — a trajectory's G lanes (dir_group_width) fastest, so D·G floats per (save time, trajectory) where the
+// two-state systems have 2·NP; `np` is then D·G/2 (G is even; 16 for the double pendulum), and every size and offset below serves these
+// kinds unchanged.
 static int dual_partials(const lde_problem_desc& d) {
-  if (is_kuramoto(d)) return dir_state_ok(d.state_dim) ? d.state_dim * dir_group_width(d.state_dim) / 2 : 0;
+  if (is_dir(d)) return d.state_dim * dir_group_width(d) / 2;   // (0 where the kind does not serve state_dim)
   return is_lv(d) ? 6 : 3;
 }
 static size_t dual_rec_bytes(int B, int T, int cap, bool trace, int np) {
@@ -326,6 +349,20 @@ static int dir_dispatch_n(int N, F&& f) {
 template <class F>
 static int dir_dispatch(int N, int solver, bool adaptive, F&& f) {
   return dir_dispatch_n(N, [&](auto n) -> int { return lv_dispatch(solver, adaptive, [&](auto S) -> int { return f(n, S); }); });
+}
+// … over the system: f(KIND, D) / f(KIND, D, SOLVER) with (LDE_RHS_KURAMOTO, N = 2 … 7) or (LDE_RHS_DOUBLE_PENDULUM, 4) — the one dispatch
+// behind the one forward and the one pullback launcher; any other kind or state_dim is LDE_ERR_UNSUPPORTED.
+template <class F>
+static int dir_dispatch_n(const lde_problem_desc& d, F&& f) {
+  if (is_kuramoto(d)) return dir_dispatch_n(d.state_dim, [&](auto n) -> int { return f(std::integral_constant<int, LDE_RHS_KURAMOTO>{}, n); });
+  if (is_dpend(d) && d.state_dim == DPEND_D) return f(std::integral_constant<int, LDE_RHS_DOUBLE_PENDULUM>{}, std::integral_constant<int, DPEND_D>{});
+  return LDE_ERR_UNSUPPORTED;
+}
+template <class F>
+static int dir_dispatch(const lde_problem_desc& d, F&& f) {
+  return dir_dispatch_n(d, [&](auto kind, auto n) -> int {
+    return lv_dispatch(d.solver, d.adaptive != 0, [&](auto S) -> int { return f(kind, n, S); });
+  });
 }
 
 // Which mapping serves a solve under LDE_SENSE_FORWARD_DUAL (csrc/lde_dual.h: dual_block switches on this, for every system and for the

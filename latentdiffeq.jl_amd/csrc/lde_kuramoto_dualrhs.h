@@ -9,12 +9,15 @@
 // on a φ₀-lane or a pad lane — as two per-lane constants, so that no lane branches.
 #pragma once
 #include "lde_device.h"
+#include "lde_host.h"
 
 namespace lde {
 
 template <int N>
 struct KuramotoDir {
+  static constexpr int D = N;            // components
   static constexpr int NP = 2 * N + 1;   // partial directions: φ₀ (N), ω (N), K
+  static constexpr int G = lde_host::dir_group_width(N);   // lanes of a trajectory: 8 for N ≤ 3, 16 for N ≤ 7
   static constexpr int DN = 2 * N;       // floats of a lane's state: the N values and its one tangent column
   float om[N];     // ω
   float kn;        // K/N

@@ -24,8 +24,9 @@ struct StepRec {
 // LDE_SENSE_FORWARD_DUAL's record in device memory (include/lde.h: lde_set_step_record): written by k_forward_dual (csrc/lde_dual.hip) or
 // k_pend_forward_sde, read by k_adjoint_dual. J holds ∂ẑ(t_j)/∂q of every save time, trajectory fastest, with NP partials per component — a
 // compile-time constant of the kernels (the system's: 3 for the pendulums, q = (x₀, v₀, L); 6 for Lotka–Volterra, q = (x₀, y₀, α, β, γ, δ)):
-// element (j, i, q, b) at ((j·2 + i)·NP + q)·B + b. No field says which NP: the kernels read none. The Kuramoto system's kernels
-// (csrc/lde_dual_dir.hip) use the same struct with extents of their own, J [T][N][B][G]: element (j, i, b, q) at ((j·N + i)·B + b)·G + q.
+// element (j, i, q, b) at ((j·2 + i)·NP + q)·B + b. No field says which NP: the kernels read none. The lane-per-direction kernels
+// (csrc/lde_dual_dir.hip: Kuramoto, the double pendulum) use the same struct with extents of their own, J [T][D][B][G]: element (j, i, b, q) at
+// ((j·D + i)·B + b)·G + q.
 struct DualRec {
   int32_t* n;    // [B] accepted steps; −retcode for a failed trajectory
   float* J;      // [T][2][NP][B]
