@@ -65,6 +65,10 @@ enum lde_rhs_kind {
                                      g = 10 — the GOKU-net paper's second benchmark. LDE_SENSE_FORWARD_DUAL only; see "the double pendulum"
                                      below. 9, not 8: the value 8, like 6, is no right-hand side and stays refused as "unknown rhs_kind"
                                      (the tests of the Lotka–Volterra and Kuramoto host logic pin both refusals) */
+  LDE_RHS_CVS               = 11, /* the cardiovascular system: z = (p_a/100, p_v/10, s, sv/100), θ = (i_ext, r_mod) per trajectory (state_dim 4,
+                                     param_dim 2) — the GOKU-net paper's third benchmark, its form as recalled (unpinned).
+                                     LDE_SENSE_FORWARD_DUAL only; see "the cardiovascular system" below. 11, not 10: the value 10, like 6 and
+                                     8, is no right-hand side and stays refused as "unknown rhs_kind" (the double pendulum's host tests pin it) */
   LDE_RHS_LOTKA_VOLTERRA    = 5   /* Lotka–Volterra: dx = αx − βxy, dy = −γy + δxy, θ = (α, β, γ, δ) = p[1:4] per trajectory (state_dim 2,
                                      param_dim 4). The first right-hand side with more than one parameter — the reference's `diffeq` plug-in is
                                      "any Julia function" [REF src/models/GOKU.jl:98-130]; this one has no file of its own there.
@@ -327,6 +331,40 @@ int lde_set_noise(lde_handle* h, uint64_t seed, uint64_t offset, uint64_t first_
  * records are. Failure semantics (NaN ẑ block, zero J, n = −retcode, zero gradient) and statistics are those of the pendulum's dual solve.
  * lde_last_kernel: "k_forward_dual_dir" / "k_adjoint_dual_dir" (labels of the path, shared with the Kuramoto system). */
 
+/* ---- the cardiovascular system (LDE_RHS_CVS = 11): z = (z₀, z₁, z₂, z₃), θ = (i_ext, r_mod) ----
+ * The GOKU-net paper's third benchmark. STATED DEVIATION: the reference repository has no file for this system, and neither the paper nor
+ * its code was at hand when this was written — the form below follows the GOKU-net authors' data generator AS RECALLED, unpinned (marked as
+ * the AdaBelief ε placement is). The text here is the contract.
+ * State scaling — all four states are O(1): arterial pressure p_a = 100·z₀, venous pressure p_v = 10·z₁, baroreflex signal s = z₂, stroke
+ * volume sv = 100·z₃. Parameters: i_ext (external blood flow; ≤ 0 is blood loss) and r_mod (a drop of the peripheral resistance; may be 0).
+ *     f_hr  = s·(F_MAX − F_MIN) + F_MIN
+ *     r_tpr = s·(R_MAX − R_MIN) + R_MIN − r_mod
+ *     dva   = −(p_a − p_v)/r_tpr + sv·f_hr
+ *     z₀' = dva / (C_A·100)
+ *     z₁' = (−dva + i_ext) / (C_V·10)
+ *     z₂' = (1 − σ(K_W·(p_a − P_SET)) − s) / TAU          σ(x) = 1/(1 + e^(−x))
+ *     z₃' = i_ext · SV_MOD
+ * with F_MAX = 3, F_MIN = 2/3, R_MAX = 2.134, R_MIN = 0.5335, C_A = 4, C_V = 111, K_W = 0.1838, P_SET = 70, TAU = 20, SV_MOD = 0.001.
+ * 1 − σ(x) is evaluated as w = 1/(1 + eˣ), its partial as −K_W·w·(1 − w)·∂p_a: a pressure far from the set point saturates w to 0 or 1 with
+ * finite (zero) partials. The blood volume 400·z₀ + 1110·z₁ − i_ext·t is constant along a solution; z₃ is linear in t.
+ * z0, dz0 [4×B] — trajectory b's values at z0[4·b … 4·b + 3] — z_out, dz_out [T×B×4]; theta, dtheta [2×B], trajectory b's (i_ext, r_mod) at
+ * theta[2·b], theta[2·b + 1].
+ * Served: state_dim = 4, param_dim = 2, augment_dim = 0, n_layers = 0 (anything else: LDE_ERR_INVALID_ARG), LDE_BATCH_PER_TRAJECTORY,
+ * LDE_SOLVER_TSIT5 adaptive or fixed-step and LDE_SOLVER_RK4 fixed-step, sensealg LDE_SENSE_FORWARD_DUAL: NP = 6 partials per component in the
+ * order (z₀₀, z₁₀, z₂₀, z₃₀, i_ext, r_mod), all of them in every norm of the step control, the RMS over the four components.
+ * lde_num_weights = 0; dW must be NULL. The enum value is 11: rhs_kind = 6, 8 and 10 are no right-hand sides ("unknown rhs_kind").
+ * Refused with LDE_ERR_UNSUPPORTED, lde_desc_error naming the missing piece: another sensealg ("… use LDE_SENSE_FORWARD_DUAL"),
+ * LDE_BATCH_COUPLED, the stochastic steppers and adaptive RK4 (their own texts); lde_set_noise on such a handle.
+ * The kernels are the Kuramoto system's, a lane per partial direction: one group of G = 8 lanes per trajectory, lanes 6 and 7 pad lanes. The
+ * dual record (A(x) = x rounded up to a multiple of 256 bytes):
+ *     n  int32 [B]                at 0                      as below
+ *     J  float [T][4][B][8]       at A(4B)                  J[j][i][b][q] = ∂ẑ_i(t_j)/∂q_q of trajectory b, q fastest: element
+ *                                                           ((j·4 + i)·B + b)·8 + q; q = 0 … 3: ẑ₀, 4: i_ext, 5: r_mod; q = 6, 7: 0 (pad lanes)
+ *     t, dt double [cap][B]       at A(4B) + A(128·TB)      option "step_trace" = 1 only, as below
+ * served by lde_step_record_bytes, lde_set_step_record, lde_reserve, lde_step_record_status and lde_get_step_record as the other dual
+ * records are. Failure semantics (NaN ẑ block, zero J, n = −retcode, zero gradient) and statistics are those of the pendulum's dual solve.
+ * lde_last_kernel: "k_forward_dual_dir" / "k_adjoint_dual_dir" (labels of the path, shared with the Kuramoto system). */
+
 /* Pre-size the handle's workspace for batches up to B and T save points (so that later
  * lde_forward/lde_adjoint calls allocate nothing and can be captured in a hipGraph). */
 int lde_reserve(lde_handle* h, int B, int T);
@@ -412,7 +450,7 @@ int lde_set_global_sum_peers(lde_handle* h, int rank, int nranks, void* const* m
  *                                                           LDE_RHS_LOTKA_VOLTERRA
  *     t  double [cap][B]          at A(4B) + A(4·2·NP·TB)   option "step_trace" = 1 only: start time of accepted step s of trajectory b at s·B + b
  *     dt double [cap][B]          at … + A(8·cap·B)         … and its size; cap = lde_step_record_capacity(h, T)
- * (Pendulums: J [T][2][3][B], the trace at A(4B) + A(24TB), as before. LDE_RHS_KURAMOTO: J [T][N][B][G], "the Kuramoto system" above; LDE_RHS_DOUBLE_PENDULUM: J [T][4][B][8], "the double pendulum" above.) J of a failed trajectory is zero. With "step_trace" = 1 lde_get_step_record(h, 0, …) returns the accepted steps (what a checker replays). */
+ * (Pendulums: J [T][2][3][B], the trace at A(4B) + A(24TB), as before. LDE_RHS_KURAMOTO: J [T][N][B][G], "the Kuramoto system" above; LDE_RHS_DOUBLE_PENDULUM and LDE_RHS_CVS: J [T][4][B][8], "the double pendulum" and "the cardiovascular system" above.) J of a failed trajectory is zero. With "step_trace" = 1 lde_get_step_record(h, 0, …) returns the accepted steps (what a checker replays). */
 int64_t lde_step_record_bytes(const lde_handle* h, int B, int T);
 int lde_set_step_record(lde_handle* h, void* rec_dev, int64_t bytes);
 /* Did the record hold the solve? lde_step_record_capacity(h, T) = the accepted steps per sequence a record made now would hold;

@@ -423,7 +423,7 @@ int lde_forward(lde_handle* h, const float* z0, const float* theta, const double
       rc = lde::launch_pend_forward_sde(h->d.solver, z0, theta, h->ts_dev, o, r, h->noise, sde_plan(h->d, ts, T).over, z_out, retcode, st[0],
                                         st[1], st[2], st[3], stream);
       h->last_kernel[0] = "k_pend_forward_sde";
-    } else if (is_dir(h->d)) {   // Kuramoto and the double pendulum: a lane per (trajectory, partial direction) (csrc/lde_dual_dir.hip)
+    } else if (is_dir(h->d)) {   // Kuramoto, the double pendulum and CVS: a lane per (trajectory, partial direction) (csrc/lde_dual_dir.hip)
       rc = lde::launch_forward_dual_dir(h->d, z0, theta, h->ts_dev, o, r, z_out, retcode, st[0], st[1], st[2], st[3], stream);
       h->last_kernel[0] = "k_forward_dual_dir";
     } else {              // the pendulums and Lotka–Volterra: one kernel over the system (csrc/lde_dual.hip)

@@ -1,6 +1,7 @@
 // lde_dual_dir.hip — LDE_SENSE_FORWARD_DUAL with ONE LANE PER (TRAJECTORY, PARTIAL DIRECTION): the dual-number solve for systems of more than
-// two states, as kernels over a system: LDE_RHS_KURAMOTO (N = 2 … 7 phase oscillators: csrc/lde_kuramoto_dualrhs.h, KuramotoDir<N>) and
-// LDE_RHS_DOUBLE_PENDULUM (four states, four parameters: csrc/lde_dpend_dualrhs.h, DoublePendDir).
+// two states, as kernels over a system: LDE_RHS_KURAMOTO (N = 2 … 7 phase oscillators: csrc/lde_kuramoto_dualrhs.h, KuramotoDir<N>),
+// LDE_RHS_DOUBLE_PENDULUM (four states, four parameters: csrc/lde_dpend_dualrhs.h, DoublePendDir) and LDE_RHS_CVS (the cardiovascular
+// system, four states, two parameters: csrc/lde_cvs_dualrhs.h, CvsDir).
 //
 // k_forward_dual (csrc/lde_dual.hip) keeps a trajectory's whole dual state, D·(1 + D + P) floats, and Tsit5's seven slopes of it in one lane:
 // 14 floats per vector for Lotka–Volterra, 112 for seven oscillators — it cannot grow in D. Here a trajectory is a GROUP of G consecutive
@@ -8,7 +9,7 @@
 // group carries
 //   * the D values z — redundant: every lane of the group computes the same bits from the same inputs by the same instructions —
 //   * and ONE tangent column v = ∂z/∂q_q, q = (ẑ₀ (D), θ (NP − D)),
-// 2D floats per vector, ≈ 12 vectors live. Lanes q ≥ NP are pad lanes (Kuramoto: G − 2N − 1 of them; the double pendulum: none): zero seed,
+// 2D floats per vector, ≈ 12 vectors live. Lanes q ≥ NP are pad lanes (Kuramoto: G − 2N − 1 of them; the double pendulum: none; CVS: two): zero seed,
 // zero forcing, so their tangent stays 0, adds 0 to every norm, and they need no branch. The stage sums, the solution weights and the
 // interpolant are lde_device.h's on the 2D-vector (tsit5_attempt / rk4_step / tsit5_dense_*), as k_forward_dual uses them on its DN-vector;
 // the loop around them is k_forward_dual's. What a system supplies: D, NP ≤ G, G, DN = 2·D, load(theta, b, q), seed(z0, b, q, y),
@@ -25,7 +26,7 @@
 // a group, so a lane's partners are always active; a group whose trajectory is past the batch leaves as a whole, after dual_stage_ts's
 // barrier. Groups of one wave do take different numbers of steps: that is divergence between groups, never inside one.
 //
-// The dual record of this kind (lde_types.h: DualRec; include/lde.h: "the Kuramoto system", "the double pendulum") is n [B] | J [T][D][B][G]:
+// The dual record of this kind (lde_types.h: DualRec; include/lde.h: "the Kuramoto system", "the double pendulum", "the cardiovascular system") is n [B] | J [T][D][B][G]:
 // element (j, i, b, q) = ∂ẑ_i(t_j)/∂q_q at ((j·D + i)·B + b)·G + q — a wave's 64 lanes write 64 consecutive floats per (save time,
 // component), and the pullback reads them the same way (the trajectory-fastest layout of the two-state kernels would put neighbouring lanes
 // B floats apart). Pad lanes write their zeros. ẑ goes to z_out [T×B×D] from the group's first lane, which also writes the step trace, the
@@ -37,6 +38,7 @@
 #include "lde_host.h"
 #include "lde_kuramoto_dualrhs.h"
 #include "lde_dpend_dualrhs.h"
+#include "lde_cvs_dualrhs.h"
 
 namespace lde {
 
@@ -148,7 +150,7 @@ __device__ __forceinline__ void dir_save(float* z_out, const DualRec& rec, int j
   for (int i = 0; i < D; i++) Jj[(size_t)i * B * G] = u[D + i];
 }
 
-// SYS (csrc/lde_kuramoto_dualrhs.h: KuramotoDir<N>; csrc/lde_dpend_dualrhs.h: DoublePendDir) supplies D components, NP ≤ G directions, the
+// SYS (csrc/lde_kuramoto_dualrhs.h: KuramotoDir<N>; csrc/lde_dpend_dualrhs.h: DoublePendDir; csrc/lde_cvs_dualrhs.h: CvsDir) supplies D components, NP ≤ G directions, the
 // group width G (8 or 16), DN = 2·D, load(theta, b, q), seed(z0, b, q, y), anchor(y) and operator()(u, du).
 template <class SYS, int SOLVER, bool TS_LDS>
 __global__ void __launch_bounds__(256) k_forward_dual_dir(const float* __restrict__ z0, const float* __restrict__ theta,
@@ -311,13 +313,15 @@ __global__ void __launch_bounds__(256) k_adjoint_dual_dir(DualRec rec, const flo
 }
 
 // ---- host-side launchers (called from lde_api.hip) -------------------------------------------------------------------------------
-// lde_host::dir_dispatch hands out (rhs_kind, state_dim) as constants; this is the system they name
+// lde_host::dir_system_dispatch hands out (rhs_kind, state_dim) as constants; this is the system they name
 template <int KIND, int N>
 struct DirSystem;
 template <int N>
 struct DirSystem<LDE_RHS_KURAMOTO, N> { using type = KuramotoDir<N>; };
 template <>
 struct DirSystem<LDE_RHS_DOUBLE_PENDULUM, 4> { using type = DoublePendDir; };
+template <>
+struct DirSystem<LDE_RHS_CVS, 4> { using type = CvsDir; };
 
 int launch_forward_dual_dir(const lde_problem_desc& d, const float* z0, const float* theta, const double* ts_dev, const KOpts& o,
                             const DualRec& rec, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret,
@@ -326,7 +330,7 @@ int launch_forward_dual_dir(const lde_problem_desc& d, const float* z0, const fl
   const int64_t grid = lde_host::dir_grid(d, o.B);
   if (grid < 1 || grid > 0x7fffffff) return LDE_ERR_INVALID_ARG;
   const size_t shm = o.T <= DUAL_TS_LDS_MAX ? (size_t)o.T * sizeof(double) : 0;
-  const int rc = lde_host::dir_dispatch(d, [&](auto kind, auto n, auto S) -> int {
+  const int rc = lde_host::dir_system_dispatch(d, [&](auto kind, auto n, auto S) -> int {
     using SYS = typename DirSystem<kind, n>::type;
     static_assert(SYS::D == n && SYS::G == lde_host::dir_group_width(kind, n) && SYS::NP == lde_host::dir_partials(kind, n), "the host's shape of the launch is the system's");
     if (shm)
@@ -345,7 +349,7 @@ int launch_adjoint_dual_dir(const lde_problem_desc& d, const DualRec& rec, const
   const int block = lde_host::dir_block(d, B);
   const int64_t grid = lde_host::dir_grid(d, B);
   if (grid < 1 || grid > 0x7fffffff) return LDE_ERR_INVALID_ARG;
-  const int rc = lde_host::dir_dispatch_n(d, [&](auto kind, auto n) -> int {
+  const int rc = lde_host::dir_system_dispatch_n(d, [&](auto kind, auto n) -> int {
     constexpr int NP = lde_host::dir_partials(kind, n), G = lde_host::dir_group_width(kind, n);
     hipLaunchKernelGGL((k_adjoint_dual_dir<n, NP, G>), dim3((unsigned)grid), dim3(block), 0, stream, rec, dz_out, T, B, dz0, dtheta, nfe, nacc,
                        nrej, ret);

@@ -22,9 +22,10 @@ using lde::DualRec;
 // ---- the lane-per-direction dual solve (csrc/lde_dual_dir.hip: k_forward_dual_dir / k_adjoint_dual_dir over a system): a trajectory of D
 // states and NP partial directions is a group of G consecutive lanes, lane q of it carries the D values and the ONE tangent column ∂z/∂q_q.
 // G = 8 holds NP ≤ 8, G = 16 holds NP ≤ 16: a group never leaves a 16-lane row, which is what its cross-lane sums (DPP within a row) need.
-// Two systems: LDE_RHS_KURAMOTO, D = N and NP = 2N + 1 directions q = (φ₀ (N), ω (N), K), N ≤ 3 in 8 lanes and N ≤ 7 in 16 (the forms that
+// Three systems: LDE_RHS_KURAMOTO, D = N and NP = 2N + 1 directions q = (φ₀ (N), ω (N), K), N ≤ 3 in 8 lanes and N ≤ 7 in 16 (the forms that
 // take N alone are this system's; 0: N is not served), and LDE_RHS_DOUBLE_PENDULUM, D = 4 and NP = 8 = (ẑ₀ (4), L₁, L₂, m₁, m₂): one 8-lane
-// group with no pad lane. The forms that take (rhs_kind, state_dim) or a description serve both.
+// group with no pad lane; and LDE_RHS_CVS, D = 4 and NP = 6 = (ẑ₀ (4), i_ext, r_mod): one 8-lane group whose lanes 6 and 7 are pad lanes. The
+// forms that take (rhs_kind, state_dim) or a description serve all three.
 constexpr int KURAMOTO_MIN_N = 2, KURAMOTO_MAX_N = 7;
 static constexpr bool dir_state_ok(int N) { return N >= KURAMOTO_MIN_N && N <= KURAMOTO_MAX_N; }
 static constexpr int dir_partials(int N) { return dir_state_ok(N) ? 2 * N + 1 : 0; }
@@ -36,8 +37,13 @@ static int dir_block(int N, int B) { return dir_lanes(N, B) <= 4096 ? 64 : 256; 
 static int64_t dir_grid(int N, int B) { return (dir_lanes(N, B) + dir_block(N, B) - 1) / dir_block(N, B); }
 // … of either system: D = state_dim of a right-hand side of `kind` (0: not a system of these kernels, or a D it does not serve)
 constexpr int DPEND_D = 4, DPEND_P = 4;
-static constexpr bool dir_state_ok(int kind, int D) { return kind == LDE_RHS_KURAMOTO ? dir_state_ok(D) : kind == LDE_RHS_DOUBLE_PENDULUM && D == DPEND_D; }
-static constexpr int dir_partials(int kind, int D) { return kind == LDE_RHS_KURAMOTO ? dir_partials(D) : dir_state_ok(kind, D) ? DPEND_D + DPEND_P : 0; }
+constexpr int CVS_D = 4, CVS_P = 2;
+static constexpr bool dir_state_ok(int kind, int D) {
+  return kind == LDE_RHS_KURAMOTO ? dir_state_ok(D) : (kind == LDE_RHS_DOUBLE_PENDULUM && D == DPEND_D) || (kind == LDE_RHS_CVS && D == CVS_D);
+}
+static constexpr int dir_partials(int kind, int D) {
+  return kind == LDE_RHS_KURAMOTO ? dir_partials(D) : !dir_state_ok(kind, D) ? 0 : kind == LDE_RHS_CVS ? CVS_D + CVS_P : DPEND_D + DPEND_P;
+}
 static constexpr int dir_group_width(int kind, int D) { return kind == LDE_RHS_KURAMOTO ? dir_group_width(D) : dir_state_ok(kind, D) ? 8 : 0; }
 static int dir_group_width(const lde_problem_desc& d) { return dir_group_width(d.rhs_kind, d.state_dim); }
 static int64_t dir_lanes(const lde_problem_desc& d, int B) { return B < 1 ? 0 : (int64_t)B * dir_group_width(d); }
@@ -50,7 +56,8 @@ static bool has_mlp(const lde_problem_desc& d) {
 static bool is_lv(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_LOTKA_VOLTERRA; }
 static bool is_kuramoto(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_KURAMOTO; }
 static bool is_dpend(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_DOUBLE_PENDULUM; }
-static bool is_dir(const lde_problem_desc& d) { return is_kuramoto(d) || is_dpend(d); }   // the systems of the lane-per-direction kernels
+static bool is_cvs(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_CVS; }
+static bool is_dir(const lde_problem_desc& d) { return is_kuramoto(d) || is_dpend(d) || is_cvs(d); }   // the systems of the lane-per-direction kernels
 static bool has_pend(const lde_problem_desc& d) { return d.rhs_kind != LDE_RHS_MLP && !is_lv(d) && !is_dir(d); }
 static bool is_sde(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_SPENDULUM; }
 static bool sde_solver(int solver) { return solver == LDE_SOLVER_EM || solver == LDE_SOLVER_EULER_HEUN; }
@@ -63,8 +70,8 @@ static int validate(const lde_problem_desc* d, std::string* why) {
   if (!d) return bad("desc is NULL");
   if (d->abi_version != LDE_ABI_VERSION) return bad("abi_version mismatch");
   // 6 and 8 are no right-hand sides and stay refused: tests/lv_host_driver.cpp and tests/kuramoto_host_driver.cpp pin them as "unknown
-  // rhs_kind", so the Kuramoto system took 7 and the double pendulum 9
-  if (d->rhs_kind < 0 || d->rhs_kind > LDE_RHS_DOUBLE_PENDULUM || d->rhs_kind == 6 || d->rhs_kind == 8) return bad("unknown rhs_kind");
+  // rhs_kind", so the Kuramoto system took 7 and the double pendulum 9; tests/dpend_host_driver.cpp pins 10 likewise, so CVS took 11
+  if (d->rhs_kind < 0 || d->rhs_kind > LDE_RHS_CVS || d->rhs_kind == 6 || d->rhs_kind == 8 || d->rhs_kind == 10) return bad("unknown rhs_kind");
   if (d->state_dim < 1 || d->param_dim < 0 || d->augment_dim < 0) return bad("bad dims");
   if (has_pend(*d) && (d->state_dim != 2 || d->param_dim != 1 || d->augment_dim != 0))
     return bad("pendulum RHS needs state_dim=2, param_dim=1, augment_dim=0");
@@ -74,6 +81,8 @@ static int validate(const lde_problem_desc* d, std::string* why) {
     return bad("LDE_RHS_KURAMOTO needs state_dim=N with 2 <= N <= 7, param_dim=N+1, augment_dim=0");
   if (is_dpend(*d) && (d->state_dim != DPEND_D || d->param_dim != DPEND_P || d->augment_dim != 0))
     return bad("LDE_RHS_DOUBLE_PENDULUM needs state_dim=4, param_dim=4, augment_dim=0");
+  if (is_cvs(*d) && (d->state_dim != CVS_D || d->param_dim != CVS_P || d->augment_dim != 0))
+    return bad("LDE_RHS_CVS needs state_dim=4, param_dim=2, augment_dim=0");
   if (d->rhs_kind == LDE_RHS_MLP && d->param_dim != 0) return bad("MLP RHS takes no per-trajectory parameters");
   if (has_mlp(*d)) {
     if (d->n_layers < 1 || d->n_layers > LDE_MAX_LAYERS) return bad("n_layers out of range");
@@ -87,6 +96,7 @@ static int validate(const lde_problem_desc* d, std::string* why) {
   if (is_lv(*d) && d->n_layers != 0) return bad("LDE_RHS_LOTKA_VOLTERRA is analytic: n_layers must be 0");
   if (is_kuramoto(*d) && d->n_layers != 0) return bad("LDE_RHS_KURAMOTO is analytic: n_layers must be 0");
   if (is_dpend(*d) && d->n_layers != 0) return bad("LDE_RHS_DOUBLE_PENDULUM is analytic: n_layers must be 0");
+  if (is_cvs(*d) && d->n_layers != 0) return bad("LDE_RHS_CVS is analytic: n_layers must be 0");
   if (d->solver != LDE_SOLVER_TSIT5 && d->solver != LDE_SOLVER_RK4 && !sde_solver(d->solver)) return bad("unknown solver");
   if (d->batching != LDE_BATCH_PER_TRAJECTORY && d->batching != LDE_BATCH_COUPLED && d->batching != LDE_BATCH_COUPLED_GLOBAL)
     return bad("unknown batching");
@@ -127,6 +137,11 @@ static int validate(const lde_problem_desc* d, std::string* why) {
     if (d->batching != LDE_BATCH_PER_TRAJECTORY) return unsupported("LDE_RHS_DOUBLE_PENDULUM: no coupled solve; LDE_BATCH_PER_TRAJECTORY only");
     if (d->sensealg != LDE_SENSE_FORWARD_DUAL)
       return unsupported("LDE_RHS_DOUBLE_PENDULUM: only the solve on dual numbers exists for this system (no discrete sweep, no continuous adjoint); use LDE_SENSE_FORWARD_DUAL");
+  }
+  if (is_cvs(*d)) {   // … and the cardiovascular system, their third
+    if (d->batching != LDE_BATCH_PER_TRAJECTORY) return unsupported("LDE_RHS_CVS: no coupled solve; LDE_BATCH_PER_TRAJECTORY only");
+    if (d->sensealg != LDE_SENSE_FORWARD_DUAL)
+      return unsupported("LDE_RHS_CVS: only the solve on dual numbers exists for this system (no discrete sweep, no continuous adjoint); use LDE_SENSE_FORWARD_DUAL");
   }
   if (d->solver == LDE_SOLVER_RK4 && d->adaptive) {
     if (why) *why = "RK4 is fixed-step only here: pass adaptive=0, dt=h";
@@ -179,9 +194,9 @@ static StepRec rec_view(const lde_problem_desc& d, void* base, int B, int cap, b
 // LDE_SENSE_FORWARD_DUAL's record (include/lde.h: "the dual record"): n [B] | J [T][2][NP][B] f32 | with the step trace t, dt [cap][B] f64;
 // `np` = NP = D + P partials per component — 3 for the pendulums (the four-argument forms), 6 for Lotka–Volterra (dual_partials).
 // J first: its place depends on B alone, so the pullback (which reads n and J) finds it whether or not the forward traced its steps.
-// The record of the lane-per-direction kernels' systems is its own (include/lde.h: "the Kuramoto system", "the double pendulum"): n [B] |
+// The record of the lane-per-direction kernels' systems is its own (include/lde.h: "the Kuramoto system", "the double pendulum", "the cardiovascular system"): n [B] |
 // J [T][D][B][G] f32 | t, dt — a trajectory's G lanes (dir_group_width) fastest, so D·G floats per (save time, trajectory) where the
-// two-state systems have 2·NP; `np` is then D·G/2 (G is even; 16 for the double pendulum), and every size and offset below serves these
+// two-state systems have 2·NP; `np` is then D·G/2 (G is even; 16 for the double pendulum and for CVS), and every size and offset below serves these
 // kinds unchanged.
 static int dual_partials(const lde_problem_desc& d) {
   if (is_dir(d)) return d.state_dim * dir_group_width(d) / 2;   // (0 where the kind does not serve state_dim)
@@ -361,6 +376,20 @@ static int dir_dispatch_n(const lde_problem_desc& d, F&& f) {
 template <class F>
 static int dir_dispatch(const lde_problem_desc& d, F&& f) {
   return dir_dispatch_n(d, [&](auto kind, auto n) -> int {
+    return lv_dispatch(d.solver, d.adaptive != 0, [&](auto S) -> int { return f(kind, n, S); });
+  });
+}
+// … and with (LDE_RHS_CVS, 4), the third system: what the launchers call. A layer of its own and not one more branch above, because
+// tests/dpend_host_driver.cpp hands the two-system forms a functor that static_asserts the pairs it may be instantiated with — a third
+// pair there would stop that driver from compiling, and it stays as it is.
+template <class F>
+static int dir_system_dispatch_n(const lde_problem_desc& d, F&& f) {
+  if (is_cvs(d)) return d.state_dim == CVS_D ? f(std::integral_constant<int, LDE_RHS_CVS>{}, std::integral_constant<int, CVS_D>{}) : (int)LDE_ERR_UNSUPPORTED;
+  return dir_dispatch_n(d, f);
+}
+template <class F>
+static int dir_system_dispatch(const lde_problem_desc& d, F&& f) {
+  return dir_system_dispatch_n(d, [&](auto kind, auto n) -> int {
     return lv_dispatch(d.solver, d.adaptive != 0, [&](auto S) -> int { return f(kind, n, S); });
   });
 }
