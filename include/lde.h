@@ -69,6 +69,12 @@ enum lde_rhs_kind {
                                      param_dim 2) — the GOKU-net paper's third benchmark, its form as recalled (unpinned).
                                      LDE_SENSE_FORWARD_DUAL only; see "the cardiovascular system" below. 11, not 10: the value 10, like 6 and
                                      8, is no right-hand side and stays refused as "unknown rhs_kind" (the double pendulum's host tests pin it) */
+  LDE_RHS_STUART_LANDAU     = 13, /* N Stuart–Landau (Hopf normal form) oscillators with uniform all-to-all diffusive coupling, N = 1 … 3:
+                                     z = (x₁ … x_N, y₁ … y_N), θ = (a₁ … a_N, ω₁ … ω_N, G) per trajectory (state_dim 2N, param_dim 2N + 1) — the
+                                     latent system of GOKU-UI, its form as recalled (unpinned). LDE_SENSE_FORWARD_DUAL only; deterministic
+                                     (Tsit5, RK4) or stochastic (LDE_SOLVER_EM / LDE_SOLVER_EULER_HEUN, additive noise): see "the Stuart–Landau
+                                     network" below. 13, not 12: the value 12, like 6, 8 and 10, is no right-hand side and stays refused as
+                                     "unknown rhs_kind" (the cardiovascular system's host tests pin it) */
   LDE_RHS_LOTKA_VOLTERRA    = 5   /* Lotka–Volterra: dx = αx − βxy, dy = −γy + δxy, θ = (α, β, γ, δ) = p[1:4] per trajectory (state_dim 2,
                                      param_dim 4). The first right-hand side with more than one parameter — the reference's `diffeq` plug-in is
                                      "any Julia function" [REF src/models/GOKU.jl:98-130]; this one has no file of its own there.
@@ -78,9 +84,9 @@ enum lde_rhs_kind {
 enum lde_solver {
   LDE_SOLVER_TSIT5 = 0,           /* Tsit5()  [REF pendulum.jl:11], [REF nODE.jl:15] */
   LDE_SOLVER_RK4   = 1,           /* RK4(), fixed step only (adaptive=0, dt=h) — BASELINE.json configs[1] */
-  LDE_SOLVER_EM    = 2,           /* StochasticDiffEq's EM() (Euler–Maruyama), fixed step: y' = y + h·f(y) + ΔW. LDE_RHS_SPENDULUM only */
+  LDE_SOLVER_EM    = 2,           /* StochasticDiffEq's EM() (Euler–Maruyama), fixed step: y' = y + h·f(y) + ΔW. LDE_RHS_SPENDULUM and LDE_RHS_STUART_LANDAU */
   LDE_SOLVER_EULER_HEUN = 3       /* StochasticDiffEq's EulerHeun(), fixed step: ȳ = y + h·f(y) + ΔW, y' = y + (h/2)·(f(y) + f(ȳ)) + ΔW
-                                     (the same ΔW in both lines). LDE_RHS_SPENDULUM only */
+                                     (the same ΔW in both lines). LDE_RHS_SPENDULUM and LDE_RHS_STUART_LANDAU */
 };
 
 enum lde_batching {
@@ -131,7 +137,9 @@ enum lde_sensealg {
                                            LDE_ERR_UNSUPPORTED (lde_desc_error names the missing piece). Opt-in: lde_problem_desc_default keeps
                                            LDE_SENSE_DISCRETE. LDE_RHS_LOTKA_VOLTERRA runs the same solve with NP = 6 partials per component,
                                            (x₀, y₀, α, β, γ, δ): "the Lotka–Volterra system" below. LDE_RHS_KURAMOTO runs it for N states with
-                                           NP = 2N + 1 partials per component, a lane per partial direction: "the Kuramoto system" below. */
+                                           NP = 2N + 1 partials per component, a lane per partial direction: "the Kuramoto system" below — as do
+                                           LDE_RHS_DOUBLE_PENDULUM, LDE_RHS_CVS and LDE_RHS_STUART_LANDAU, the last one also under its two
+                                           stochastic steppers: "the Stuart–Landau network" below. */
 };
 
 enum lde_activation { LDE_ACT_RELU = 0, LDE_ACT_TANH = 1 };
@@ -259,7 +267,7 @@ int lde_set_weights_device(lde_handle* h, const float* flat_dev, int64_t n, void
  * NULL). May be called between solves; `epoch_dev` (device int64, or NULL) is read by the kernel at run time, as lde_randn reads its
  * own: inside a captured step it is the optimiser's step count, and every replay draws fresh noise. A batch sharded by trajectory passes
  * each shard's first global trajectory index as `first_trajectory`: sharded and unsharded solves then draw the same path.
- * LDE_ERR_UNSUPPORTED on a handle of another right-hand side. */
+ * LDE_ERR_UNSUPPORTED on a handle of another right-hand side (LDE_RHS_STUART_LANDAU takes it too: "the Stuart–Landau network" below). */
 int lde_set_noise(lde_handle* h, uint64_t seed, uint64_t offset, uint64_t first_trajectory, const int64_t* epoch_dev);
 
 /* ---- the Lotka–Volterra system (LDE_RHS_LOTKA_VOLTERRA): dx = αx − βxy, dy = −γy + δxy ----
@@ -365,6 +373,48 @@ int lde_set_noise(lde_handle* h, uint64_t seed, uint64_t offset, uint64_t first_
  * records are. Failure semantics (NaN ẑ block, zero J, n = −retcode, zero gradient) and statistics are those of the pendulum's dual solve.
  * lde_last_kernel: "k_forward_dual_dir" / "k_adjoint_dual_dir" (labels of the path, shared with the Kuramoto system). */
 
+/* ---- the Stuart–Landau network (LDE_RHS_STUART_LANDAU = 13): N Hopf normal-form oscillators, N = 1 … 3 ----
+ * The latent system of GOKU-UI (the successor model of the reference, by the same author). STATED DEVIATION: neither that paper nor its code
+ * was at hand when this was written — the form below is recalled from the literature (Deco et al.'s whole-brain Hopf model, with uniform
+ * all-to-all coupling), unpinned, as the cardiovascular system's is. The text here is the contract.
+ *     r_j² = x_j² + y_j²,   x̄ = (1/N) Σ x_i,   ȳ = (1/N) Σ y_i
+ *     dx_j = (a_j − r_j²) x_j − ω_j y_j + G (x̄ − x_j)
+ *     dy_j = (a_j − r_j²) y_j + ω_j x_j + G (ȳ − y_j)
+ * a_j is the bifurcation parameter and may be zero or negative (a < 0: a damped focus, a > 0: a limit cycle of radius √a); G may be 0. The
+ * system is polynomial: no transcendental function, no angle to anchor.
+ * State z = (x₁ … x_N, y₁ … y_N): z0, dz0 [2N×B], trajectory b's values at z0[2N·b …]; z_out, dz_out [T×B×2N]; θ = (a₁ … a_N, ω₁ … ω_N, G):
+ * theta, dtheta [(2N+1)×B], trajectory b's values at theta[(2N+1)·b …].
+ * The Jacobian, in blocks: ∂ẋ_j/∂x_j = a_j − r_j² − 2x_j² − G(1 − 1/N), ∂ẋ_j/∂y_j = −2x_jy_j − ω_j, ∂ẏ_j/∂x_j = −2x_jy_j + ω_j,
+ * ∂ẏ_j/∂y_j = a_j − r_j² − 2y_j² − G(1 − 1/N); G/N off the diagonal inside the x block and inside the y block; nothing else. The forcing
+ * columns: ∂f/∂a_j = (x_j, y_j) on oscillator j, ∂f/∂ω_j = (−y_j, x_j) on oscillator j, ∂f/∂G = (x̄ − x, ȳ − y).
+ * Partial directions q = (ẑ₀ (2N), a (N), ω (N), G): NP = 4N + 1 — 5, 9, 13 for N = 1, 2, 3 — on the lane-per-direction kernels: a group of
+ * G_lanes = 8 (N = 1; three pad lanes) or 16 (N = 2: seven pad lanes; N = 3: three) lanes per trajectory. The dual record is theirs
+ * (A(x) = x rounded up to a multiple of 256 bytes; D = 2N):
+ *     n  int32 [B]                at 0
+ *     J  float [T][D][B][G_lanes] at A(4B)                  J[j][i][b][q] = ∂ẑ_i(t_j)/∂q_q: element ((j·D + i)·B + b)·G_lanes + q; pad lanes: 0
+ *     t, dt double [cap][B]       at A(4B) + A(4·D·G_lanes·TB)   option "step_trace" = 1 only
+ * Served: state_dim = 2N ∈ {2, 4, 6}, param_dim = 2N + 1, augment_dim = 0, n_layers = 0 (anything else: LDE_ERR_INVALID_ARG, before any solver
+ * check), LDE_BATCH_PER_TRAJECTORY, sensealg LDE_SENSE_FORWARD_DUAL, and
+ *   * deterministic: LDE_SOLVER_TSIT5 adaptive or fixed-step, LDE_SOLVER_RK4 fixed-step — the Kuramoto system's kernels over this system, all
+ *     NP partials in every norm of the step control, the RMS over the 2N components. lde_last_kernel: "k_forward_dual_dir" / "k_adjoint_dual_dir";
+ *   * stochastic: LDE_SOLVER_EM or LDE_SOLVER_EULER_HEUN with adaptive = 0 and a finite dt > 0 (the conditions of LDE_RHS_SPENDULUM) —
+ *     dz = f(z) dt + σ dW, diagonal additive noise with ONE σ for all 2N components: option "noise_sigma" (default 0.01, the pendulum's; finite
+ *     and ≥ 0, else LDE_ERR_INVALID_ARG; 0 gives the deterministic scheme on the same substeps; LDE_ERR_UNSUPPORTED on a handle of another
+ *     kind). The substep rule, the failure semantics and the statistics are the stochastic pendulum's ("the substep rule" above), with
+ *     ΔW_c = (σ·sqrtf(h))·ξ_c, one draw per substep, the same ΔW in both lines of EulerHeun. The tangents get no noise: the gradient is the exact
+ *     derivative of the scheme along the drawn path, and lde_adjoint contracts the dual record the forward leaves.
+ *     lde_last_kernel: "k_forward_sde_dir" / "k_adjoint_dual_dir".
+ * Refused with LDE_ERR_UNSUPPORTED, lde_desc_error naming the missing piece: another sensealg ("… use LDE_SENSE_FORWARD_DUAL"),
+ * LDE_BATCH_COUPLED, adaptive RK4 (its own text), a stochastic stepper with adaptive = 1 or without a finite dt > 0.
+ * The noise of this kind — a pure function of (seed, offset + *epoch_dev, first_trajectory + b, substep s, component c), whatever the launch
+ * geometry, a shard's place in the batch or a graph replay; lde_set_noise is accepted on every handle of this kind: component c
+ * (c = 0 … 2N − 1 in the order of z) takes output word c mod 4 of Philox block ⌊c/4⌋ of (trajectory, substep); words 0, 1 and words 2, 3 of a
+ * block are Box–Muller pairs by lde_randn's map (the cosine branch on the even word). Block 0 has exactly the stochastic pendulum's counter
+ * (first_trajectory + b, s, low word of off, high word of off) and key (low word of seed, high word of seed): for N = 1, (ξ_x, ξ_y) are the
+ * stochastic pendulum's (ξ_x, ξ_v) of the same arguments. Block 1 (N = 3: components 4 and 5) has the same counter and the key with the top
+ * bit of its high word flipped — all 128 counter bits and 64 key bits being spoken for, block 1 of seed S is block 0 of seed S xor 2⁶³, so a
+ * caller should not run the two seeds S and S xor 2⁶³ side by side. */
+
 /* Pre-size the handle's workspace for batches up to B and T save points (so that later
  * lde_forward/lde_adjoint calls allocate nothing and can be captured in a hipGraph). */
 int lde_reserve(lde_handle* h, int B, int T);
@@ -450,7 +500,7 @@ int lde_set_global_sum_peers(lde_handle* h, int rank, int nranks, void* const* m
  *                                                           LDE_RHS_LOTKA_VOLTERRA
  *     t  double [cap][B]          at A(4B) + A(4·2·NP·TB)   option "step_trace" = 1 only: start time of accepted step s of trajectory b at s·B + b
  *     dt double [cap][B]          at … + A(8·cap·B)         … and its size; cap = lde_step_record_capacity(h, T)
- * (Pendulums: J [T][2][3][B], the trace at A(4B) + A(24TB), as before. LDE_RHS_KURAMOTO: J [T][N][B][G], "the Kuramoto system" above; LDE_RHS_DOUBLE_PENDULUM and LDE_RHS_CVS: J [T][4][B][8], "the double pendulum" and "the cardiovascular system" above.) J of a failed trajectory is zero. With "step_trace" = 1 lde_get_step_record(h, 0, …) returns the accepted steps (what a checker replays). */
+ * (Pendulums: J [T][2][3][B], the trace at A(4B) + A(24TB), as before. LDE_RHS_KURAMOTO: J [T][N][B][G], "the Kuramoto system" above; LDE_RHS_DOUBLE_PENDULUM and LDE_RHS_CVS: J [T][4][B][8], "the double pendulum" and "the cardiovascular system" above.; LDE_RHS_STUART_LANDAU: J [T][2N][B][8 or 16], "the Stuart–Landau network" above.) J of a failed trajectory is zero. With "step_trace" = 1 lde_get_step_record(h, 0, …) returns the accepted steps (what a checker replays). */
 int64_t lde_step_record_bytes(const lde_handle* h, int B, int T);
 int lde_set_step_record(lde_handle* h, void* rec_dev, int64_t bytes);
 /* Did the record hold the solve? lde_step_record_capacity(h, T) = the accepted steps per sequence a record made now would hold;
@@ -481,6 +531,8 @@ int lde_get_step_record(lde_handle* h, int which, double* t_host, double* dt_hos
  * all ranks should be warmed up before the first exchanging call). The library reads NO environment variable for any of this.
  * lde_get_option also answers the read-only "adjoint_family": the kernel family the last lde_adjoint ran on an MLP right-hand side
  * (0 tiles, 1 k_mlp64, 2 k_mlpb, 3 k_mlpc, 4 k_mlpw, 5 k_mlpv, 6 k_mlp4; −1 none) — what bench.py prices its roofline with.
+ * "noise_sigma" (LDE_RHS_STUART_LANDAU only; the one option that is not an integer): the σ of the stochastic solve's additive noise, default
+ * 0.01; a value that is not finite or is negative: LDE_ERR_INVALID_ARG; a handle of another kind: LDE_ERR_UNSUPPORTED (set and get).
  * Unknown key: LDE_ERR_INVALID_ARG. */
 int lde_set_option(lde_handle* h, const char* key, double value);
 int lde_get_option(const lde_handle* h, const char* key, double* value);
@@ -495,7 +547,8 @@ const char* lde_last_error(const lde_handle* h);
  * Under LDE_SENSE_FORWARD_DUAL the strings are labels of the path taken, not symbol names — the deterministic systems run one kernel
  * template over the system: "k_pend_forward_dual" / "k_pend_adjoint_dual" (the pendulums), "k_lv_forward_dual" / "k_lv_adjoint_dual"
  * (Lotka–Volterra), "k_pend_forward_sde" / "k_pend_adjoint_dual" (the stochastic pendulum); the Kuramoto system runs the
- * lane-per-direction kernels: "k_forward_dual_dir" / "k_adjoint_dual_dir". */
+ * lane-per-direction kernels: "k_forward_dual_dir" / "k_adjoint_dual_dir", as do the double pendulum, the cardiovascular system and the
+ * deterministic Stuart–Landau network; its stochastic solve is "k_forward_sde_dir" / "k_adjoint_dual_dir". */
 const char* lde_last_kernel(const lde_handle* h, int which);
 
 

@@ -80,6 +80,7 @@ solver_code(::EulerHeun) = Int32(3)                                     # LDE_SO
 const LDE_RHS_SPENDULUM = Int32(4)
 const LDE_RHS_KURAMOTO = Int32(7)   # N phase oscillators, state_dim = N (2 … 7), param_dim = N + 1; LDE_SENSE_FORWARD_DUAL only (6 is no right-hand side)
 const LDE_RHS_DOUBLE_PENDULUM = Int32(9)   # z = (θ₁, θ₂, ω₁, ω₂), p = (L₁, L₂, m₁, m₂): state_dim = 4, param_dim = 4; LDE_SENSE_FORWARD_DUAL only (8 is no right-hand side)
+const LDE_RHS_STUART_LANDAU = Int32(13)   # N = 1 … 3 Stuart–Landau oscillators, z = (x…, y…), p = (a…, ω…, G): state_dim = 2N, param_dim = 2N + 1; LDE_SENSE_FORWARD_DUAL only, Tsit5 / RK4 or EM / EulerHeun with option "noise_sigma" (12 is no right-hand side)
 const LDE_RHS_CVS = Int32(11)   # the cardiovascular system, z = (p_a/100, p_v/10, s, sv/100), p = (i_ext, r_mod): state_dim = 4, param_dim = 2; LDE_SENSE_FORWARD_DUAL only (10 is no right-hand side)
 
 # one handle per `diffeq` struct, built lazily from its fields (solver, sensealg, kwargs...)  [REF GOKU.jl:105-108]. The analytic right-hand

@@ -5,7 +5,7 @@ Layout:
   csrc/      HIP kernels (gfx950) + the C ABI of include/lde.h  → liblde.so
   _lib.py    ctypes binding of liblde.so (no fallback: raises if the library is missing)
   api.py     host-side mirror of the reference interface: Pendulum / Pendulum_friction / SPendulum / LotkaVolterra / Kuramoto / DoublePendulum /
-             CVS / NODE,
+             CVS / StuartLandau / NODE,
              GOKU_basic / LatentODE, Decoder, diffeq_layer, transform_after_diffeq
   chain.py   Dense / SkipConnection / Chain, apply_latent_out, apply_reconstructor (the dense chains either side of the solve)
   recurrent.py  RNN / LSTM / GRU / Recurrent, Encoder, apply_feature_extractor / _pattern_extractor / _latent_in, sample

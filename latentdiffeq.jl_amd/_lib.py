@@ -19,6 +19,7 @@ RHS_PENDULUM, RHS_PENDULUM_FRICTION, RHS_MLP, RHS_PENDULUM_PLUS_MLP, RHS_SPENDUL
 RHS_KURAMOTO = 7   # (6 is no right-hand side: include/lde.h)
 RHS_DOUBLE_PENDULUM = 9   # (nor is 8)
 RHS_CVS = 11   # (nor is 10)
+RHS_STUART_LANDAU = 13   # (nor is 12)
 SOLVER_TSIT5, SOLVER_RK4, SOLVER_EM, SOLVER_EULER_HEUN = 0, 1, 2, 3
 BATCH_PER_TRAJECTORY, BATCH_COUPLED, BATCH_COUPLED_GLOBAL = 0, 1, 2
 SENSE_BACKSOLVE_CHECKPOINTED, SENSE_BACKSOLVE, SENSE_PARALLEL_CHECKPOINTED, SENSE_DISCRETE, SENSE_FORWARD_DUAL = 0, 1, 2, 3, 4

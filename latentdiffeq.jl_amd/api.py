@@ -13,6 +13,7 @@ include/lde.h. PyTorch is used only for device memory, streams and autograd plum
     (… with more than two states and transform_after_diffeq)           Kuramoto(N=3, solver=Tsit5(), **kwargs)  — LDE_RHS_KURAMOTO
     (… the GOKU-net paper's second benchmark: four states, four parameters)  DoublePendulum(solver=Tsit5(), **kwargs)  — LDE_RHS_DOUBLE_PENDULUM
     (… its third: four states, two parameters that may be zero or negative)  CVS(solver=Tsit5(), **kwargs)  — LDE_RHS_CVS
+    (… GOKU-UI's latent system, deterministic or under additive noise)  StuartLandau(N=2, solver=Tsit5(), sigma=, dt=, seed=, **kwargs)  — LDE_RHS_STUART_LANDAU
     NODE(latent_dim_in; hidden_dim, augment_dim, kwargs...) [REF nODE.jl:3-32]   NODE(latent_dim_in, hidden_dim=, augment_dim=, **kwargs)
     GOKU_basic(), LatentODE()                 [REF GOKU.jl:6-7], [REF LatentODE.jl:6]   same
     Decoder(model_type, (latent_out, diffeq, reconstructor)) [REF LatentDiffEqModel.jl:79-99]   same
@@ -48,12 +49,12 @@ class RK4:
 
 
 class EM:
-    """StochasticDiffEq's EM() (Euler–Maruyama), fixed step: y' = y + h·f(y) + ΔW. SPendulum only."""
+    """StochasticDiffEq's EM() (Euler–Maruyama), fixed step: y' = y + h·f(y) + ΔW. SPendulum and StuartLandau."""
     code = L.SOLVER_EM
 
 
 class EulerHeun:
-    """StochasticDiffEq's EulerHeun(), fixed step: ȳ = y + h·f(y) + ΔW, y' = y + (h/2)·(f(y) + f(ȳ)) + ΔW. SPendulum only (its default:
+    """StochasticDiffEq's EulerHeun(), fixed step: ȳ = y + h·f(y) + ΔW, y' = y + (h/2)·(f(y) + f(ȳ)) + ΔW. SPendulum and StuartLandau (SPendulum's default:
     with σ = 0.01 the drift's order limits accuracy, not the noise's — include/lde.h)."""
     code = L.SOLVER_EULER_HEUN
 
@@ -104,7 +105,7 @@ class ForwardDiffSensitivity(DiscreteSensitivity):
 
     `dual_norm=True` (opt-in; LDE_SENSE_FORWARD_DUAL): the solve on dual numbers as upstream runs it during training — the error norm sees
     the partials, so the accepted steps are the reference's training-time ones, not the primal solve's. The forward pass carries the
-    Jacobians ∂ẑ(t_j)/∂(ẑ₀, θ̂) and the pullback contracts them. Analytic right-hand sides (Pendulum, Pendulum_friction, LotkaVolterra, Kuramoto, DoublePendulum, CVS) only."""
+    Jacobians ∂ẑ(t_j)/∂(ẑ₀, θ̂) and the pullback contracts them. Analytic right-hand sides (Pendulum, Pendulum_friction, LotkaVolterra, Kuramoto, DoublePendulum, CVS, StuartLandau) only."""
 
     def __init__(self, exact: bool = True, dual_norm: bool = False):
         self.dual_norm = bool(dual_norm)
@@ -375,6 +376,64 @@ class CVS(_PhysicsDiffEq):
             d = _make_desc(self._rhs_kind, 4, 2, 0, (), self.solver, self.sensealg, L.BATCH_PER_TRAJECTORY, self.kwargs)
             self._handle = _Handle(d)
         return self._handle
+
+
+class StuartLandau(_PhysicsDiffEq):
+    """N Stuart–Landau (Hopf normal form) oscillators with uniform all-to-all diffusive coupling, N = 1 … 3 — LDE_RHS_STUART_LANDAU
+    (include/lde.h: "the Stuart–Landau network"), GOKU-UI's latent system; its form is stated there as recalled from the literature,
+    unpinned: dx_j = (a_j − r_j²) x_j − ω_j y_j + G (x̄ − x_j), dy_j = (a_j − r_j²) y_j + ω_j x_j + G (ȳ − y_j). z = (x₁ … x_N, y₁ … y_N),
+    p = (a₁ … a_N, ω₁ … ω_N, G): `prob.u0` has 2N entries and `prob.p` 2N + 1, so `default_layers` builds a 2N-wide `lo_z₀` and a
+    (2N+1)-wide `lo_θ`; diffeq_layer takes ẑ₀ [2N, B] and θ̂ [2N+1, B] and autograd returns gradients of those shapes.
+    `transform_after_diffeq` is the identity.
+
+    Build the heads with `default_layers(..., theta_activation="identity")`: a_j is the bifurcation parameter and both of its signs are
+    legitimate (a < 0 a damped focus, a > 0 a limit cycle), and G may be 0 — which the default softplus head cannot reach.
+
+    Served on the dual-number path only (`ForwardDiffSensitivity(dual_norm=True)`, LDE_SENSE_FORWARD_DUAL; another sensealg is refused by
+    the library, with its text), on the lane-per-direction kernels, in two ways:
+      * `Tsit5()` (the default; adaptive or fixed-step) or `RK4()` (fixed-step): a deterministic plug-in like CVS;
+      * `EM()` or `EulerHeun()`: stochastic, dz = f(z) dt + σ dW with diagonal additive noise of one `sigma` (option "noise_sigma") at the
+        fixed step `dt`, and it behaves like SPendulum: the noise is a pure function of (seed, offset, trajectory, substep, component),
+        every forward call advances `offset` by one, `reseed(seed)` starts the sequence again, `epoch` is a device int64 tensor the kernel
+        adds to the offset at run time, `first_trajectory` the global index of this call's first trajectory
+        (dist.diffeq_layer_sharded sets it). The gradient is the exact derivative of the scheme along the drawn path.
+    `dt` is the stochastic solvers' fixed step (default 0.05); with a deterministic solver it is the usual solve kwarg and has no default.
+    `sigma`, `seed` and `epoch` are read by the stochastic solvers only."""
+    _rhs_kind = L.RHS_STUART_LANDAU
+
+    def __init__(self, N: int = 2, solver=None, sensalg=None, sensealg=None, sigma: float = 0.01, dt: Optional[float] = None, seed: int = 0,
+                 epoch=None, **kwargs):
+        sa = sensealg if sensealg is not None else sensalg
+        self.stochastic = isinstance(solver, (EM, EulerHeun))
+        if self.stochastic:
+            kwargs.setdefault("adaptive", False)
+            kwargs["dt"] = 0.05 if dt is None else dt
+        elif dt is not None:              # a deterministic solver's `dt` is the solve kwarg it always was (RK4's step, Tsit5's first step)
+            kwargs["dt"] = dt
+        super().__init__(solver=solver, sensealg=sa if sa is not None else ForwardDiffSensitivity(dual_norm=True), **kwargs)
+        self.N = int(N)
+        self.sigma = float(sigma)
+        self.prob = _ODEProblemStub(np.ones(2 * self.N, np.float32), np.ones(2 * self.N + 1, np.float32), (0.0, 1.0))
+        self.seed, self.offset, self.first_trajectory, self.epoch = int(seed), 0, 0, epoch
+
+    def reseed(self, seed: int):
+        self.seed, self.offset = int(seed), 0
+
+    def _native(self) -> _Handle:
+        if self._handle is None:
+            d = _make_desc(self._rhs_kind, 2 * self.N, 2 * self.N + 1, 0, (), self.solver, self.sensealg, L.BATCH_PER_TRAJECTORY, self.kwargs)
+            self._handle = _Handle(d)
+            L.call("lde_set_option", self._handle.ptr, b"noise_sigma", self.sigma)
+        return self._handle
+
+    def _next_noise(self):
+        """(seed, offset, first_trajectory, epoch tensor) of the forward call being made — the offset then moves on — or None for a
+        deterministic solver."""
+        if not self.stochastic:
+            return None
+        nz = (self.seed, self.offset, int(self.first_trajectory), self.epoch)
+        self.offset += 1
+        return nz
 
 
 def _set_noise(handle: _Handle, nz):

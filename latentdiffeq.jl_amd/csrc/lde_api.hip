@@ -37,6 +37,9 @@ int launch_forward_dual_dir(const lde_problem_desc& d, const float* z0, const fl
                             hipStream_t stream);
 int launch_adjoint_dual_dir(const lde_problem_desc& d, const DualRec& rec, const float* dz_out, int T, int B, float* dz0, float* dtheta,
                             int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
+int launch_forward_sde_dir(const lde_problem_desc& d, const float* z0, const float* theta, const double* ts_dev, const KOpts& o,
+                           const DualRec& rec, const SdeNoise& nz, float sigma, bool over, float* z_out, int32_t* retcode, int32_t* nfe,
+                           int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream);
 int launch_pend_forward_sde(int solver, const float* z0, const float* theta, const double* ts_dev, const KOpts& o, const DualRec& rec,
                             const SdeNoise& nz, bool over, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej,
                             int32_t* ret, hipStream_t stream);
@@ -94,7 +97,8 @@ struct lde_handle {
   int opt_record_capacity = 0;       // 0: automatic
   int opt_step_trace = 0;
   int opt_adjoint_overwrite = 0;
-  lde::SdeNoise noise;               // LDE_RHS_SPENDULUM: what lde_set_noise left for the next lde_forward calls
+  lde::SdeNoise noise;               // LDE_RHS_SPENDULUM, LDE_RHS_STUART_LANDAU: what lde_set_noise left for the next lde_forward calls
+  double noise_sigma = 0.01;         // LDE_RHS_STUART_LANDAU: option "noise_sigma", the σ of the stochastic solve's additive noise
   lde::PendTune pend_tune;           // kernel-choice knobs of the analytic right-hand sides (MLP ones live in the plan)
   const char* last_kernel[2] = {"", ""};   // lde_last_kernel: the solve kernel the last lde_forward / lde_adjoint launched
   std::string err = "";
@@ -423,7 +427,11 @@ int lde_forward(lde_handle* h, const float* z0, const float* theta, const double
       rc = lde::launch_pend_forward_sde(h->d.solver, z0, theta, h->ts_dev, o, r, h->noise, sde_plan(h->d, ts, T).over, z_out, retcode, st[0],
                                         st[1], st[2], st[3], stream);
       h->last_kernel[0] = "k_pend_forward_sde";
-    } else if (is_dir(h->d)) {   // Kuramoto, the double pendulum and CVS: a lane per (trajectory, partial direction) (csrc/lde_dual_dir.hip)
+    } else if (is_dir_sde(h->d)) {   // the Stuart–Landau network under noise: the same frame, its own stepper (csrc/lde_dual_dir.hip)
+      rc = lde::launch_forward_sde_dir(h->d, z0, theta, h->ts_dev, o, r, h->noise, (float)h->noise_sigma, sde_plan(h->d, ts, T).over, z_out,
+                                       retcode, st[0], st[1], st[2], st[3], stream);
+      h->last_kernel[0] = "k_forward_sde_dir";
+    } else if (is_dir(h->d)) {   // Kuramoto, the double pendulum, CVS and the Stuart–Landau network: a lane per (trajectory, partial direction) (csrc/lde_dual_dir.hip)
       rc = lde::launch_forward_dual_dir(h->d, z0, theta, h->ts_dev, o, r, z_out, retcode, st[0], st[1], st[2], st[3], stream);
       h->last_kernel[0] = "k_forward_dual_dir";
     } else {              // the pendulums and Lotka–Volterra: one kernel over the system (csrc/lde_dual.hip)
@@ -533,7 +541,7 @@ int lde_adjoint(lde_handle* h, const float* z_out, const float* theta, const dou
 
 int lde_set_noise(lde_handle* h, uint64_t seed, uint64_t offset, uint64_t first_trajectory, const int64_t* epoch_dev) {
   if (!h) return LDE_ERR_INVALID_ARG;
-  if (!is_sde(h->d)) {
+  if (!is_sde(h->d) && !is_sl(h->d)) {
     h->err = "lde_set_noise: the handle's right-hand side is deterministic (LDE_RHS_SPENDULUM only)";
     return LDE_ERR_UNSUPPORTED;
   }
@@ -708,6 +716,18 @@ static int* option_slot(lde_handle* h, const char* key) {
 }
 int lde_set_option(lde_handle* h, const char* key, double value) {
   if (!h || !key) return LDE_ERR_INVALID_ARG;
+  if (!std::strcmp(key, "noise_sigma")) {   // the one option that is not an integer (include/lde.h: "the Stuart–Landau network")
+    if (!is_sl(h->d)) {
+      h->err = "lde_set_option: noise_sigma: LDE_RHS_STUART_LANDAU only";
+      return LDE_ERR_UNSUPPORTED;
+    }
+    if (!std::isfinite(value) || !(value >= 0)) {
+      h->err = "lde_set_option: noise_sigma must be finite and >= 0";
+      return LDE_ERR_INVALID_ARG;
+    }
+    h->noise_sigma = value;
+    return LDE_OK;
+  }
   int* slot = option_slot(h, key);
   if (!slot || !(value >= ((std::strcmp(key, "pend_lb_hold") && std::strcmp(key, "pend_sh_max_b")) ? 0 : -1)) || value > 2e9) {
     h->err = std::string("lde_set_option: unknown key or value out of range: ") + key;
@@ -720,6 +740,11 @@ int lde_get_option(const lde_handle* h, const char* key, double* value) {
   if (!h || !key || !value) return LDE_ERR_INVALID_ARG;
   if (!std::strcmp(key, "adjoint_family")) {   // read-only: the kernel family the last lde_adjoint ran (MLP right-hand sides; −1: none)
     *value = h->mlp ? (double)lde::mlp_last_family(h->mlp) : -1.0;
+    return LDE_OK;
+  }
+  if (!std::strcmp(key, "noise_sigma")) {
+    if (!is_sl(h->d)) return LDE_ERR_UNSUPPORTED;
+    *value = h->noise_sigma;
     return LDE_OK;
   }
   int* slot = option_slot(const_cast<lde_handle*>(h), key);

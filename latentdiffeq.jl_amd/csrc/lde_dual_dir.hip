@@ -1,7 +1,8 @@
 // lde_dual_dir.hip — LDE_SENSE_FORWARD_DUAL with ONE LANE PER (TRAJECTORY, PARTIAL DIRECTION): the dual-number solve for systems of more than
 // two states, as kernels over a system: LDE_RHS_KURAMOTO (N = 2 … 7 phase oscillators: csrc/lde_kuramoto_dualrhs.h, KuramotoDir<N>),
-// LDE_RHS_DOUBLE_PENDULUM (four states, four parameters: csrc/lde_dpend_dualrhs.h, DoublePendDir) and LDE_RHS_CVS (the cardiovascular
-// system, four states, two parameters: csrc/lde_cvs_dualrhs.h, CvsDir).
+// LDE_RHS_DOUBLE_PENDULUM (four states, four parameters: csrc/lde_dpend_dualrhs.h, DoublePendDir), LDE_RHS_CVS (the cardiovascular
+// system, four states, two parameters: csrc/lde_cvs_dualrhs.h, CvsDir) and LDE_RHS_STUART_LANDAU (N = 1 … 3 Hopf oscillators, 2N states,
+// 2N + 1 parameters: csrc/lde_sl_dualrhs.h, StuartLandauDir<N>) — the last one also under additive noise, by k_forward_sde_dir below.
 //
 // k_forward_dual (csrc/lde_dual.hip) keeps a trajectory's whole dual state, D·(1 + D + P) floats, and Tsit5's seven slopes of it in one lane:
 // 14 floats per vector for Lotka–Volterra, 112 for seven oscillators — it cannot grow in D. Here a trajectory is a GROUP of G consecutive
@@ -39,6 +40,8 @@
 #include "lde_kuramoto_dualrhs.h"
 #include "lde_dpend_dualrhs.h"
 #include "lde_cvs_dualrhs.h"
+#include "lde_sl_dualrhs.h"
+#include "lde_philox.h"
 
 namespace lde {
 
@@ -150,7 +153,7 @@ __device__ __forceinline__ void dir_save(float* z_out, const DualRec& rec, int j
   for (int i = 0; i < D; i++) Jj[(size_t)i * B * G] = u[D + i];
 }
 
-// SYS (csrc/lde_kuramoto_dualrhs.h: KuramotoDir<N>; csrc/lde_dpend_dualrhs.h: DoublePendDir; csrc/lde_cvs_dualrhs.h: CvsDir) supplies D components, NP ≤ G directions, the
+// SYS (csrc/lde_kuramoto_dualrhs.h: KuramotoDir<N>; csrc/lde_dpend_dualrhs.h: DoublePendDir; csrc/lde_cvs_dualrhs.h: CvsDir; csrc/lde_sl_dualrhs.h: StuartLandauDir<N>) supplies D components, NP ≤ G directions, the
 // group width G (8 or 16), DN = 2·D, load(theta, b, q), seed(z0, b, q, y), anchor(y) and operator()(u, du).
 template <class SYS, int SOLVER, bool TS_LDS>
 __global__ void __launch_bounds__(256) k_forward_dual_dir(const float* __restrict__ z0, const float* __restrict__ theta,
@@ -312,8 +315,111 @@ __global__ void __launch_bounds__(256) k_adjoint_dual_dir(DualRec rec, const flo
   }
 }
 
+// ---- the stochastic solve in the same frame: dz = f(z) dt + σ dW, diagonal additive noise with one σ (include/lde.h: "the Stuart–Landau
+// network") — k_pend_forward_sde's stepper (csrc/lde_pend_sde.hip) over a system SYS, a group of G lanes per trajectory. Fixed-step EM() or
+// EulerHeun() on the substeps of lde::sde_substeps, save times hit exactly, one draw per substep shared by both lines of EulerHeun. Lane q
+// carries the D values and its one tangent column; the tangents get no noise — the gradient is the exact derivative of the scheme along the
+// drawn path, and the pullback is k_adjoint_dual_dir on the record this kernel leaves.
+// EVERY lane of a group computes the draw itself, from the same counter by the same instructions: the G copies of z receive the same bits
+// of ΔW and stay the same bits; no lane reads another's. Component c takes word c mod 4 of Philox block ⌊c/4⌋ of (trajectory, substep);
+// words (0, 1) and (2, 3) are Box–Muller pairs. Block 0 has the stochastic pendulum's counter and key; block 1 (D > 4) the same counter and
+// the key with the top bit of its high word flipped. One look per save interval for a non-finite state — a count over the group, so the
+// group decides together. `over`: the host's substep plan is longer than maxiters (lde_host::sde_plan): LDE_RET_MAXITERS, nothing stepped.
+template <class SYS, int SOLVER, bool TS_LDS>
+__global__ void __launch_bounds__(256) k_forward_sde_dir(const float* __restrict__ z0, const float* __restrict__ theta,
+                                                         const double* __restrict__ ts_g, KOpts o, DualRec rec, SdeNoise nz, float sigma, int over,
+                                                         float* __restrict__ z_out, int32_t* __restrict__ retcode, int32_t* __restrict__ st_nfe,
+                                                         int32_t* __restrict__ st_nacc, int32_t* __restrict__ st_nrej,
+                                                         int32_t* __restrict__ st_ret) {
+  constexpr int D = SYS::D, DN = SYS::DN, G = SYS::G;
+  static_assert(DN == 2 * D && SYS::NP <= G && (G == 8 || G == 16) && D % 2 == 0 && D <= 8, "whole Box–Muller pairs, at most two Philox blocks");
+  static_assert(SOLVER == LDE_SOLVER_EM || SOLVER == LDE_SOLVER_EULER_HEUN, "the two stochastic steppers");
+  const int T = o.T, B = o.B;
+  dual_stage_ts<TS_LDS>(ts_g, T);
+  const long long lane = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long b = lane / G;
+  const int q = (int)(lane % G);
+  if (b >= B) return;   // (the whole group: its G lanes share b)
+
+  SYS f = SYS::load(theta, b, q);
+  float y[DN];
+  SYS::seed(z0, b, q, y);
+  dir_save<D, G>(z_out, rec, 0, B, b, q, y);   // ẑ(ts[0]) = ẑ₀
+  int ret = over ? LDE_RET_MAXITERS : LDE_RET_SUCCESS;
+  long long nsub = 0;
+
+  if (!over && T > 1) {
+    // the counter's words that do not change along the solve
+    const unsigned long long off = nz.offset + (nz.epoch_dev ? (unsigned long long)*nz.epoch_dev : 0ull);
+    const unsigned c_traj = (unsigned)(nz.first_trajectory + (unsigned long long)b), c_lo = (unsigned)off, c_hi = (unsigned)(off >> 32);
+    const unsigned k_lo = (unsigned)nz.seed, k_hi = (unsigned)(nz.seed >> 32);
+    unsigned s = 0;   // the substep index of the whole solve: the counter's second word
+    double tprev = o.t_first;
+    for (int j = 1; j < T; j++) {
+      const double tj = dual_ts<TS_LDS>(ts_g, j), Dt = tj - tprev;
+      const int n = sde_substeps(Dt, o.dt_fixed);
+      const double hd = Dt / (double)n;
+      const float h = (float)hd, hh = 0.5f * h, sw = sigma * sqrtf(h);
+      for (int i = 0; i < n; i++, s++) {
+        float dw[D];
+#pragma unroll
+        for (int m = 0; m < (D + 3) / 4; m++) {
+          unsigned w[4];
+          philox4x32_10(c_traj, s, c_lo, c_hi, k_lo, m ? k_hi ^ 0x80000000u : k_hi, w);
+#pragma unroll
+          for (int p = 0; p < 2; p++)
+            if (4 * m + 2 * p < D) {
+              float xa, xb;
+              box_muller_pair(w[2 * p], w[2 * p + 1], xa, xb);
+              dw[4 * m + 2 * p] = sw * xa;
+              dw[4 * m + 2 * p + 1] = sw * xb;
+            }
+        }
+        float k0[DN];
+        f.anchor(y);
+        f(y, k0);
+        if (SOLVER == LDE_SOLVER_EM) {
+#pragma unroll
+          for (int c = 0; c < DN; c++) y[c] += h * k0[c];
+        } else {
+          float yb[DN], k1[DN];
+#pragma unroll
+          for (int c = 0; c < DN; c++) yb[c] = y[c] + h * k0[c];
+#pragma unroll
+          for (int c = 0; c < D; c++) yb[c] += dw[c];
+          f(yb, k1);
+#pragma unroll
+          for (int c = 0; c < DN; c++) y[c] += hh * (k0[c] + k1[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < D; c++) y[c] += dw[c];
+        if (q == 0 && rec.t && nsub + i < rec.cap) {   // option "step_trace": the substep's start time and size
+          rec.t[(size_t)(nsub + i) * B + b] = tprev + (double)i * hd;
+          rec.dt[(size_t)(nsub + i) * B + b] = hd;
+        }
+      }
+      nsub += n;
+      // (a non-finite value never becomes finite again under y ← y + …: one look per save interval sees it; one lane's tangent may overflow
+      // where its neighbours' do not, so the group counts)
+      const float nbad = group_sum<G>(all_finite<DN>(y) ? 0.f : 1.f);
+      if (nbad != 0.f) { ret = LDE_RET_NONFINITE; break; }
+      dir_save<D, G>(z_out, rec, j, B, b, q, y);
+      tprev = tj;
+    }
+  }
+  if (ret != LDE_RET_SUCCESS) {   // failed solve ⇒ NaN block and zero Jacobians (zero gradient) [REF GOKU.jl:114]
+    float u[DN];
+#pragma unroll
+    for (int c = 0; c < DN; c++) u[c] = c < D ? __int_as_float(0x7fc00000) : 0.f;
+    for (int jj = 0; jj < T; jj++) dir_save<D, G>(z_out, rec, jj, B, b, q, u);
+  }
+  constexpr int NFE = SOLVER == LDE_SOLVER_EM ? 1 : 2;
+  const int nacc = (int)(nsub < 0x3fffffffLL ? nsub : 0x3fffffffLL);   // (int32 statistics: a longer solve saturates)
+  if (q == 0) dual_finish((int)b, ret, NFE * nacc, nacc, 0, rec, retcode, st_nfe, st_nacc, st_nrej, st_ret);
+}
+
 // ---- host-side launchers (called from lde_api.hip) -------------------------------------------------------------------------------
-// lde_host::dir_system_dispatch hands out (rhs_kind, state_dim) as constants; this is the system they name
+// lde_host::dir_all_dispatch hands out (rhs_kind, state_dim) as constants; this is the system they name
 template <int KIND, int N>
 struct DirSystem;
 template <int N>
@@ -322,6 +428,8 @@ template <>
 struct DirSystem<LDE_RHS_DOUBLE_PENDULUM, 4> { using type = DoublePendDir; };
 template <>
 struct DirSystem<LDE_RHS_CVS, 4> { using type = CvsDir; };
+template <int D>
+struct DirSystem<LDE_RHS_STUART_LANDAU, D> { using type = StuartLandauDir<D / 2>; };
 
 int launch_forward_dual_dir(const lde_problem_desc& d, const float* z0, const float* theta, const double* ts_dev, const KOpts& o,
                             const DualRec& rec, float* z_out, int32_t* retcode, int32_t* nfe, int32_t* nacc, int32_t* nrej, int32_t* ret,
@@ -330,7 +438,7 @@ int launch_forward_dual_dir(const lde_problem_desc& d, const float* z0, const fl
   const int64_t grid = lde_host::dir_grid(d, o.B);
   if (grid < 1 || grid > 0x7fffffff) return LDE_ERR_INVALID_ARG;
   const size_t shm = o.T <= DUAL_TS_LDS_MAX ? (size_t)o.T * sizeof(double) : 0;
-  const int rc = lde_host::dir_system_dispatch(d, [&](auto kind, auto n, auto S) -> int {
+  const int rc = lde_host::dir_all_dispatch(d, [&](auto kind, auto n, auto S) -> int {
     using SYS = typename DirSystem<kind, n>::type;
     static_assert(SYS::D == n && SYS::G == lde_host::dir_group_width(kind, n) && SYS::NP == lde_host::dir_partials(kind, n), "the host's shape of the launch is the system's");
     if (shm)
@@ -349,10 +457,32 @@ int launch_adjoint_dual_dir(const lde_problem_desc& d, const DualRec& rec, const
   const int block = lde_host::dir_block(d, B);
   const int64_t grid = lde_host::dir_grid(d, B);
   if (grid < 1 || grid > 0x7fffffff) return LDE_ERR_INVALID_ARG;
-  const int rc = lde_host::dir_system_dispatch_n(d, [&](auto kind, auto n) -> int {
+  const int rc = lde_host::dir_all_dispatch_n(d, [&](auto kind, auto n) -> int {
     constexpr int NP = lde_host::dir_partials(kind, n), G = lde_host::dir_group_width(kind, n);
     hipLaunchKernelGGL((k_adjoint_dual_dir<n, NP, G>), dim3((unsigned)grid), dim3(block), 0, stream, rec, dz_out, T, B, dz0, dtheta, nfe, nacc,
                        nrej, ret);
+    return LDE_OK;
+  });
+  return rc != LDE_OK ? rc : hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;
+}
+
+// the stochastic solve: lde_host::dir_sde_dispatch hands out the Stuart–Landau network's D and the two solvers validate() admits for it
+int launch_forward_sde_dir(const lde_problem_desc& d, const float* z0, const float* theta, const double* ts_dev, const KOpts& o,
+                           const DualRec& rec, const SdeNoise& nz, float sigma, bool over, float* z_out, int32_t* retcode, int32_t* nfe,
+                           int32_t* nacc, int32_t* nrej, int32_t* ret, hipStream_t stream) {
+  const int block = lde_host::dir_block(d, o.B);
+  const int64_t grid = lde_host::dir_grid(d, o.B);
+  if (grid < 1 || grid > 0x7fffffff) return LDE_ERR_INVALID_ARG;
+  const size_t shm = o.T <= DUAL_TS_LDS_MAX ? (size_t)o.T * sizeof(double) : 0;
+  const int rc = lde_host::dir_sde_dispatch(d, [&](auto n, auto S) -> int {
+    using SYS = typename DirSystem<LDE_RHS_STUART_LANDAU, n>::type;
+    static_assert(SYS::D == n && SYS::G == lde_host::dir_group_width(LDE_RHS_STUART_LANDAU, n) && SYS::NP == lde_host::dir_partials(LDE_RHS_STUART_LANDAU, n), "the host's shape of the launch is the system's");
+    if (shm)
+      hipLaunchKernelGGL((k_forward_sde_dir<SYS, S, true>), dim3((unsigned)grid), dim3(block), shm, stream, z0, theta, ts_dev, o, rec, nz, sigma,
+                         (int)over, z_out, retcode, nfe, nacc, nrej, ret);
+    else
+      hipLaunchKernelGGL((k_forward_sde_dir<SYS, S, false>), dim3((unsigned)grid), dim3(block), 0, stream, z0, theta, ts_dev, o, rec, nz, sigma,
+                         (int)over, z_out, retcode, nfe, nacc, nrej, ret);
     return LDE_OK;
   });
   return rc != LDE_OK ? rc : hipGetLastError() == hipSuccess ? LDE_OK : LDE_ERR_HIP;

@@ -25,7 +25,7 @@ using lde::DualRec;
 // Three systems: LDE_RHS_KURAMOTO, D = N and NP = 2N + 1 directions q = (φ₀ (N), ω (N), K), N ≤ 3 in 8 lanes and N ≤ 7 in 16 (the forms that
 // take N alone are this system's; 0: N is not served), and LDE_RHS_DOUBLE_PENDULUM, D = 4 and NP = 8 = (ẑ₀ (4), L₁, L₂, m₁, m₂): one 8-lane
 // group with no pad lane; and LDE_RHS_CVS, D = 4 and NP = 6 = (ẑ₀ (4), i_ext, r_mod): one 8-lane group whose lanes 6 and 7 are pad lanes. The
-// forms that take (rhs_kind, state_dim) or a description serve all three.
+// forms that take (rhs_kind, state_dim) or a description serve all three, and the fourth system below (LDE_RHS_STUART_LANDAU).
 constexpr int KURAMOTO_MIN_N = 2, KURAMOTO_MAX_N = 7;
 static constexpr bool dir_state_ok(int N) { return N >= KURAMOTO_MIN_N && N <= KURAMOTO_MAX_N; }
 static constexpr int dir_partials(int N) { return dir_state_ok(N) ? 2 * N + 1 : 0; }
@@ -38,13 +38,25 @@ static int64_t dir_grid(int N, int B) { return (dir_lanes(N, B) + dir_block(N, B
 // … of either system: D = state_dim of a right-hand side of `kind` (0: not a system of these kernels, or a D it does not serve)
 constexpr int DPEND_D = 4, DPEND_P = 4;
 constexpr int CVS_D = 4, CVS_P = 2;
+// LDE_RHS_STUART_LANDAU, the fourth system: N = 1 … 3 oscillators, D = 2N components (x₁ … x_N, y₁ … y_N), NP = 4N + 1 directions
+// q = (ẑ₀ (2N), a (N), ω (N), G) — 5 in 8 lanes (N = 1), 9 and 13 in 16 (N = 2, 3). D = 6 is the first D that is no Kuramoto N and not 4.
+constexpr int SL_MIN_N = 1, SL_MAX_N = 3;
+static constexpr bool sl_state_ok(int D) { return D == 2 || D == 4 || D == 6; }
 static constexpr bool dir_state_ok(int kind, int D) {
-  return kind == LDE_RHS_KURAMOTO ? dir_state_ok(D) : (kind == LDE_RHS_DOUBLE_PENDULUM && D == DPEND_D) || (kind == LDE_RHS_CVS && D == CVS_D);
+  return kind == LDE_RHS_KURAMOTO ? dir_state_ok(D)
+                                  : (kind == LDE_RHS_DOUBLE_PENDULUM && D == DPEND_D) || (kind == LDE_RHS_CVS && D == CVS_D) ||
+                                        (kind == LDE_RHS_STUART_LANDAU && sl_state_ok(D));
 }
 static constexpr int dir_partials(int kind, int D) {
-  return kind == LDE_RHS_KURAMOTO ? dir_partials(D) : !dir_state_ok(kind, D) ? 0 : kind == LDE_RHS_CVS ? CVS_D + CVS_P : DPEND_D + DPEND_P;
+  return kind == LDE_RHS_KURAMOTO ? dir_partials(D)
+         : !dir_state_ok(kind, D) ? 0
+         : kind == LDE_RHS_STUART_LANDAU ? 2 * D + 1
+         : kind == LDE_RHS_CVS ? CVS_D + CVS_P
+                               : DPEND_D + DPEND_P;
 }
-static constexpr int dir_group_width(int kind, int D) { return kind == LDE_RHS_KURAMOTO ? dir_group_width(D) : dir_state_ok(kind, D) ? 8 : 0; }
+static constexpr int dir_group_width(int kind, int D) {
+  return kind == LDE_RHS_KURAMOTO ? dir_group_width(D) : !dir_state_ok(kind, D) ? 0 : (kind == LDE_RHS_STUART_LANDAU && D > 2) ? 16 : 8;
+}
 static int dir_group_width(const lde_problem_desc& d) { return dir_group_width(d.rhs_kind, d.state_dim); }
 static int64_t dir_lanes(const lde_problem_desc& d, int B) { return B < 1 ? 0 : (int64_t)B * dir_group_width(d); }
 static int dir_block(const lde_problem_desc& d, int B) { return dir_lanes(d, B) <= 4096 ? 64 : 256; }
@@ -57,10 +69,13 @@ static bool is_lv(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_LOTK
 static bool is_kuramoto(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_KURAMOTO; }
 static bool is_dpend(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_DOUBLE_PENDULUM; }
 static bool is_cvs(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_CVS; }
-static bool is_dir(const lde_problem_desc& d) { return is_kuramoto(d) || is_dpend(d) || is_cvs(d); }   // the systems of the lane-per-direction kernels
+static bool is_sl(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_STUART_LANDAU; }
+static bool is_dir(const lde_problem_desc& d) { return is_kuramoto(d) || is_dpend(d) || is_cvs(d) || is_sl(d); }   // the systems of the lane-per-direction kernels
 static bool has_pend(const lde_problem_desc& d) { return d.rhs_kind != LDE_RHS_MLP && !is_lv(d) && !is_dir(d); }
 static bool is_sde(const lde_problem_desc& d) { return d.rhs_kind == LDE_RHS_SPENDULUM; }
 static bool sde_solver(int solver) { return solver == LDE_SOLVER_EM || solver == LDE_SOLVER_EULER_HEUN; }
+// the stochastic solve of the lane-per-direction frame (csrc/lde_dual_dir.hip: k_forward_sde_dir): the Stuart–Landau network under a stochastic stepper
+static bool is_dir_sde(const lde_problem_desc& d) { return is_sl(d) && sde_solver(d.solver); }
 
 static int validate(const lde_problem_desc* d, std::string* why) {
   auto bad = [&](const char* m) {
@@ -70,8 +85,10 @@ static int validate(const lde_problem_desc* d, std::string* why) {
   if (!d) return bad("desc is NULL");
   if (d->abi_version != LDE_ABI_VERSION) return bad("abi_version mismatch");
   // 6 and 8 are no right-hand sides and stay refused: tests/lv_host_driver.cpp and tests/kuramoto_host_driver.cpp pin them as "unknown
-  // rhs_kind", so the Kuramoto system took 7 and the double pendulum 9; tests/dpend_host_driver.cpp pins 10 likewise, so CVS took 11
-  if (d->rhs_kind < 0 || d->rhs_kind > LDE_RHS_CVS || d->rhs_kind == 6 || d->rhs_kind == 8 || d->rhs_kind == 10) return bad("unknown rhs_kind");
+  // rhs_kind", so the Kuramoto system took 7 and the double pendulum 9; tests/dpend_host_driver.cpp pins 10 likewise, so CVS took 11, and
+  // tests/cvs_host_driver.cpp pins 12, so the Stuart–Landau network took 13 (nothing pins 14: the next kind takes it)
+  if (d->rhs_kind < 0 || d->rhs_kind > LDE_RHS_STUART_LANDAU || d->rhs_kind == 6 || d->rhs_kind == 8 || d->rhs_kind == 10 || d->rhs_kind == 12)
+    return bad("unknown rhs_kind");
   if (d->state_dim < 1 || d->param_dim < 0 || d->augment_dim < 0) return bad("bad dims");
   if (has_pend(*d) && (d->state_dim != 2 || d->param_dim != 1 || d->augment_dim != 0))
     return bad("pendulum RHS needs state_dim=2, param_dim=1, augment_dim=0");
@@ -83,6 +100,8 @@ static int validate(const lde_problem_desc* d, std::string* why) {
     return bad("LDE_RHS_DOUBLE_PENDULUM needs state_dim=4, param_dim=4, augment_dim=0");
   if (is_cvs(*d) && (d->state_dim != CVS_D || d->param_dim != CVS_P || d->augment_dim != 0))
     return bad("LDE_RHS_CVS needs state_dim=4, param_dim=2, augment_dim=0");
+  if (is_sl(*d) && (!sl_state_ok(d->state_dim) || d->param_dim != d->state_dim + 1 || d->augment_dim != 0))
+    return bad("LDE_RHS_STUART_LANDAU needs state_dim=2N with 1 <= N <= 3, param_dim=2N+1, augment_dim=0");
   if (d->rhs_kind == LDE_RHS_MLP && d->param_dim != 0) return bad("MLP RHS takes no per-trajectory parameters");
   if (has_mlp(*d)) {
     if (d->n_layers < 1 || d->n_layers > LDE_MAX_LAYERS) return bad("n_layers out of range");
@@ -97,6 +116,7 @@ static int validate(const lde_problem_desc* d, std::string* why) {
   if (is_kuramoto(*d) && d->n_layers != 0) return bad("LDE_RHS_KURAMOTO is analytic: n_layers must be 0");
   if (is_dpend(*d) && d->n_layers != 0) return bad("LDE_RHS_DOUBLE_PENDULUM is analytic: n_layers must be 0");
   if (is_cvs(*d) && d->n_layers != 0) return bad("LDE_RHS_CVS is analytic: n_layers must be 0");
+  if (is_sl(*d) && d->n_layers != 0) return bad("LDE_RHS_STUART_LANDAU is analytic: n_layers must be 0");
   if (d->solver != LDE_SOLVER_TSIT5 && d->solver != LDE_SOLVER_RK4 && !sde_solver(d->solver)) return bad("unknown solver");
   if (d->batching != LDE_BATCH_PER_TRAJECTORY && d->batching != LDE_BATCH_COUPLED && d->batching != LDE_BATCH_COUPLED_GLOBAL)
     return bad("unknown batching");
@@ -109,8 +129,9 @@ static int validate(const lde_problem_desc* d, std::string* why) {
     if (why) *why = m;
     return (int)LDE_ERR_UNSUPPORTED;
   };
-  // the stochastic pendulum is served by its own two fixed-step schemes on the dual-number path, and they serve nothing else (include/lde.h)
-  if (sde_solver(d->solver) && !is_sde(*d))
+  // the stochastic pendulum is served by its own two fixed-step schemes on the dual-number path; besides it they serve the Stuart–Landau
+  // network (below) and nothing else (include/lde.h)
+  if (sde_solver(d->solver) && !is_sde(*d) && !is_sl(*d))
     return unsupported("LDE_SOLVER_EM / LDE_SOLVER_EULER_HEUN are stochastic steppers: LDE_RHS_SPENDULUM only");
   if (is_sde(*d)) {
     if (!sde_solver(d->solver)) return unsupported("LDE_RHS_SPENDULUM: no deterministic solver; use LDE_SOLVER_EM or LDE_SOLVER_EULER_HEUN");
@@ -142,6 +163,15 @@ static int validate(const lde_problem_desc* d, std::string* why) {
     if (d->batching != LDE_BATCH_PER_TRAJECTORY) return unsupported("LDE_RHS_CVS: no coupled solve; LDE_BATCH_PER_TRAJECTORY only");
     if (d->sensealg != LDE_SENSE_FORWARD_DUAL)
       return unsupported("LDE_RHS_CVS: only the solve on dual numbers exists for this system (no discrete sweep, no continuous adjoint); use LDE_SENSE_FORWARD_DUAL");
+  }
+  if (is_sl(*d)) {   // … and the Stuart–Landau network, their fourth — and the first with a stochastic solve (k_forward_sde_dir)
+    if (d->batching != LDE_BATCH_PER_TRAJECTORY) return unsupported("LDE_RHS_STUART_LANDAU: no coupled solve; LDE_BATCH_PER_TRAJECTORY only");
+    if (d->sensealg != LDE_SENSE_FORWARD_DUAL)
+      return unsupported("LDE_RHS_STUART_LANDAU: only the solve on dual numbers exists for this system (no discrete sweep, no continuous adjoint); use LDE_SENSE_FORWARD_DUAL");
+    if (sde_solver(d->solver)) {   // the conditions of LDE_RHS_SPENDULUM
+      if (d->adaptive) return unsupported("LDE_RHS_STUART_LANDAU: no adaptive stochastic stepping; pass adaptive=0, dt=h with LDE_SOLVER_EM / LDE_SOLVER_EULER_HEUN");
+      if (!(d->dt > 0) || !std::isfinite(d->dt)) return unsupported("LDE_RHS_STUART_LANDAU: the stochastic steppers are fixed-step; pass a finite dt > 0");
+    }
   }
   if (d->solver == LDE_SOLVER_RK4 && d->adaptive) {
     if (why) *why = "RK4 is fixed-step only here: pass adaptive=0, dt=h";
@@ -392,6 +422,44 @@ static int dir_system_dispatch(const lde_problem_desc& d, F&& f) {
   return dir_system_dispatch_n(d, [&](auto kind, auto n) -> int {
     return lv_dispatch(d.solver, d.adaptive != 0, [&](auto S) -> int { return f(kind, n, S); });
   });
+}
+// … and with (LDE_RHS_STUART_LANDAU, D = 2, 4, 6), the fourth system: what the launchers call now. Once more a layer of its own:
+// tests/cvs_host_driver.cpp hands dir_system_dispatch(_n) a functor that static_asserts the three systems' pairs. dir_all_dispatch serves the
+// deterministic solves (Tsit5 adaptive, Tsit5 fixed-step, RK4 fixed-step: lv_dispatch); a stochastic solver is LDE_ERR_UNSUPPORTED here.
+template <class F>
+static int dir_all_dispatch_n(const lde_problem_desc& d, F&& f) {
+  if (is_sl(d)) {
+    using K = std::integral_constant<int, LDE_RHS_STUART_LANDAU>;
+    switch (d.state_dim) {
+      case 2: return f(K{}, std::integral_constant<int, 2>{});
+      case 4: return f(K{}, std::integral_constant<int, 4>{});
+      case 6: return f(K{}, std::integral_constant<int, 6>{});
+      default: return LDE_ERR_UNSUPPORTED;
+    }
+  }
+  return dir_system_dispatch_n(d, f);
+}
+template <class F>
+static int dir_all_dispatch(const lde_problem_desc& d, F&& f) {
+  return dir_all_dispatch_n(d, [&](auto kind, auto n) -> int {
+    return lv_dispatch(d.solver, d.adaptive != 0, [&](auto S) -> int { return f(kind, n, S); });
+  });
+}
+// The template arguments of k_forward_sde_dir (csrc/lde_dual_dir.hip): f(D, SOLVER) for the Stuart–Landau network's D = 2, 4, 6 × {LDE_SOLVER_EM,
+// LDE_SOLVER_EULER_HEUN} with adaptive = 0 — what validate() admits for the stochastic solve — and nothing else.
+template <class F>
+static int dir_sde_dispatch(const lde_problem_desc& d, F&& f) {
+  if (!is_dir_sde(d) || d.adaptive) return LDE_ERR_UNSUPPORTED;
+  auto with_solver = [&](auto n) -> int {
+    if (d.solver == LDE_SOLVER_EM) return f(n, std::integral_constant<int, LDE_SOLVER_EM>{});
+    return f(n, std::integral_constant<int, LDE_SOLVER_EULER_HEUN>{});
+  };
+  switch (d.state_dim) {
+    case 2: return with_solver(std::integral_constant<int, 2>{});
+    case 4: return with_solver(std::integral_constant<int, 4>{});
+    case 6: return with_solver(std::integral_constant<int, 6>{});
+    default: return LDE_ERR_UNSUPPORTED;
+  }
 }
 
 // Which mapping serves a solve under LDE_SENSE_FORWARD_DUAL (csrc/lde_dual.h: dual_block switches on this, for every system and for the

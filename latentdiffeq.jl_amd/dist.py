@@ -372,7 +372,7 @@ def diffeq_layer_sharded(decoder, l_hat, t, rank: Optional[int] = None, world: O
         z0, theta = l_hat
         local = (shard_columns(z0, rank, world, 1), shard_columns(theta, rank, world, 1))
         if hasattr(decoder.diffeq, "first_trajectory"):
-            # SPendulum: the noise is indexed by the GLOBAL trajectory — the shards draw the unsharded solve's path
+            # SPendulum, StuartLandau: the noise is indexed by the GLOBAL trajectory — the shards draw the unsharded solve's path
             decoder.diffeq.first_trajectory = shard_bounds(z0.shape[1], rank, world)[0]
     else:
         local = shard_columns(l_hat, rank, world, 1)
