@@ -23,7 +23,15 @@ k_pend_adjoint_disc_tp<0, 0> (hipcc -O3 --offload-arch=gfx950 -S; before → aft
 s_cbranch_execz 21 → 15, v_mov_b64 30 → 7; s_load 11 in eight groups with seven s_waitcnt lgkmcnt(0) in series in front of the round loop
 → 9, all in front of the first global_load with one wait; no exec-masked block around a first-round load (the nine global_load follow
 each other, one s_waitcnt vmcnt(0)); on the one-trip path of the save-time phase ten ds_read_b64 and one s_waitcnt lgkmcnt(0) in front
-of the four bodies and no s_and_saveexec_b64 inside them."""
+of the four bodies and no s_and_saveexec_b64 inside them.
+
+Round 8 (profiles/r8_disc_tp_stamps.txt): tbeg, tend and jscale from the kernel arguments (the f64 division in flight with the loads), the
+failure tests as scalar selects with one scalar branch around the rounds, the later rounds' loads behind a scalar `r > 0` at clamped
+indices, the save-time trip speculative in front of ONE vote: entry → sweep done 5746 → 5458 cycles (2.48 → 2.37 µs). The stamps mean what
+they meant: the entry's constants and the round's top lie between stamps 1 and 2 ("stage points": 945 → 688), and in THIS build stamp 2's
+store holds the stage phase in front of the save times; in the product build the compiler sinks that phase below the vote, into the block
+of c_tau. Holding it in front of the vote there (one block for both phases) regroups the vectorised multiply-adds and moves bits, so it
+is not done, and no stamp spans two overlapping phases."""
 import ctypes as C
 import os
 import subprocess

@@ -1937,8 +1937,9 @@ __global__ void __launch_bounds__(64) k_pend_adjoint_disc_tp(const float2* __res
   const int32_t* const rec_n = o.rec.n;
   const double *const rec_t = o.rec.t, *const rec_dt = o.rec.dt;
   const float2* const rec_y = reinterpret_cast<const float2*>(o.rec.y);
+  const double tbeg = o.t_first, tend = o.t_last;   // ts[0], ts[T − 1] as the host read them (csrc/lde_host.h: make_opts): no LDS round trip for them behind the barrier
   asm volatile("" ::"s"(z_out), "s"(theta), "s"(ts_g), "s"(dz_out), "s"(dz0), "s"(dtheta), "s"(st_nfe), "s"(st_nacc), "s"(st_nrej), "s"(st_ret),
-               "s"(rec_n), "s"(rec_t), "s"(rec_dt), "s"(rec_y), "s"(T), "s"(B), "s"(cap), "s"(nwg));
+               "s"(rec_n), "s"(rec_t), "s"(rec_dt), "s"(rec_y), "s"(T), "s"(B), "s"(cap), "s"(nwg), "s"(tbeg), "s"(tend));
   // trajectory ↔ workgroup as in k_pend_forward_sh (the grid is a multiple of 8): the workgroup lands on the XCD whose L2 holds the
   // record and the ẑ the forward launch wrote for this trajectory
   const int b = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
@@ -1966,6 +1967,10 @@ __global__ void __launch_bounds__(64) k_pend_adjoint_disc_tp(const float2* __res
   int nsv = rec_n[b];
   float L = theta[b];
   float2 y0 = z_out[b];
+  // where a uniform grid would have a save time (a first guess, checked): an IEEE f64 division of kernel arguments — a dozen dependent
+  // instructions that now run while the loads above are in flight (pinned in front of their wait), not behind it
+  double jscale = (double)(T - 1) / (tend - tbeg);
+  asm volatile("" : "+v"(jscale));
   asm volatile("" : "+v"(tsv), "+v"(dv.x), "+v"(dv.y), "+v"(t0r), "+v"(dt0r), "+v"(tn0r), "+v"(y0r.x), "+v"(y0r.y), "+v"(nsv), "+v"(L), "+v"(y0.x), "+v"(y0.y));
   const int ns = __builtin_amdgcn_readfirstlane(nsv);
   if (j0ok) {
@@ -1979,24 +1984,28 @@ __global__ void __launch_bounds__(64) k_pend_adjoint_disc_tp(const float2* __res
   __syncthreads();
   PPROF(1);
   const float ngl = -10.0f / L, gl2 = 10.0f / (L * L);
-  int ret = LDE_RET_SUCCESS;
-  if (!isfinite(y0.x) || !isfinite(y0.y)) ret = LDE_RET_NONFINITE;      // a failed forward trajectory: zero gradient [REF GOKU.jl:114]
-  else if (T > 1 && (ns < 1 || ns > cap)) ret = LDE_RET_MAXITERS;      // no usable record: NaN gradient (never a truncated sweep)
+  // the failure tests on wave-uniform words (every lane loaded the same y_0 and step count): scalar compares and selects, and ONE
+  // scalar branch around the rounds — not five branches on fresh vector compares
+  const int y0xi = __builtin_amdgcn_readfirstlane(__float_as_int(y0.x)), y0yi = __builtin_amdgcn_readfirstlane(__float_as_int(y0.y));
+  const bool y0bad = ((y0xi & 0x7f800000) == 0x7f800000) | ((y0yi & 0x7f800000) == 0x7f800000);   // an exponent of all ones: ±∞ or NaN
+  const bool norec = (T > 1) & ((ns < 1) | (ns > cap));
+  // a failed forward trajectory: zero gradient [REF GOKU.jl:114]; no usable record: NaN gradient (never a truncated sweep)
+  const int ret = y0bad ? LDE_RET_NONFINITE : (norec ? LDE_RET_MAXITERS : LDE_RET_SUCCESS);
   float ax = 0.f, ay = 0.f, gth = 0.f;   // wave-uniform: the cotangent below the steps done so far, dθ
-  if (ret == LDE_RET_SUCCESS && T > 1) {
-    const double tbeg = s_t[0], tend = s_t[T - 1];
-    const double jscale = (double)(T - 1) / (tend - tbeg);   // where a uniform grid would have a save time (a first guess, checked)
+  if ((ret == LDE_RET_SUCCESS) & (T > 1)) {
     const float e0x = tau == 0 ? 1.f : 0.f, e0y = tau == 1 ? 1.f : 0.f, pth = tau == 2 ? gl2 : 0.f;
     for (int r = (ns - 1) / DTP_STEPS; r >= 0; r--) {
       const int s = r * DTP_STEPS + sl;
       const bool act = sl < DTP_STEPS && s < ns;
       double t = t0r, dt = dt0r, tnew = tn0r;
       float2 yv = y0r;
-      if (r > 0 && act) {
-        t = rec_t[(size_t)s * B + b];
-        dt = rec_dt[(size_t)s * B + b];
-        yv = rec_y[(size_t)s * B + b];
-        if (s + 1 < ns) tnew = rec_t[(size_t)(s + 1) * B + b];
+      if (__builtin_expect(r > 0, 0)) {   // a scalar branch, not taken in round 0 (the only round of records up to 21 steps). The lane condition is
+        // inside it as clamped indices (1 ≤ ns ≤ cap here): what a lane without a step loads is zeroed or never used, as at the entry
+        const int sc = min(s, ns - 1), sc1 = min(s + 1, ns - 1);
+        t = rec_t[(size_t)sc * B + b];
+        dt = rec_dt[(size_t)sc * B + b];
+        yv = rec_y[(size_t)sc * B + b];
+        tnew = rec_t[(size_t)sc1 * B + b];
       }
       const bool last = s == ns - 1;
       if (last) tnew = tend;
@@ -2062,8 +2071,13 @@ __global__ void __launch_bounds__(64) k_pend_adjoint_disc_tp(const float2* __res
       //  are compares combined with & and | (no short-circuit: && and || on fresh compares become exec-mask blocks), their results
       //  selects — a save time outside the step, or a lane without a step, enters with weight zero on a Θ made finite (h = 0: 1/h = ∞) —
       //  and the four bodies are independent on register pairs (x, y); only the ten running sums chain from body to body. What is rare
-      //  sits behind wave votes, out of the way: a grid the guess is wrong on, and steps with more than four save times per lane.
-      //  The phase at the metric's shape: 2 011 → ≈ 1 575 cycles, abl/disc_tp_prof.py; same sums in the same order: bit-identical results.)
+      //  sits behind ONE wave vote, out of the way: a grid the guess is wrong on, and steps with more than four save times per lane. The
+      //  trip runs speculatively on the guessed index in front of that vote; a lane whose guess was wrong drops its sums and runs the
+      //  trip again from the index it walked to (its speculative reads were clamped like every other).
+      //  The phase at the metric's shape: 2 011 → ≈ 1 575 cycles, abl/disc_tp_prof.py; same sums in the same order: bit-identical results.
+      //  The stage phase above is NOT held in front of the vote: the compiler sinks it into the block of c_τ below, and an empty asm that
+      //  keeps it here makes the vectoriser regroup its multiply-adds (other pairs fused: dz0, dθ move in the last bits), as does any
+      //  reordering of that block — DESIGN.md §4.2c, round 8.)
       f32x2 ev = {0.f, 0.f}, ynv = {0.f, 0.f}, c1 = {0.f, 0.f}, c2 = {0.f, 0.f}, c3 = {0.f, 0.f}, c4 = {0.f, 0.f};   // Tsit5: moments of Θ; RK4: the four Hermite sums
       {
         // the last save time ≤ tnew: where a uniform grid has it (exact there: the index in f64 with a margin far below a grid spacing),
@@ -2117,19 +2131,20 @@ __global__ void __launch_bounds__(64) k_pend_adjoint_disc_tp(const float2* __res
         j -= tau;   // the step's three lanes share its save times: lane τ takes the τ-th, (τ + 3)-th, … from the last one down
         fetch();
         asm volatile("" : "+v"(ttop), "+v"(tup), "+v"(tq[0]), "+v"(tq[1]), "+v"(tq[2]), "+v"(tq[3]), "+v"(dq[0]), "+v"(dq[1]), "+v"(dq[2]), "+v"(dq[3]));   // (all six reads issued, one wait)
-        const bool ragged = act & !((ttop <= tnew) & ((jg == T - 1) | (tup > tnew)));
-        if (__builtin_expect(__any(ragged), 0)) {   // (a ragged grid: walk to it)
-          if (ragged) {
+        const bool ragged = act & !((ttop <= tnew) & ((jg == T - 1) | (tup > tnew)));   // the guess is not the grid's answer: this lane's first trip is void
+        bool more = trip();   // (speculative: on the guessed index, in front of the vote)
+        if (__builtin_expect(__any(ragged | more), 0)) {   // ---- the one vote; what follows it is out of line
+          if (ragged) {   // (a ragged grid: drop the speculative trip's sums, walk to the right index, run the trip again)
+            const f32x2 zero = {0.f, 0.f};
+            ev = ynv = c1 = c2 = c3 = c4 = zero;
             j = jg;
             while (j < T - 1 && s_t[j + 1] <= tnew) j++;
             while (j > 0 && s_t[j] > tnew) j--;
             j -= tau;
             fetch();
+            more = trip();
           }
-        }
-        bool more = trip();
-        if (__builtin_expect(__any(more), 0)) {   // (more than four save times of the step for one of its lanes)
-          while (more) {
+          while (more) {   // (more than four save times of the step for one of its lanes)
             j -= 12;
             fetch();
             more = trip();
