@@ -199,7 +199,7 @@ __global__ void __launch_bounds__(256) k_forward_dual_dir(const float* __restric
       if (iters++ >= o.maxiters) { ret = LDE_RET_MAXITERS; break; }
       double dtp = dt;
       bool last = false;
-      if (t + dt >= tend - 1e-12 * fabs(tend)) { dt = tend - t; last = true; }
+      if (t + dt >= tend - 1e-12 * fmax(fabs(tend), dtmax)) { dt = tend - t; last = true; }
       const float h = (float)dt;
       float EEst = 0.f;
       f.anchor(y);

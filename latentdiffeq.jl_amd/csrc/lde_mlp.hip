@@ -485,7 +485,7 @@ __global__ void __launch_bounds__(NT) k_mlp_forward(MlpDims dm, KOpts o, FwdArgs
         double dt = c->dt[col];
         const double t = c->t[col];
         int last = 0;
-        if (t + dt >= tend - 1e-12 * fabs(tend)) { dt = tend - t; last = 1; }
+        if (t + dt >= tend - 1e-12 * fmax(fabs(tend), dtmax)) { dt = tend - t; last = 1; }
         c->last[col] = last;
         c->tnew[col] = last ? tend : t + dt;
         c->h[col] = (float)dt;

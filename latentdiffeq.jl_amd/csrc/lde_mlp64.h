@@ -313,7 +313,7 @@ __device__ __forceinline__ void mlp64_body(const MlpDims& dm, const KOpts& o, co
       if (!ADJ) {
         double d = dt;
         last = 0;
-        if (t + d >= tend - 1e-12 * fabs(tend)) { d = tend - t; last = 1; }
+        if (t + d >= tend - 1e-12 * fmax(fabs(tend), dtmax)) { d = tend - t; last = 1; }
         tnew = last ? tend : t + d;
         h = (float)d;
         wq = (float)d;

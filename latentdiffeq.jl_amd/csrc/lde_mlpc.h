@@ -210,7 +210,7 @@ __global__ void __launch_bounds__(256, 1) k_mlpc(MlpDims dm, CDims cd, KOpts o, 
       if (!ADJ) {
         double d = dt;
         last = 0;
-        if (t + d >= tend - 1e-12 * fabs(tend)) { d = tend - t; last = 1; }
+        if (t + d >= tend - 1e-12 * fmax(fabs(tend), dtmax)) { d = tend - t; last = 1; }
         tnew = last ? tend : t + d;
         h = (float)d;
         wq = (float)d;

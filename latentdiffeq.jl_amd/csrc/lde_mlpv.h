@@ -557,7 +557,7 @@ __global__ void __launch_bounds__(NT, (KF > 0 ? 2 : 1)) k_mlpv(MlpDims dm, VecDi
       if (!ADJ) {
         double d = dt;
         last = 0;
-        if (t + d >= tend - 1e-12 * fabs(tend)) { d = tend - t; last = 1; }
+        if (t + d >= tend - 1e-12 * fmax(fabs(tend), dtmax)) { d = tend - t; last = 1; }
         tnew = last ? tend : t + d;
         h = (float)d;
         wq = (float)d;

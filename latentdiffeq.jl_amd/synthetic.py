@@ -15,6 +15,22 @@ def time_grid(T: int = 50, dt: float = 0.05, t0: float = 0.0):
     return t0 + dt * np.arange(T, dtype=np.float64)
 
 
+def shifted_grids(T: int = 33, spacing: float = 1.0 / 16.0):
+    """The time-translation known answer's grids: base = (0 … T−1)·spacing (a power of two: 1/16) and base + c for c = ±1024, +2²⁰, −base[−1] (ends exactly at 0) and
+    −base[T//2] (contains 0), as an ordered dict name → grid with "base" first. Every entry and every sum is a dyadic rational well inside
+    53 bits, so each shifted grid has bit-identical differences (asserted) and, with a dyadic dt, every time a stepping loop forms is exact:
+    an autonomous right-hand side must then give bit-identical results on every grid."""
+    assert np.frexp(spacing)[0] == 0.5 and spacing <= 1.0, "a power of two"
+    base = np.arange(T, dtype=np.float64) * spacing
+    shifts = {"base": 0.0, "plus_1024": 1024.0, "minus_1024": -1024.0, "plus_2p20": float(2 ** 20), "ends_at_0": -base[-1],
+              "contains_0": -base[T // 2]}
+    grids = {name: base + c for name, c in shifts.items()}
+    for name, g in grids.items():
+        assert np.array_equal(np.diff(g), np.diff(base)) and np.array_equal(g - shifts[name], base), name
+    assert grids["ends_at_0"][-1] == 0.0 and grids["contains_0"][T // 2] == 0.0
+    return grids
+
+
 def cotangent(T: int, B: int, Dp: int, seed: int = 2, dtype=np.float32):
     rng = np.random.default_rng(seed)
     return (rng.standard_normal((T, B, Dp)) / (B * T)).astype(dtype)

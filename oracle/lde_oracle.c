@@ -500,7 +500,7 @@ static void solve_forward(ode_fn fn, void* ctx, int64_t n, const real* y0, const
         t = rec->t[ntr];
         dt = rec->dt[ntr];
         last = ntr == *rec->n - 1;
-      } else if (t + dt >= tend - 1e-12 * fabs(tend)) { dt = tend - t; last = 1; }
+      } else if (t + dt >= tend - 1e-12 * fmax(fabs(tend), dtmax)) { dt = tend - t; last = 1; }   /* (scaled by the span as dtmin is: a grid that ends at 0 keeps its guard) */
       real EEst = 0;
       if (o->solver == LDE_SOLVER_TSIT5)
         EEst = tsit5_attempt(fn, ctx, &w, t, dt, y, 0, 0.0, o, st);
@@ -1507,7 +1507,7 @@ static int dual_solve(int kind, real L, const real* z0, const double* ts, int T,
       if (presc) {
         if (ntr >= *rec->n) { ret = LDE_RET_MAXITERS; break; }
         t = rec->t[ntr]; dt = rec->dt[ntr]; last = ntr == *rec->n - 1;
-      } else if (t + dt >= tend - 1e-12 * fabs(tend)) { dt = tend - t; last = 1; }
+      } else if (t + dt >= tend - 1e-12 * fmax(fabs(tend), dtmax)) { dt = tend - t; last = 1; }
       const real h = (real)dt;
       const int S = o->solver == LDE_SOLVER_TSIT5 ? 6 : 4;   /* index of the FSAL slope */
       if (o->solver == LDE_SOLVER_TSIT5) {

@@ -331,7 +331,7 @@ class Oracle:
 # synthetic-input generators live in the product package (pure numpy); re-exported for the tests
 import sys as _sys
 _sys.path.insert(0, os.path.dirname(_HERE))
-from latentdiffeq_amd.synthetic import cotangent, mlp_weights, pendulum_inputs, time_grid  # noqa: E402,F401
+from latentdiffeq_amd.synthetic import cotangent, mlp_weights, pendulum_inputs, shifted_grids, time_grid  # noqa: E402,F401
 
 
 # ---- dense chains either side of the solve (oracle/lde_chain_oracle.c) ------------------------------------------

@@ -142,7 +142,7 @@ def _group(sys, y, th, ts, solver, adaptive, dt_fixed, steps, o, dtype):
                         ret = RET_MAXITERS
                         break
                     t, dt, last = float(steps[0][ntr]), float(steps[1][ntr]), ntr == len(steps[0]) - 1
-                elif t + dt >= tend - 1e-12 * abs(tend):
+                elif t + dt >= tend - 1e-12 * max(abs(tend), dtmax):
                     dt, last = tend - t, True
                 h = dtype(np.float32(dt))          # the state advances by the f32 of the f64 step, whatever the arithmetic
                 EEst = dtype(0)
